@@ -16,7 +16,9 @@ per GPU, 128x416, fp32, synthetic KITTI-shaped inputs resident in HBM.  With N>1
 each rank trains its own batch-20 shard and the gradient arena is all-reduced
 with RCCL (weak scaling).  Rank 0 prints ONE JSON line.
 
-The same line carries
+A plain run does only what that line's headline figure needs: set up, warm up, time the --steps steps, print `value` (images/s),
+`ms_per_step` and the workload's description.  --dump-outputs DIR also writes what the last timed step computed (loss, depth
+map, a seeded sample of the model's state after Adam) as DIR/<name>.npy.  With --full the same line also carries
   step_kernel_breakdown -- device time per kernel symbol over two steps after the timed region (torch.profiler): decides which
                   kernel `roofline` describes;
   roofline     -- the dominant kernel of the step by that measurement: the per-bin complex GEMMs of the frequency-domain layers
@@ -596,6 +598,7 @@ def infer_main(args):
     if world > 1:
         torch.distributed.barrier()
     if rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"depth": o}) if args.dump_outputs else None
         ms = dt / args.steps * 1e3
         rec = {"metric": "inference images/sec at 256x832 batch=64 (legacy AutoEncoder forward)",
                "value": round(B * world * args.steps / dt, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -609,15 +612,18 @@ def infer_main(args):
                           "direct_conv_equiv_note": "throughput label: direct-convolution FLOPs / time (fp32 k>=5 layers run in "
                                                     "the frequency domain, 3x3 as Winograd); not a utilisation",
                           "out_checksum": round(float(o.double().abs().mean().item()), 6)}}
+        if dumped is not None:
+            rec["outputs_dumped"] = dumped
         flush_c_stdio()
         print(json.dumps(rec), flush=True)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
 
-def make_train_step(mode, dtype, dev, batch, fast_guide=False, latent_grad=False, use_graph=False):
+def make_train_step(mode, dtype, dev, batch, fast_guide=False, latent_grad=False, use_graph=False, keep=None):
     """One full training step of `mode` (DtoD / RtoD) as a closure over a resident batch: forward, fused losses,
-    backward (tape), gradient all-reduce when data-parallel, fused Adam.  Returns (step, graphed-or-None)."""
+    backward (tape), gradient all-reduce when data-parallel, fused Adam.  Returns (step, graphed-or-None).  A dict passed as
+    `keep` receives the model ("model") and, at every step, the model's output ("out"; no copy: the step allocates a new one)."""
     import gdn_amd.AE_model_unet as M
     from gdn_amd import distributed as D
     from gdn_amd import trainer as T
@@ -638,12 +644,16 @@ def make_train_step(mode, dtype, dev, batch, fast_guide=False, latent_grad=False
         if latent_grad:
             G.requires_grad_(False)
     opt = Adam(model.parameters(), 2e-5, [0.9, 0.999], eps=1e-08, weight_decay=5e-4, capturable=use_graph)
+    if keep is not None:
+        keep["model"] = model
 
     from gdn_amd import tracing
 
     def step_fn(depth, rgb, sparse):
         tracing.push("gdn.forward")
         out = model(depth if mode == "DtoD" else rgb, istrain=False)
+        if keep is not None:
+            keep["out"] = out
         tracing.pop()
         tracing.push("gdn.losses")
         if mode == "DtoD":
@@ -773,6 +783,41 @@ def flush_c_stdio():
     except OSError:
         pass
     sys.stdout.flush()
+
+
+DUMP_BYTES = 60 * 2 ** 20         # --dump-outputs: all arrays together stay under 64 MB (npy headers included)
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_BYTES, seed=0):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as DIR/<name>.npy, float64 kept, everything else as float32.
+    The arrays are taken smallest first and each gets an equal share of what is left of `cap`; one larger than its share is
+    written as a fixed sample instead (flattened, `share` elements at sorted indices drawn from a generator seeded with
+    `seed`: the same indices in every run for the same size).  Returns {name: [elements written, elements of the array]}."""
+    import numpy as np
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    items = sorted(((name, t.detach()) for name, t in arrays.items()), key=lambda kv: kv[1].numel())
+    left, done = cap, {}
+    for i, (name, t) in enumerate(items):
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        share = left // (len(items) - i) // t.element_size()
+        n = t.numel()
+        if n > share:
+            idx = torch.randint(0, n, (share,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.contiguous().cpu().numpy()
+        np.save(d / (name + ".npy"), a)
+        left -= a.nbytes
+        done[name] = [int(a.size), int(n)]
+    return done
+
+
+def train_outputs(keep, loss):
+    """What a caller of the training step has after its last step: the loss, the model's output (the depth map), and the
+    model's state (parameters after Adam, BatchNorm running statistics; every floating tensor of state_dict() in its order,
+    flattened into one vector)."""
+    state = [v.detach().reshape(-1).float() for v in keep["model"].state_dict().values() if v.is_floating_point()]
+    return {"loss": loss.detach().reshape(1), "depth": keep["out"], "state": torch.cat(state)}
 
 
 def timed(step, steps, warmup):
@@ -955,11 +1000,18 @@ def main():
     ap.add_argument("--no-overlap", action="store_true",
                     help="data parallel: one all-reduce of the whole gradient arena after backward instead of the bucketed "
                          "reduction overlapped with it (= GDN_OVERLAP_ALLREDUCE=0), to read a scaling curve against")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's own measurement, also run everything else the record can carry: roofline "
+                         "probes and the step's kernel breakdown, gpu_state, mfma_util, other_configs, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, under "
+                         "64 MB in all; a fixed, seeded sample of an array that does not fit)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline records out")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)   # CPU test of the self-launcher
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short RtoD fp32 / RtoD bf16 / inference measurements appended as other_configs (N=1 only)")
+                    help="with --full: skip the short RtoD fp32 / RtoD bf16 / inference measurements appended as other_configs "
+                         "(N=1 only)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -992,8 +1044,9 @@ def main():
     B = args.batch
     depth, rgb, sparse = synthetic_batch(B, 128, 416, seed=rank, device=dev)
 
+    keep = {} if args.dump_outputs and rank == 0 else None
     step, graphed = make_train_step(args.mode, args.dtype, dev, (depth, rgb, sparse), fast_guide=args.fast_guide,
-                                    latent_grad=args.latent_grad, use_graph=args.graph and world == 1)
+                                    latent_grad=args.latent_grad, use_graph=args.graph and world == 1, keep=keep)
 
     def barrier():
         if world > 1:
@@ -1037,6 +1090,9 @@ def main():
     t_tail = time.perf_counter()
 
     if rank == 0:
+        # first, before anything below runs more steps on this model: what the timed path computed in its last step
+        dumped = dump_outputs(args.dump_outputs, train_outputs(keep, loss)) if keep is not None else None
+        keep = None
         ms = dt / args.steps * 1e3
         value = B * world * args.steps / dt
         gflop_img = DTOD_TRAIN_GFLOP_PER_IMG if args.mode == "DtoD" else (1595.2 if args.fast_guide else 1922.6)
@@ -1064,20 +1120,23 @@ def main():
                                      "rms(HIP - fp64) <= 1.1 x rms(oracle fp32 - fp64); tensors 1e-3 relative + 1e-4 of max; "
                                      "gradients 2e-2 relative L2; bf16: <= 1.25 x the bf16 emulation's own drift"},
         }
-        if not args.no_roofline and args.dtype == "fp32":
-            try:
-                roofline_records(rec, dev, B, step, world)
-            except Exception as e:  # noqa: BLE001 -- a failed probe must not lose the measured line
-                rec["roofline_error"] = "%s: %s" % (type(e).__name__, e)
-        rec["gpu_state"] = gpu_state()
-        if args.dtype == "fp32" and args.mode == "DtoD":
-            rec["mfma_util"] = step_mfma_util()
-        if world == 1 and not args.no_other_configs and args.mode == "DtoD" and args.dtype == "fp32" and B == 20:
-            del step
-            torch.cuda.empty_cache()
-            rec["other_configs"] = other_configs(dev, B, depth, rgb, sparse)
-        if world == 1 and not args.no_cpu_baseline:
-            rec["cpu_baseline"] = cpu_baseline(B)
+        if dumped is not None:
+            rec["outputs_dumped"] = dumped
+        if args.full:
+            if not args.no_roofline and args.dtype == "fp32":
+                try:
+                    roofline_records(rec, dev, B, step, world)
+                except Exception as e:  # noqa: BLE001 -- a failed probe must not lose the measured line
+                    rec["roofline_error"] = "%s: %s" % (type(e).__name__, e)
+            rec["gpu_state"] = gpu_state()
+            if args.dtype == "fp32" and args.mode == "DtoD":
+                rec["mfma_util"] = step_mfma_util()
+            if world == 1 and not args.no_other_configs and args.mode == "DtoD" and args.dtype == "fp32" and B == 20:
+                del step
+                torch.cuda.empty_cache()
+                rec["other_configs"] = other_configs(dev, B, depth, rgb, sparse)
+            if world == 1 and not args.no_cpu_baseline:
+                rec["cpu_baseline"] = cpu_baseline(B)
         rec["tail_s"] = round(time.perf_counter() - t_tail, 2)      # rank 0's time between the closing barrier and this line
         flush_c_stdio()
         print(json.dumps(rec), flush=True)

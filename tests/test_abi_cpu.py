@@ -167,7 +167,8 @@ def test_host_planning_code_under_asan():
     lib = mod.build_asan()
     rt = mod.asan_runtime()
     assert rt and os.path.exists(rt), "clang ASan runtime not found"
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", GDN_HIP_LIB=str(lib),
+    pre = os.environ.get("LD_PRELOAD")       # the ASan runtime must come first; what the environment preloads stays loaded
+    env = dict(os.environ, LD_PRELOAD=rt + (":" + pre if pre else ""), ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", GDN_HIP_LIB=str(lib),
                PYTHONPATH=os.pathsep.join([str(REPO / "gdn-pytorch_amd"), str(REPO)]))
     r = subprocess.run([sys.executable, str(REPO / "tests" / "asan_host_queries.py")], env=env, capture_output=True, text=True,
                        timeout=600)

@@ -604,7 +604,7 @@ def _no_error_keys(o, path=""):
 
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])
 def test_bench_gpus_2_default_flags_rooflines_on(gpu, launcher):
-    """The command the driver's scaling run takes: `bench.py --gpus 2` WITHOUT --no-roofline.  After the
+    """`bench.py --gpus 2 --full`: the multi-rank command with the rooflines on.  After the
     closing barrier the other rank leaves the process group; rank 0 must not run another training step (it holds the gradient
     all-reduce -- under RCCL a collective issued alone never returns, under gloo it raises): one JSON line, no 'error' anywhere
     in it, the breakdown marked as an N = 1 property, a live `roofline`, and the tail after the timed region short.  1-GPU box:
@@ -619,7 +619,7 @@ def test_bench_gpus_2_default_flags_rooflines_on(gpu, launcher):
     base = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     multi = torch.cuda.device_count() >= 2
     env = base if multi else dict(base, GDN_SINGLE_DEVICE="1", GDN_DIST_BACKEND="gloo")
-    tail = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2"]
+    tail = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--full"]
     if launcher == "self":
         cmd = [sys.executable, str(root / "bench.py"), *tail]
     else:
@@ -654,7 +654,7 @@ def test_bench_forced_rccl_one_rank_rooflines_on(gpu):
     env = dict(os.environ, GDN_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29527", RANK="0", LOCAL_RANK="0",
                WORLD_SIZE="1")
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline", "--no-other-configs"],
+                        "--full", "--no-cpu-baseline", "--no-other-configs"],
                        capture_output=True, text=True, env=env, timeout=900, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -667,6 +667,41 @@ def test_bench_forced_rccl_one_rank_rooflines_on(gpu):
     for k in ("roofline", "roofline_direct3x3", "roofline_fftconv"):
         assert rec[k]["achieved"] > 0, k
     assert "largest single symbol" in rec["roofline"]["chosen_by"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(gpu, tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline fields, K timed steps, none of the extra measurements.
+    --dump-outputs writes the last timed step's loss, depth map and a sample of the model state as float32 .npy under 64 MB,
+    and a second run with the same arguments writes the same bits (same inputs, same model, deterministic step)."""
+    import json
+    import pathlib
+    import subprocess
+    import sys
+    import numpy as np
+    root = pathlib.Path(__file__).resolve().parent.parent
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=str(root))
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in rec, k
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["dtype"] == "f32"
+        for k in ("roofline", "step_kernel_breakdown", "gpu_state", "mfma_util", "other_configs", "cpu_baseline"):
+            assert k not in rec, k
+        files = sorted(d.glob("*.npy"))
+        assert [f.stem for f in files] == ["depth", "loss", "state"]
+        assert sum(f.stat().st_size for f in files) <= 64 * 10 ** 6
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["depth"].shape == (4, 1, 128, 416)
+        assert abs(float(arrs["loss"][0]) - rec["config"]["final_loss"]) <= 1e-5 * abs(rec["config"]["final_loss"]) + 1e-6
+        assert rec["outputs_dumped"]["state"][0] == arrs["state"].size < rec["outputs_dumped"]["state"][1]
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def _diag_child(script, args, timeout=600):

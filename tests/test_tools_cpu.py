@@ -74,3 +74,29 @@ def test_bench_kernel_family_table():
     assert f("fft2d_fwd_kernel") == f("ifft_rows_overlap_kernel") == f("fft_wgrad_taps_kernel") == "fft_transforms"
     assert f("wino_gemm_kernel") == "wino_gemm_f32" and f("wino4_input_kernel") == "winograd_transforms"
     assert f("bn_bwd_apply_kernel") == "batchnorm" and f("conv_ring2_bf16") == "bf16_ring" and f("berhu_kernel") == "other"
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: arrays that fit are written whole (float32, float64 kept), a larger one as a sample at the same
+    seeded indices in every run, and all files together stay under the 64 MB cap."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    g = torch.Generator().manual_seed(3)
+    arrays = {"loss": torch.tensor([1.5], dtype=torch.float64), "depth": torch.rand(2, 1, 8, 16, generator=g),
+              "state": torch.rand(24 * 2 ** 20, generator=g)}
+    got = []
+    for run in range(2):
+        d = tmp_path / str(run)
+        done = bench.dump_outputs(d, arrays)
+        files = {f.stem: np.load(f) for f in d.glob("*.npy")}
+        assert set(files) == set(arrays)
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64 * 10 ** 6
+        assert files["loss"].dtype == np.float64 and files["loss"][0] == 1.5
+        assert files["depth"].dtype == np.float32 and np.array_equal(files["depth"], arrays["depth"].numpy())
+        s = files["state"]
+        assert s.dtype == np.float32 and s.ndim == 1 and done["state"] == [s.size, 24 * 2 ** 20] and 0 < s.size < 24 * 2 ** 20
+        assert np.isin(s[:1000], arrays["state"].numpy()).all()
+        got.append(s)
+    assert np.array_equal(got[0], got[1])

@@ -9,5 +9,4 @@ bash tools/prof_step.sh r06f_rtod_bf16 --mode RtoD --dtype bf16 > /dev/null 2>&1
 bash tools/prof_step.sh r06f_dtod_bf16 --dtype bf16 > /dev/null 2>&1
 for t in dtod_fp32 rtod_bf16 dtod_bf16; do echo "== $t"; head -3 gpurun_out/prof_step_r06f_$t/step_summary.txt; cat gpurun_out/prof_step_r06f_$t/mfma16_vs_fft.txt 2>/dev/null | tail -3; done
 python -c "import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")" 2>&1 | tail -1
-python bench.py > gpurun_out/r06f_bench.json 2> gpurun_out/r06f_bench.err
-tail -c 6000 gpurun_out/r06f_bench.json
+python bench.py --full 2>&1 | tail -c 6000
