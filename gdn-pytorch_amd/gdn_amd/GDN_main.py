@@ -13,6 +13,11 @@ The KITTI/NYU file pipeline (datasets_list.py / transform_list.py) is host I/O
 outside the hot path: pass ``--synthetic`` for KITTI-shaped random batches, or
 call ``run(args, train_loader, val_loader)`` with loaders that yield the
 reference's sample contract ``(gt[B,1,H,W], rgb[B,3,H,W], sparse[B,1,H,W])`` in [-1,1].
+
+Evaluation (--mode DtoD_test / RtoD_test, :234-307): ``--real_test`` evaluates KITTI on the Eigen test split
+(TestFolder) instead of val.txt; ``--dataset NYU`` evaluates the NYU Depth v2 test set with compute_errors_NYU;
+``--img_save`` writes the output depth, ground truth and input colour of every test image as JPEG under --result_dir,
+from the validation pass itself.  NYU and Make3D training and Make3D evaluation are not implemented.
 """
 import os
 import sys
@@ -24,14 +29,57 @@ from . import option
 from .AE_model_unet import AutoEncoder, AutoEncoder_2, AutoEncoder_DtoD
 from .optim import Adam
 from .synthetic import SyntheticLoader
-from .trainer import load_checkpoint, train_AE_DtoD, train_AE_RtoD, validate
+from .trainer import load_checkpoint, train_AE_DtoD, train_AE_RtoD, validate, validate_NYU
+
+TEST_MODES = ('DtoD_test', 'RtoD_test')
 
 
 def _make_optimizer(model, args):
     return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4)
 
 
+def _check_dataset(args):
+    """What the file pipeline can read, checked before anything touches the GPU."""
+    if args.synthetic:
+        return
+    if args.dataset == "Make3D":
+        raise RuntimeError("--dataset Make3D is not supported: the reference's Make3D loader resizes with cv2.INTER_AREA "
+                           "to 232x176, a size the U-Net cannot take (compute_errors_Make3D itself is available in "
+                           "gdn_amd.calculate_error)")
+    if args.dataset == "NYU" and args.mode not in TEST_MODES:
+        raise RuntimeError("--dataset NYU is implemented for evaluation only (--mode DtoD_test / RtoD_test); NYU training "
+                           "is out of scope")
+    if args.dataset not in ("KITTI", "NYU"):
+        raise RuntimeError("unknown --dataset %r (KITTI, NYU)" % (args.dataset,))
+
+
+class ImageSaver:
+    """--img_save (GDN_main.py:268-307): for every test image, in loader order, result_dir/output_depth/final_AE_depth_%05d.jpg,
+    ground_truth/final_AE_gt_%05d.jpg and input_rgb/final_AE_rgb_%05d.jpg, bytescaled on the GPU like scipy.misc.imsave
+    and written by PIL as JPEG with its default quality.  Called with each validation batch (no second forward pass)."""
+
+    FOLDERS = (("output_depth", "final_AE_depth_"), ("ground_truth", "final_AE_gt_"), ("input_rgb", "final_AE_rgb_"))
+
+    def __init__(self, result_dir):
+        self.dirs = [os.path.join(result_dir, f) for f, _ in self.FOLDERS]
+        for d in self.dirs:
+            os.makedirs(d, exist_ok=True)
+        self.k = 0
+
+    def __call__(self, depth, img, depth_np, out):
+        from PIL import Image
+        from . import ops
+        for t, d, (_, name) in zip((out, depth, img), self.dirs, self.FOLDERS):
+            u8 = ops.bytescale_u8(t.detach().float()).cpu().numpy()
+            for i in range(u8.shape[0]):
+                im = u8[i, :, :, 0] if u8.shape[3] == 1 else u8[i]
+                Image.fromarray(im).save(os.path.join(d, name + '%05d.jpg' % (self.k + i)))
+        self.k += out.shape[0]
+
+
 def run(args, train_loader=None, val_loader=None):
+    if train_loader is None:
+        _check_dataset(args)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num
@@ -50,12 +98,30 @@ def run(args, train_loader=None, val_loader=None):
     if train_loader is None:
         from .datasets import GpuAugmentLoader, SequenceFolder, SyntheticRawKitti
         steps = args.epoch_size or 100
-        if not args.synthetic and os.path.isdir(str(args.data)):
+        if not args.synthetic and os.path.isdir(str(args.data)) and args.mode in TEST_MODES and \
+                (args.dataset == "NYU" or args.real_test):
+            # evaluation only: the NYU test set (datasets_list.py:366-444) or the Eigen test split (:111-189); no train set
+            from .datasets import GpuCropLoader, NYUdataset, TestFolder
+            if args.dataset == "NYU":
+                val_loader = GpuCropLoader(NYUdataset(args.data, args, seed=args.seed, train=False, mode=args.mode),
+                                           args.batch_size, dev, H, W, workers=args.workers)
+            else:
+                val_loader = GpuAugmentLoader(TestFolder(args.data, args, seed=args.seed, train=False, mode=args.mode),
+                                              args.batch_size, dev, train=False, workers=args.workers)
+            train_loader = val_loader
+            if rank == 0:
+                print("=> test on %s: %d samples" % ("the NYU Depth v2 test set" if args.dataset == "NYU"
+                                                     else "the Eigen test split", len(val_loader.ds)))
+        elif not args.synthetic and os.path.isdir(str(args.data)):
             # the reference's file layout (datasets_list.py:61-76); decode on the host, augment on the GPU
             if args.dataset != "KITTI":
                 raise RuntimeError("only the KITTI pipeline (GDN_main.py:56-80) is implemented; NYU is out of scope")
             train_set = SequenceFolder(args.data, args, seed=args.seed, train=True, mode=args.mode)     # same file order on every rank
-            val_set = SequenceFolder(args.data, args, seed=args.seed, train=False, mode=args.mode)
+            if args.real_test:          # GDN_main.py:70-79: validate on the Eigen test split
+                from .datasets import TestFolder
+                val_set = TestFolder(args.data, args, seed=args.seed, train=False, mode=args.mode)
+            else:
+                val_set = SequenceFolder(args.data, args, seed=args.seed, train=False, mode=args.mode)
             # data parallelism: a common shuffle, rank r takes samples r, r + world, ... (each sample once per epoch);
             # --batch_size is per GPU, so the global batch is world * batch_size at the given learning rate
             train_loader = GpuAugmentLoader(train_set, args.batch_size, dev, train=True, seed=args.seed + rank,
@@ -114,7 +180,9 @@ def run(args, train_loader=None, val_loader=None):
         if os.path.exists(ckpt):
             load_checkpoint(model, ckpt)
         model.eval()
-        errors, min_errors, names = validate(args, val_loader, model, 0, logger, args.mode)
+        saver = ImageSaver(args.result_dir) if args.img_save and rank == 0 else None
+        evaluate = validate_NYU if args.dataset == "NYU" else validate
+        errors, min_errors, names = evaluate(args, val_loader, model, 0, logger, args.mode, on_batch=saver)
         if rank == 0:
             print("Results: " + ", ".join("%s %.4f" % (n, e) for n, e in zip(names, errors)))
         return errors

@@ -110,6 +110,12 @@ _SIGS = {
     "gdn_mse_grad": (c_int32, [_P, _P, _i64, _f, _P, _P, _i32, _P]),
     "gdn_depth_metrics_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "gdn_depth_metrics": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, _P, _P, _sz, _P]),
+    "gdn_depth_metrics_nyu_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "gdn_depth_metrics_nyu": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _P, _P, _sz, _P]),
+    "gdn_depth_metrics_make3d_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "gdn_depth_metrics_make3d": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _P, _P, _sz, _P]),
+    "gdn_crop_normalize": (c_int32, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
+    "gdn_bytescale_u8": (c_int32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
     "gdn_adam_step": (c_int32, [_P, _P, _P, _P, _i64, _f, _f, _f, _f, _f, _i32, _f, _P]),
     "gdn_adam_step_dev": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
@@ -121,7 +127,7 @@ _STATUS_FUNCS = {n for n, (r, _) in _SIGS.items() if r is c_int32} - {"gdn_versi
 EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --
 # a stale build would take the arguments apart differently.
-ABI_VERSION = 222
+ABI_VERSION = 223
 
 
 class _Lib:

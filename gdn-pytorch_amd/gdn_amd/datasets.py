@@ -7,6 +7,10 @@ depth, ``gt/*.png`` sparse depth, shuffled for training) but the per-sample tran
 Normalize -- runs in ONE HIP kernel per tensor on the whole batch (``gdn_kitti_augment``), bit-exact
 with the host pipeline: the host only decodes files to uint8 and draws five random numbers per sample,
 in the reference's call order.
+
+Evaluation (GDN_main.py:64-79, :128-130): ``TestFolder`` reads the Eigen test split (KITTI files already at the network's
+size: the validation transform of gdn_kitti_augment applies), ``NYUdataset(train=False)`` the NYU Depth v2 test set, whose
+CenterCrop + ArrayToTensor + Normalize runs batched in ``GpuCropLoader`` (gdn_crop_normalize).
 """
 import concurrent.futures as cf
 import pathlib
@@ -59,6 +63,81 @@ class SequenceFolder:
     def __getitem__(self, index):
         s = self.samples[index]
         return _decode(s["gt"]), _decode(s["rgb"]), _decode(s["gt_np"])
+
+    def __len__(self):
+        return len(self.samples)
+
+
+def _decode_or_raise(path):
+    try:
+        return _decode(path)
+    except Exception as e:        # missing, truncated or not an image
+        raise GdnError("cannot decode %s: %s" % (path, e)) from e
+
+
+class TestFolder:
+    """The Eigen test split (datasets_list.py:111-189): root/eigen_test_files_img.txt, _color_gt.txt and _gt.txt list the
+    colour frame, the dense depth and the sparse depth of each sample (first token of every line), in file order.  An
+    entry is taken as written if that path exists, else relative to root.  Samples are the raw decoded
+    (gt_color, rgb, gt) images.
+
+    Deliberate divergence: the reference substitutes the previous sample when a file fails to load (and loops forever if
+    the first one does); here a file that cannot be decoded raises GdnError naming it."""
+
+    LISTS = ("eigen_test_files_img.txt", "eigen_test_files_color_gt.txt", "eigen_test_files_gt.txt")
+
+    def __init__(self, root, args=None, seed=None, train=False, transform=None, target_transform=None, mode="DtoD"):
+        self.root = pathlib.Path(root)
+        self.train, self.mode, self.args = train, mode, args
+        self.crawl_folders()
+
+    def _entries(self, name):
+        with open(self.root / name) as f:
+            toks = [line.split()[0] for line in f if line.split()]
+        return [pathlib.Path(t) if pathlib.Path(t).exists() else self.root / t for t in toks]
+
+    def crawl_folders(self):
+        imgs, color_gt, gt = (self._entries(n) for n in self.LISTS)
+        if not (len(imgs) == len(color_gt) == len(gt)):
+            raise GdnError("Eigen test lists differ in length: %d img, %d color_gt, %d gt" % (len(imgs), len(color_gt),
+                                                                                               len(gt)))
+        self.samples = [{"gt": s, "rgb": i, "gt_color": c} for i, c, s in zip(imgs, color_gt, gt)]
+
+    def __getitem__(self, index):
+        s = self.samples[index]
+        return _decode_or_raise(s["gt_color"]), _decode_or_raise(s["rgb"]), _decode_or_raise(s["gt"])
+
+    def __len__(self):
+        return len(self.samples)
+
+
+class NYUdataset:
+    """NYU Depth v2 test set (datasets_list.py:366-444, train=False): root/test/test_depths/*.png (16-bit depth) paired
+    in sorted order with root/test/test_colors/*.png.  Samples are the raw decoded (gt, rgb, gt) -- the same depth array
+    twice, as the reference returns it; GpuCropLoader applies the validation transform.  The order is the sorted one
+    (the reference shuffles unless --img_test).  train=True raises: NYU training is not implemented."""
+
+    def __init__(self, root, args=None, seed=None, train=False, transform=None, transform_2=None, mode="DtoD"):
+        if train:
+            raise GdnError("NYUdataset(train=True): NYU training (random crop / rotate / imresize) is not implemented; "
+                           "only the test set can be read")
+        self.root = pathlib.Path(root)
+        self.train, self.mode, self.args = train, mode, args
+        self.depth_folder = self.root / "test" / "test_depths"
+        self.img_folder = self.root / "test" / "test_colors"
+        self.crawl_folders()
+
+    def crawl_folders(self):
+        gt = sorted(self.depth_folder.glob("*.png"))
+        rgbs = sorted(self.img_folder.glob("*.png"))
+        if len(gt) != len(rgbs):
+            raise GdnError("%s has %d png, %s has %d" % (self.depth_folder, len(gt), self.img_folder, len(rgbs)))
+        self.samples = [{"gt": g, "rgb": r} for g, r in zip(gt, rgbs)]
+
+    def __getitem__(self, index):
+        s = self.samples[index]
+        gt = _decode_or_raise(s["gt"])
+        return gt, _decode_or_raise(s["rgb"]), gt
 
     def __len__(self):
         return len(self.samples)
@@ -159,3 +238,28 @@ class GpuAugmentLoader:
                 self.last_params = host
                 params = torch.tensor(host, dtype=torch.int32).pin_memory().to(self.dev, non_blocking=True)
             yield tuple(ops.kitti_augment(self._to_device([s[j] for s in samples]), params, self.train) for j in range(3))
+
+
+class GpuCropLoader(GpuAugmentLoader):
+    """Batches of (gt, rgb, gt) as normalised NCHW float32 tensors on `device`, in dataset order, with the NYU validation
+    transform (CenterCrop to height x width at the centre of the colour image, ArrayToTensor, Normalize) executed by
+    gdn_crop_normalize.  A sample whose third image is its first (NYUdataset) shares one output tensor."""
+
+    def __init__(self, dataset, batch_size, device, height, width, workers=0):
+        super().__init__(dataset, batch_size, device, train=False, shuffle=False, workers=workers)
+        self.size = (int(height), int(width))
+
+    def __iter__(self):
+        H, W = self.size
+        order = self._epoch_order()
+        for b in range(len(self)):
+            samples = self._fetch(order[b * self.bs:(b + 1) * self.bs])
+            H0, W0 = samples[0][1].shape[:2]
+            for s in samples:
+                if any(x.shape[:2] != (H0, W0) for x in s):
+                    raise GdnError("all images of a batch must share one size, got %s" % ([x.shape for x in s],))
+            off = ops.center_crop_offsets(H0, W0, H, W)        # CenterCrop takes its window from the colour image
+            gt, rgb = (ops.crop_normalize(self._to_device([s[j] for s in samples]), H, W, off) for j in range(2))
+            third = gt if all(s[2] is s[0] for s in samples) else \
+                ops.crop_normalize(self._to_device([s[2] for s in samples]), H, W, off)
+            yield gt, rgb, third

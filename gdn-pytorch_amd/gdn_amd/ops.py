@@ -930,6 +930,57 @@ def depth_metrics(gt_sparse, gt, pred, crop=True):
     return err
 
 
+def depth_metrics_nyu(gt, pred, crop=True):
+    """compute_errors_NYU on [B,1,H,W] float32 device tensors -> device [8] batch means (no sync)."""
+    B, _, H, W = pred.shape
+    nb = int(lib.gdn_depth_metrics_nyu_workspace_bytes(B, H, W))
+    ws = workspace(nb, pred.device, "metrics")
+    err = torch.empty(8, dtype=torch.float32, device=pred.device)
+    lib.gdn_depth_metrics_nyu(_p(gt), _p(pred), B, H, W, 1 if crop else 0, _p(err), _p(ws), nb, stream())
+    return err
+
+
+def depth_metrics_make3d(gt_np, gt, pred):
+    """compute_errors_Make3D on [B,1,H,W] float32 device tensors -> device [4] batch means (no sync)."""
+    B, _, H, W = pred.shape
+    nb = int(lib.gdn_depth_metrics_make3d_workspace_bytes(B, H, W))
+    ws = workspace(nb, pred.device, "metrics")
+    err = torch.empty(4, dtype=torch.float32, device=pred.device)
+    lib.gdn_depth_metrics_make3d(_p(gt_np), _p(gt), _p(pred), B, H, W, _p(err), _p(ws), nb, stream())
+    return err
+
+
+def center_crop_offsets(in_h, in_w, out_h, out_w):
+    """CenterCrop.get_params (transform_list.py:260-261): Python's round, i.e. half to even."""
+    return int(round((in_h - out_h) / 2.)), int(round((in_w - out_w) / 2.))
+
+
+def crop_normalize(src, H, W, offsets=None):
+    """src [B,H0,W0,C] uint8/float32 as decoded, on the device -> [B,C,H,W] float32 (v/255 - 0.5)/0.5 of the window at
+    `offsets` (default: the centre crop).  Float sources are not bytescaled (the NYU validation transform has no imresize)."""
+    if not src.is_cuda or src.dtype not in (torch.uint8, torch.float32) or src.dim() != 4 or not src.is_contiguous():
+        raise GdnError("crop_normalize: src must be a dense [B,H,W,C] uint8/float32 tensor on the GPU")
+    B, H0, W0, C = src.shape
+    oy, ox = center_crop_offsets(H0, W0, H, W) if offsets is None else offsets
+    if not (0 <= oy and oy + H <= H0 and 0 <= ox and ox + W <= W0):
+        raise GdnError("crop_normalize: window %dx%d at (%d, %d) does not fit a %dx%d image" % (H, W, oy, ox, H0, W0))
+    dst = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+    lib.gdn_crop_normalize(_p(src), 1 if src.dtype == torch.float32 else 0, B, H0, W0, C, int(oy), int(ox), H, W,
+                           _p(dst), stream())
+    return dst
+
+
+def bytescale_u8(x):
+    """[B,C,H,W] float32 device tensor -> [B,H,W,C] uint8 as scipy.misc.imsave bytescales an image (per image, fp64)."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        raise GdnError("bytescale_u8: x must be a [B,C,H,W] float32 tensor on the GPU")
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    dst = torch.empty((B, H, W, C), dtype=torch.uint8, device=x.device)
+    lib.gdn_bytescale_u8(_p(x), B, C, H, W, _p(dst), stream())
+    return dst
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     lib.gdn_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, int(step),
                       float(grad_scale), stream())

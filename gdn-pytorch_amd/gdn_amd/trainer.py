@@ -18,7 +18,8 @@ import torch
 from . import distributed as D
 from . import tracing
 from . import utils as U
-from .calculate_error import ERROR_NAMES, compute_errors_device
+from .calculate_error import (ERROR_NAMES, ERROR_NAMES_MAKE3D, ERROR_NAMES_NYU, compute_errors_device,
+                              compute_errors_Make3D_device, compute_errors_NYU_device)
 
 
 def _is_main():
@@ -220,10 +221,10 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     return loss, output_loss, latent
 
 
-def validate(args, val_loader, model, epoch, logger, mode='DtoD'):
-    """Forward (no_grad) + compute_errors per batch; returns (mean errors, mean of the
-    abs_diff-sorted errors, names) like trainer.py:17-87.  Metrics stay on the device;
-    one D2H copy at the end."""
+def _evaluate(val_loader, model, mode, metric, names, on_batch=None):
+    """Forward (no_grad) + `metric(depth_np, depth, out)` per batch; returns (mean errors, mean of the abs_diff-sorted
+    errors, names) like trainer.py:17-87.  Metrics stay on the device; one D2H copy at the end.  on_batch(depth, img,
+    depth_np, out) sees every batch in loader order (--img_save writes its images from there)."""
     dev = _device_of(model)
     per_batch = []
     for depth, img, depth_np in val_loader:
@@ -231,10 +232,29 @@ def validate(args, val_loader, model, epoch, logger, mode='DtoD'):
         x = img if mode in ('RtoD', 'RtoD_test', 'RtoD_single') else depth
         with torch.no_grad():
             out = model(x, istrain=False)
-        per_batch.append(compute_errors_device(depth_np, depth, out, crop=True))
+        per_batch.append(metric(depth_np, depth, out))
+        if on_batch is not None:
+            on_batch(depth, img, depth_np, out)
     if not per_batch:
-        return [float('nan')] * 8, [float('nan')] * 8, ERROR_NAMES
+        return [float('nan')] * len(names), [float('nan')] * len(names), names
     allv = torch.stack(per_batch).cpu()
     avg = allv.mean(0).tolist()
     order = torch.argsort(allv[:, 0])
-    return avg, allv[order].mean(0).tolist(), ERROR_NAMES
+    return avg, allv[order].mean(0).tolist(), names
+
+
+def validate(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None):
+    """KITTI: compute_errors (Godard crop) per batch, trainer.py:17-87."""
+    return _evaluate(val_loader, model, mode, lambda s, g, o: compute_errors_device(s, g, o, crop=True), ERROR_NAMES,
+                     on_batch)
+
+
+def validate_NYU(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None):
+    """NYU Depth v2: compute_errors_NYU (crop on) per batch, trainer.py:200-270."""
+    return _evaluate(val_loader, model, mode, lambda s, g, o: compute_errors_NYU_device(g, o, crop=True), ERROR_NAMES_NYU,
+                     on_batch)
+
+
+def validate_Make3D(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None):
+    """Make3D: compute_errors_Make3D per batch, trainer.py:272-327."""
+    return _evaluate(val_loader, model, mode, compute_errors_Make3D_device, ERROR_NAMES_MAKE3D, on_batch)

@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 const char* gdn_strerror(int status);
@@ -514,6 +514,52 @@ size_t gdn_depth_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int gdn_depth_metrics(const float* gt_sparse, const float* gt, const float* pred,
                       int32_t B, int32_t H, int32_t W, int32_t crop,
                       float* errors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * NYU Depth v2 depth metrics, calculate_error.py:105-150 (compute_errors_NYU):
+ * per image min-max -> x10, valid = (gt < 10) & (gt > 0), with crop the rows AND
+ * columns [int(0.0359477 n), int(0.96405229 n)), median scaling (lower median),
+ * clamp to [1e-3, 10], 8 reductions in fp64.  gt/pred are [B,1,H,W];
+ * errors[8] = batch means of [abs_diff, abs_rel, log10, a1, a2, a3, rmse, rmse_log],
+ * device memory.  An image with no valid pixel gives NaN (the reference raises:
+ * torch.median of an empty tensor).
+ * ---------------------------------------------------------------------- */
+size_t gdn_depth_metrics_nyu_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int gdn_depth_metrics_nyu(const float* gt, const float* pred, int32_t B, int32_t H, int32_t W, int32_t crop,
+                          float* errors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Make3D depth metrics, calculate_error.py:152-182 (compute_errors_Make3D):
+ * gt_np, gt and pred min-max normalised per image; valid = normalised gt_np and
+ * gt > 1e-2 and their x80 values < 80; gt and pred x80 clamped to [1e-2, 80]
+ * BEFORE the median scaling (none after).  gt_np/gt/pred are [B,1,H,W];
+ * errors[4] = batch means of [abs_diff, abs_rel, ave_log10, rmse].  No valid
+ * pixel: NaN, as above.
+ * ---------------------------------------------------------------------- */
+size_t gdn_depth_metrics_make3d_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int gdn_depth_metrics_make3d(const float* gt_np, const float* gt, const float* pred, int32_t B, int32_t H, int32_t W,
+                             float* errors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * NYU validation transform (GDN_main.py:41-47: CenterCrop, ArrayToTensor,
+ * Normalize) for a batch, bit-exact with torch's fp32 arithmetic.
+ *   src  [B][H0][W0][C] as decoded: uint8, or float32 when src_is_f32 (NOT
+ *        bytescaled: this transform has no imresize); 1 <= C <= 3
+ *   the window (off_y, off_x, H, W) must lie inside H0 x W0; CenterCrop's offsets
+ *   are round((H0-H)/2), round((W0-W)/2) with Python's round-half-even (the
+ *   caller computes them, transform_list.py:260-261)
+ *   dst  [B][C][H][W] float32 = (v/255 - 0.5)/0.5
+ * ---------------------------------------------------------------------- */
+int gdn_crop_normalize(const void* src, int32_t src_is_f32, int32_t B, int32_t H0, int32_t W0, int32_t C,
+                       int32_t off_y, int32_t off_x, int32_t H, int32_t W, float* dst, void* stream);
+
+/* ------------------------------------------------------------------------
+ * --img_save's image conversion (GDN_main.py:285-307: scipy.misc.imsave ->
+ * toimage -> bytescale): src [B][C][H][W] float32 -> dst [B][H][W][C] uint8,
+ * per image over all channels jointly, in fp64: cscale = max - min (1 when 0),
+ * u8 = trunc(clip((x - min) * (255 / cscale), 0, 255) + 0.5).
+ * ---------------------------------------------------------------------- */
+int gdn_bytescale_u8(const float* src, int32_t B, int32_t C, int32_t H, int32_t W, uint8_t* dst, void* stream);
 
 /* ------------------------------------------------------------------------
  * KITTI training-time augmentation on the device.  Replaces the host pipeline
