@@ -39,17 +39,6 @@ static_assert(FFT_BINS_OF(32) % 8 == 0 && FFT_BINS_OF(16) % 8 == 0 && FFT_BINS_O
 // not fold it back into multiplies.
 #define GDN_KEEP(v) asm volatile("" : "+v"(v))
 
-// Round-6 A/B switches (tools/ab_variant.sh ... -DGDN_x=n; measured in profiles/r06_fft_ab.txt):
-#ifndef GDN_ICOLS_ORDER
-#define GDN_ICOLS_ORDER 1    // ifft_cols grid: 0: blockIdx.x = tile group, y = kx;  1: blockIdx.x = kx (fastest), y = tile group
-#endif
-#ifndef GDN_FFT_DGRAD_PATCH
-#define GDN_FFT_DGRAD_PATCH 1  // data gradient's inverse: 1 = single-pass inverse into a patch buffer + gather (overlap-add), 0 = ifft_cols + two
-#endif                         //                           ordered ifft_rows_overlap launches through the intermediate S (rounds 1-5)
-#ifndef GDN_ROWS_REMAP
-#define GDN_ROWS_REMAP 2     // ifft_rows_overlap: 0 = 4 tiles x 64-channel chunk, 1 = (256 / C) tiles x all channels, 2 = 1 only for C = 256
-#endif
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned uint2_t __attribute__((ext_vector_type(2)));
 
@@ -448,19 +437,15 @@ __global__ __launch_bounds__(256, 4) void cgemm_bins_kernel(const float* __restr
 }
 
 // icols: thread = (tile, kx, channel n): inverse FFT32 along ky, rows u < nrows kept.
-// grid: x = tile group, y = kx; block = (256 / C) WHOLE tiles x all C channels (C = 64 << cq_shift <= 256): a block's loads are one
+// grid: x = kx, y = tile group; block = (256 / C) WHOLE tiles x all C channels (C = 64 << cq_shift <= 256): a block's loads are one
 // contiguous 2 KB run per ky and its stores C x 8 B runs (round 6; before: 4 tiles x one 64-channel chunk, i.e. 512-byte pieces
 // of 1-2 KB rows on the 128- / 256-channel layers -- PMC profiles/r06_fft_pmc.json: 1.8 TB/s, 70 % of the wave time waiting)
-#ifndef GDN_ICOLS40_WAVES
-#define GDN_ICOLS40_WAVES 2
-#endif
-
 template <int NP>
-__global__ __launch_bounds__(256, NP == 40 ? GDN_ICOLS40_WAVES : 1) void ifft_cols_kernel(const float2* __restrict__ Yf, float2* __restrict__ S, int C, int M, int nrows,
+__global__ __launch_bounds__(256, NP == 40 ? 2 : 1) void ifft_cols_kernel(const float2* __restrict__ Yf, float2* __restrict__ S, int C, int M, int nrows,
                                                         int cq_shift) {
     constexpr int NK = FFT_NK_OF(NP);
     const int csh = 6 + cq_shift;                                   // log2(C)
-    const int bx = GDN_ICOLS_ORDER ? blockIdx.y : blockIdx.x, kx = GDN_ICOLS_ORDER ? blockIdx.x : blockIdx.y;
+    const int bx = blockIdx.y, kx = blockIdx.x;
     const int t = bx * (256 >> csh) + (threadIdx.x >> csh);
     if (t >= M) return;
     const int c = threadIdx.x & (C - 1);
@@ -683,12 +668,13 @@ __global__ __launch_bounds__(256) void ifft_rows_overlap_kernel(const float2* __
                                                                 int parity, int Ho, int Wo, int off, int cq_shift) {
     // output image Ho x Wo; patch row j of tile row ty lands on output row ty*T - off + j  (off = pad for a zero-padded
     // layer: dx itself; off = 0 for a reflection-padded one: the padded-domain gradient, folded afterwards)
-    // grid: x = group of tiles of this parity, y = output row, z = image; block = (256 / C) tiles x all C channels (whole 8 x C
-    // byte rows of S in, whole 4 x C byte pixels of dx out: round 6, see ifft_cols_kernel)
+    // grid: x = group of tiles of this parity (x its 64-channel chunk unless C = 256), y = output row, z = image; block = 4 tiles
+    // x one 64-channel chunk, or for C = 256 (remap) one tile x all 256 channels (whole 8 x C byte rows of S in, whole 4 x C
+    // byte pixels of dx out: round 6, see ifft_cols_kernel)
     constexpr int NK = FFT_NK_OF(NP);
     const int C = g.C, T = g.T;
     const int ntx = (g.tiles_x + 1 - parity) / 2;         // tiles of this parity per row
-    const bool remap = GDN_ROWS_REMAP == 1 || (GDN_ROWS_REMAP == 2 && cq_shift == 2);
+    const bool remap = cq_shift == 2;
     const int csh = remap ? 6 + cq_shift : 6;             // log2(channels per workgroup)
     const int txl = (remap ? blockIdx.x : (blockIdx.x >> cq_shift)) * (256 >> csh) + (threadIdx.x >> csh);
     if (txl >= ntx) return;
@@ -1237,7 +1223,7 @@ bool fft_geom(const gdn_conv_geom* g, FftGeom& f) {
 inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 inline dim3 icols_grid(const FftGeom& f, int cq_shift) {
     const int groups = cdiv(f.M, 4 >> cq_shift), nk = f.np / 2 + 1;
-    return GDN_ICOLS_ORDER ? dim3(nk, groups) : dim3(groups, nk);
+    return dim3(nk, groups);
 }
 // persistent grid of cgemm_bins_kernel: four workgroups per CU, ROUNDED DOWN to a multiple of 8 (at least 8) -- the kernel's
 // mixed-radix walk takes its stride digits from gridDim.x >> 3 (a workgroup stays on one XCD's bins), so a grid that is not a
@@ -1380,7 +1366,7 @@ extern "C" size_t gdn_fftconv_bwd_workspace_bytes(const gdn_conv_geom* g) {
 // workgroups of the data gradient's gather pass = slots of the BatchNorm-backward partial sums it can emit (0: not available:
 // reflection-padded layers finish their gradient in the fold pass, and rows wider than the gather's x table take the old inverse)
 static int fft_gather_blocks(const FftGeom& f) {
-    if (!GDN_FFT_DGRAD_PATCH || f.reflect || f.W > FFT_GATHER_MAX_W) return 0;
+    if (f.reflect || f.W > FFT_GATHER_MAX_W) return 0;
     const int64_t rows = (int64_t)f.B * f.H;
     return (int)(rows < FFT_GATHER_MAX_BLOCKS ? rows : FFT_GATHER_MAX_BLOCKS);
 }
@@ -1461,7 +1447,7 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
         float* o = f.reflect ? dxp : dx;
         const int ldo = f.reflect ? f.C : ldx, off = f.reflect ? 0 : f.pad;
         const float* ad = f.reflect ? (const float*)nullptr : addsrc;
-        if (GDN_FFT_DGRAD_PATCH && (ldo % 4) == 0 && (!ad || (ld_add % 4) == 0) && Wo <= FFT_GATHER_MAX_W) {
+        if ((ldo % 4) == 0 && (!ad || (ld_add % 4) == 0) && Wo <= FFT_GATHER_MAX_W) {
             // single-pass inverse of every tile into its own patch (the region S used to occupy), then the gather
             float* patch = (float*)R;
             const dim3 gp(f.C / FFT_CG_OF(f.np) * 8 * cdiv(f.M, 8)), bp(f.np * FFT_CG_OF(f.np));
@@ -1490,7 +1476,7 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
         for (int parity = 0; parity < 2; ++parity) {
             const int ntx = (f.tiles_x + 1 - parity) / 2;
             if (ntx == 0) continue;
-            const bool remap = GDN_ROWS_REMAP == 1 || (GDN_ROWS_REMAP == 2 && cq_shift == 2);
+            const bool remap = cq_shift == 2;
             const dim3 gr(remap ? cdiv(ntx, 4 >> cq_shift) : cdiv(ntx, 4) << cq_shift, Ho, f.B);
             if (f.np == 16)
                 hipLaunchKernelGGL(ifft_rows_overlap_kernel<16>, gr, dim3(256), 0, st, (const float2*)R, o, ldo, ad, ld_add, f, parity, Ho,

@@ -6,7 +6,8 @@ needed, pushes one closure on a tape; ``backward`` replays the tape in reverse.
 Parameters keep the reference's names/shapes but live, tap-major, in one flat
 arena per model (so Adam and the RCCL all-reduce see a single buffer).
 """
-import os
+import collections
+import functools
 
 import torch
 
@@ -14,31 +15,25 @@ from . import ops
 from ._lib import GdnError
 
 _ALIGN = 64  # floats
-_FUSE_EVAL_BN = os.environ.get("GDN_FUSE_EVAL_BN", "1") != "0"     # A/B switch for measurements
-# fp32 stride-1 zero-padded layers with a window of at least this size run in the frequency domain
-# (csrc/conv_fft.hip); 0 disables.  5x5 on 256 channels is the break-even neighbourhood.
-_FFT_MIN_K = int(os.environ.get("GDN_FFT_MIN_K", "5"))
-# fp32 3x3 stride-1 zero-padded layers on 64..512 channels run as Winograd F(2x2,3x3) (csrc/conv_wino.hip)
-_WINOGRAD = os.environ.get("GDN_WINOGRAD", "1") != "0"
-# train-mode BatchNorm fusion (A/B switch): scale/shift/ReLU of a ResidualBlock's first half applied in the consumer's
-# loader, BatchNorm-backward reductions emitted by the data-gradient epilogues
-_FUSE_TRAIN_BN = os.environ.get("GDN_FUSE_TRAIN_BN", "1") != "0"
-# per-site A/B switches of that fusion (measurement; all on by default unless a site measured slower)
-_FUSE = {k: os.environ.get("GDN_FUSE_" + k.upper(), d) != "0" for k, d in
-         (("fft_in", "1"), ("fft_dyb", "1"), ("fft_bnb", "1"), ("wino_in", "1"), ("wino_bnb", "1"), ("ring_bnb", "1"))}
+# fp32 stride-1 zero-padded layers with a window of at least this size run in the frequency domain (csrc/conv_fft.hip):
+# 5x5 on 256 channels is the break-even neighbourhood
+_FFT_MIN_K = 5
 # fp32 4x4 stride-2 pad-1 Conv2d / ConvTranspose2d layers run as Winograd F(3x3,2x2) over the polyphase images
-# (csrc/conv_wino2.hip) when both channel counts reach this value (0 disables): the transforms move ~1.8x the
-# layer's activations (measured: a gain on every such layer of G, the smallest at 64 channels, tests/diag/wino2_time.py)
-_WINO2_MIN_C = int(os.environ.get("GDN_WINO2_MIN_C", "64"))
-# fp32 1 <-> 64 channel 9x9 layers (G's first convolution, the heads' backward) on csrc/conv_c1.hip (A/B switch)
-_C1 = os.environ.get("GDN_C1", "1") != "0"
+# (csrc/conv_wino2.hip) when both channel counts reach this value: the transforms move ~1.8x the layer's
+# activations (measured: a gain on every such layer of G, the smallest at 64 channels, tests/diag/wino2_time.py)
+_WINO2_MIN_C = 64
+# The three fusions below are on; the tests switch them off to compare against the unfused form, which is also what a
+# layer that cannot fuse runs.
+# train-mode BatchNorm: scale/shift/ReLU of a ResidualBlock's first half applied in the consumer's loader, BatchNorm-backward
+# reductions emitted by the data-gradient epilogues
+_FUSE_TRAIN_BN = True
 # x2 bilinear upsampling folded into the consumer convolution's loader and its backward's fold pass (north_star "bilinear-interp
-# ... fused"; csrc/up2x.h): A/B switch
-_FUSE_UP2X = os.environ.get("GDN_FUSE_UP2X", "1") != "0"
+# ... fused"; csrc/up2x.h)
+_FUSE_UP2X = True
 # bf16 form of the same fusion (round 5, row N1): LDS-DMA operands cannot be interpolated on load, so the PRODUCER writes the
 # upsampled tensor -- BatchNorm-apply (+ residual) and the interpolation are one pass (gdn_bn_apply_up2x) -- and the consumer's
 # reflection fold applies the adjoint (gdn_conv_dgrad dx_up2x): no stand-alone upsample2x kernel in either direction
-_FUSE_UP2X_BF16 = os.environ.get("GDN_FUSE_UP2X_BF16", "1") != "0"
+_FUSE_UP2X_BF16 = True
 _GRAPH_EPOCH = 0
 
 
@@ -426,13 +421,17 @@ def _layer_dtype(ctx, conv):
     return torch.float32
 
 
+def _grad_tap(mod):
+    gv = tap_view(mod.weight.grad, isinstance(mod, torch.nn.ConvTranspose2d))
+    if gv is None:
+        raise GdnError("weight.grad is not tap-major")
+    return gv
+
+
 def _wgrad_into(ctx, mod, x, dy, x2=None):
     """Weight gradient of a conv module straight into its arena slice."""
     op = mod._gdn_op
-    tr = isinstance(mod, torch.nn.ConvTranspose2d)
-    gv = tap_view(mod.weight.grad, tr)
-    if gv is None:
-        raise GdnError("weight.grad is not tap-major")
+    gv = _grad_tap(mod)
     op.wgrad(x, dy, gv, 0)
     if x2 is not None:
         op.wgrad(x2, dy, gv, x.shape[3])
@@ -508,6 +507,56 @@ def _conv_instnorm_train(ctx, x, conv, inorm, relu, op, w, reflect, need_dx):
     return a
 
 
+# The kernels one conv_bn_act call runs (_conv_path).  fused_in: the loader applies a deferred train-mode BatchNorm
+# (in_affine / in_relu) or x2 upsampling (up2x); dyb: the backward applies this layer's BatchNorm backward while it transforms
+# dy; bnb_slots(): slots of the BatchNorm-backward partials of x's producer that the data gradient can emit; fwd(x, w, stats=,
+# [loader / epilogue keywords]) -> y or (y, stats[, saved state]); bwd(dy, w, in_hw, saved state, ...) -> dx (transform paths
+# only); c1_wgrad: the weight gradient runs on conv_c1_wgrad; up_fold: the direct data gradient may fold the producer's x2
+# upsampling (gdn_conv_dgrad dx_up2x); epilogue: the forward takes an eval-mode BatchNorm epilogue.
+ConvPath = collections.namedtuple("ConvPath", "name fused_in dyb bnb_slots fwd bwd c1_wgrad up_fold epilogue")
+
+
+def _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect):
+    """Which kernels run layer `conv` on input x (a tensor, a BnOut or an Up2x), first match wins:
+      fft     frequency domain (csrc/conv_fft.hip): fp32, window >= _FFT_MIN_K, stride 1
+      wino    Winograd F(4x4 / 2x2, 3x3) (csrc/conv_wino.hip): fp32, 3x3, stride 1 (64..512 channels)
+      wino2   Winograd F(3x3,2x2) (csrc/conv_wino2.hip): fp32, 4x4, stride 2, both channel counts >= _WINO2_MIN_C
+      c1      1 <-> 64 channel 9x9 kernels (csrc/conv_c1.hip): fp32 1- or 3-channel image into a Conv2d
+      direct  op.fwd / op.dgrad (the C library picks igemm / ring / ring2)
+    the transform paths and c1 only where the C library supports the geometry, never with a concatenated x2."""
+    k, s = conv.kernel_size[0], conv.stride[0]
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    lazy = isinstance(x, BnOut)
+    fp32 = ldt == torch.float32 and x2 is None
+    # GDN_HINT_TRAIN: a trained layer in train mode (forward + backward + weight gradient) -- the frequency-domain path then
+    # tiles for the sum of both passes (40-point tiles on the 9x9 layers); frozen / eval-mode layers keep the forward-optimal
+    # plan.  Only such a layer keeps the transform-domain state of its forward (an eval-mode backward is for frozen layers).
+    train = bool(ctx.record and bn.training and conv.weight.requires_grad)
+    path = functools.partial(ConvPath, c1_wgrad=False, up_fold=False, epilogue=conv.out_channels > 1)
+    if fp32 and k >= _FFT_MIN_K and s == 1 and op.fft_ok(B, H, W, backward=ctx.record, train=train):
+        if ctx.dtype == torch.bfloat16:
+            # A model that computes in bf16 runs barrier-paced 16-bit matrix kernels (conv_*_bf16) and must never have a
+            # frequency-domain kernel in flight beside them (DESIGN.md 2.10: measured interference on this hardware; the
+            # frequency-domain backward uses a second stream).  No layer of a bf16 model qualifies today (ldt is fp32 only for
+            # the 3-channel input conv); this keeps it that way by construction (tools/check_no_mfma16_beside_fft.py checks traces).
+            raise GdnError("internal: a bf16 model selected a frequency-domain layer")
+        return path("fft", True, True, functools.partial(op.fft_bnb_slots, B, H, W, train=train),
+                    functools.partial(op.fft_fwd, spectrum=train, train=train), functools.partial(op.fft_bwd, train=train))
+    if fp32 and k == 3 and s == 1 and op.wino_ok(B, H, W):
+        return path("wino", True, False, functools.partial(op.wino_bnb_slots, B, H, W),
+                    functools.partial(op.wino_fwd, state=train), op.wino_bwd)
+    if (fp32 and k == 4 and s == 2 and not lazy and min(conv.in_channels, conv.out_channels) >= _WINO2_MIN_C
+            and op.wino2_ok(B, H, W)):
+        return path("wino2", False, False, lambda: 0, functools.partial(op.wino2_fwd, state=train), op.wino2_bwd)
+    # (an Up2x input reaches c1 materialised: c1_ok reads dtype, channels and layout, which its source shares)
+    if (fp32 and not lazy and conv.in_channels in (1, 3) and not isinstance(conv, torch.nn.ConvTranspose2d)
+            and ops.c1_ok(x.src if isinstance(x, Up2x) else x, conv.out_channels, k, s, reflect or conv.padding[0], rgb=True)):
+        return path("c1", False, False, None, functools.partial(ops.conv_c1_fwd, reflect=bool(reflect)), None,
+                    c1_wgrad=conv.in_channels == 1)
+    return path("direct", False, False, None, functools.partial(op.fwd, x2=x2), None,
+                up_fold=bool(reflect and not lazy and x2 is None and conv.in_channels % 4 == 0 and H % 2 == 0 and W % 2 == 0))
+
+
 def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_dx=True, defer=False, up_out=None):
     """[relu](BN(conv(cat(x, x2)))) (+ residual): ConvBlock / ResidualBlock halves / ConvTBlock.
 
@@ -515,22 +564,19 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
     gets (output, upsampled) back -- on the bf16 path the BatchNorm-apply pass writes both (one kernel), on the fp32 path the
     upsampled one is the deferred Up2x of upsample().
 
-    x may be a BnOut (the deferred activation of the previous layer): the transform-domain paths apply its scale / shift /
-    ReLU while loading; any other path materialises it first.  defer=True (the caller guarantees a single consumer)
-    returns this layer's output as a BnOut instead of running the BatchNorm-apply pass, when the layer is a train-mode
-    fp32 one without a residual."""
+    x may be a BnOut (the deferred activation of the previous layer) or an Up2x (a deferred upsampling): the fft / wino loaders
+    apply its scale / shift / ReLU or interpolate while loading; any other path materialises it first.  defer=True (the
+    caller guarantees a single consumer) returns this layer's output as a BnOut instead of running the BatchNorm-apply pass,
+    when the layer is a train-mode fp32 one without a residual."""
     op = _conv_op(conv, reflect)
     ldt = _layer_dtype(ctx, conv)
+    if x.dtype != ldt:
+        raise GdnError("layer %d->%d computes in %s but its input is %s" % (conv.in_channels, conv.out_channels, ldt, x.dtype))
+    path = _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect)
     up = None
     if isinstance(x, Up2x):
-        # deferred x2 upsampling: the frequency-domain / Winograd F(2x2,3x3) loaders interpolate on the fly; training needs
-        # the fold pass of a reflection-padded layer for the adjoint.  Everything else gets the materialised tensor.
-        k, s_ = conv.kernel_size[0], conv.stride[0]
-        B_, H_, W_ = x.shape[0], x.shape[1], x.shape[2]
-        fusable = (ldt == torch.float32 and x2 is None and s_ == 1 and (not ctx.record or reflect)
-                   and ((_FFT_MIN_K > 0 and k >= _FFT_MIN_K and op.fft_ok(B_, H_, W_, backward=ctx.record))
-                        or (_WINOGRAD and k == 3 and op.wino_ok(B_, H_, W_))))
-        if fusable:
+        # training needs the fold pass of a reflection-padded layer for the adjoint of the interpolation
+        if path.fused_in and (not ctx.record or reflect):
             up = x
         else:
             x = x.dense(ctx)
@@ -538,115 +584,53 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
     lazy = isinstance(x, BnOut)
     if x2 is not None:
         ctx.claim(x2)
-    if x.dtype != ldt:
-        raise GdnError("layer %d->%d computes in %s but its input is %s" % (conv.in_channels, conv.out_channels, ldt, x.dtype))
-    w, tr = _w_for(ctx, conv, ldt)
+    w, _ = _w_for(ctx, conv, ldt)
     if bn.training and isinstance(bn, torch.nn.InstanceNorm2d):
         if lazy or up is not None or x2 is not None or residual is not None or ldt != torch.float32:
             raise GdnError("train-mode InstanceNorm is implemented for the standalone fp32 ConvBlock / ConvTBlock only")
         a = _conv_instnorm_train(ctx, x, conv, bn, relu, op, w, reflect, need_dx)
         return a if up_out is None else (a, upsample(ctx, a, bool(up_out)))
-    # GDN_HINT_TRAIN: a trained layer in train mode (forward + backward + weight gradient) -- the frequency-domain path then
-    # tiles for the sum of both passes (40-point tiles on the 9x9 layers); frozen / eval-mode layers keep the forward-optimal plan
-    fft_train = bool(ctx.record and bn.training and conv.weight.requires_grad)
-    use_fft = (_FFT_MIN_K > 0 and ldt == torch.float32 and x2 is None and conv.kernel_size[0] >= _FFT_MIN_K
-               and conv.stride[0] == 1
-               and op.fft_ok(x.shape[0], x.shape[1], x.shape[2], backward=ctx.record, train=fft_train))
-    if use_fft and ctx.dtype == torch.bfloat16:
-        # A model that computes in bf16 runs barrier-paced 16-bit matrix kernels (conv_*_bf16) and must never have a
-        # frequency-domain kernel in flight beside them (measured interference on this hardware; the
-        # frequency-domain backward uses a second stream).  No layer of a bf16 model qualifies today (ldt is fp32 only for the
-        # 3-channel input conv); this keeps it that way by construction (tools/check_no_mfma16_beside_fft.py checks traces).
-        raise GdnError("internal: a bf16 model selected a frequency-domain layer")
-    use_wino = (not use_fft and _WINOGRAD and ldt == torch.float32 and x2 is None
-                and conv.kernel_size[0] == 3 and conv.stride[0] == 1 and op.wino_ok(x.shape[0], x.shape[1], x.shape[2]))
-    use_wino2 = (not use_fft and not use_wino and _WINO2_MIN_C > 0 and ldt == torch.float32 and x2 is None
-                 and conv.kernel_size[0] == 4 and conv.stride[0] == 2 and not isinstance(x, BnOut)
-                 and min(conv.in_channels, conv.out_channels) >= _WINO2_MIN_C and op.wino2_ok(x.shape[0], x.shape[1], x.shape[2]))
-    # the transform-domain paths share one call shape: forward (+ saved state), backward from that state
-    alt_fwd = op.fft_fwd if use_fft else op.wino_fwd if use_wino else op.wino2_fwd if use_wino2 else None
-    alt_bwd = op.fft_bwd if use_fft else op.wino_bwd if use_wino else op.wino2_bwd if use_wino2 else None
-    # slots of the producer BatchNorm's backward partials the data-gradient pass can emit (wino2 epilogues do not emit them)
-    bnb_slots = (op.wino_bnb_slots if use_wino
-                 else (lambda B_, H_, W_: op.fft_bnb_slots(B_, H_, W_, train=fft_train)) if (use_fft and not use_wino2 and _FUSE["fft_bnb"])
-                 else (lambda *a: 0))
-    state_kw = "spectrum" if use_fft else "state"
-    bstate_kw = "xf" if use_fft else "state"
-    use_fft_only = use_fft
-    use_fft = use_fft or use_wino or use_wino2
-    in_kw = {}
-    xt = x                               # the tensor the conv kernels read
-    hint_kw = {"train": fft_train} if use_fft_only else {}
+    xt, kw = x, {}                       # the tensor the conv kernels read, and the forward's loader / epilogue arguments
     if up is not None:
-        if not (use_fft and not use_wino2):
-            raise GdnError("internal: deferred upsampling reached a layer without a fused loader")
-        in_kw = dict(up2x=up.mode)
-        xt = up.src
-    if lazy:
-        if use_fft and not use_wino2 and _FUSE_TRAIN_BN and _FUSE["fft_in" if use_fft_only else "wino_in"]:
-            in_kw = dict(in_affine=(x.co[0], x.co[1]), in_relu=x.relu)
-            xt = x.y
-        else:
-            xt = x.dense(ctx.dtype)      # (the direct kernels' loaders go straight to LDS: materialise)
-    xf = None
-    keep_xf = use_fft and ctx.record and conv.weight.requires_grad
-    use_c1 = (_C1 and not use_fft and ldt == torch.float32 and x2 is None and not lazy and conv.in_channels in (1, 3)
-              and not isinstance(conv, torch.nn.ConvTranspose2d)
-              and ops.c1_ok(x, conv.out_channels, conv.kernel_size[0], conv.stride[0], reflect or conv.padding[0], rgb=True))
+        xt, kw = up.src, dict(up2x=up.mode)
+    elif lazy and path.fused_in and _FUSE_TRAIN_BN:
+        xt, kw = x.y, dict(in_affine=(x.co[0], x.co[1]), in_relu=x.relu)
+    elif lazy:
+        xt = x.dense(ctx.dtype)          # (the other loaders go straight to LDS: materialise)
+    co = None if bn.training else _eval_coeffs(bn)
+    # eval-mode BN folded into the conv epilogue: conv + scale/shift + ReLU (+ residual) in one pass
+    fused = (not bn.training and path.epilogue and ldt == ctx.dtype and not (relu and residual is not None)
+             and (residual is None or residual.dtype == ldt))
+    if fused:
+        kw.update(affine=(co[0], co[1]), act=ops.ACT_RELU if relu else ops.ACT_NONE, addsrc=residual)
+    r = path.fwd(xt, w, stats=bn.training, **kw)
+    y, state, out_info = r, None, None   # state: what a trained transform-domain layer's forward keeps for its backward
     if bn.training:
-        if use_fft:
-            r = alt_fwd(xt, w, stats=True, **{state_kw: keep_xf}, **in_kw, **hint_kw)
-            y, st = r[0], r[1]
-            xf = r[2] if keep_xf else None
-        elif use_c1:
-            y, st = ops.conv_c1_fwd(xt, w, reflect=bool(reflect), stats=True)
-        else:
-            y, st = op.fwd(xt, w, x2=x2, stats=True)
+        y, st, state = r[0], r[1], (r[2] if len(r) > 2 else None)
         count = y.shape[0] * y.shape[1] * y.shape[2]
         mom = 0.1 if bn.momentum is None else bn.momentum
         co = ops.bn_finalize_train(st, count, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, mom, bn.eps,
                                    num_batches_tracked=bn.num_batches_tracked)
         bn._gdn_stats_ver = getattr(bn, "_gdn_stats_ver", 0) + 1
-    else:
-        co = _eval_coeffs(bn)
+        out_info = BnOut(y, co, relu)
     a_up = None
-    fused = (_FUSE_EVAL_BN and not bn.training and ldt == ctx.dtype and not (relu and residual is not None)
-             and (residual is None or residual.dtype == ldt) and conv.out_channels > 1)
-    out_info = None
     if fused:
-        # eval-mode BN folded into the conv epilogue: conv + scale/shift + ReLU (+ residual) in one pass
-        if use_fft:
-            y = a = alt_fwd(xt, w, affine=(co[0], co[1]), act=ops.ACT_RELU if relu else ops.ACT_NONE, addsrc=residual, **in_kw,
-                            **hint_kw)
-        elif use_c1:
-            y = a = ops.conv_c1_fwd(xt, w, reflect=bool(reflect), affine=(co[0], co[1]),
-                                    act=ops.ACT_RELU if relu else ops.ACT_NONE, addsrc=residual)
-        else:
-            y = a = op.fwd(xt, w, x2=x2, affine=(co[0], co[1]), act=ops.ACT_RELU if relu else ops.ACT_NONE, addsrc=residual)
+        a = y
+    elif (defer and out_info is not None and residual is None and _FUSE_TRAIN_BN and ldt == torch.float32
+            and ctx.dtype == torch.float32):
+        a = out_info                                      # scale / shift / ReLU happen in the consumer's loader
     else:
-        if not bn.training:
-            y = (alt_fwd(xt, w, **in_kw, **hint_kw) if use_fft else ops.conv_c1_fwd(xt, w, reflect=bool(reflect)) if use_c1
-                 else op.fwd(xt, w, x2=x2))
+        if (up_out is not None and _FUSE_UP2X_BF16 and ctx.dtype == torch.bfloat16 and y.is_contiguous()
+                and (residual is None or residual.is_contiguous()) and y.shape[0] * 2 * y.shape[1] <= 65535
+                and y.shape[3] % 4 == 0):             # (the fused kernel's channel-vector width; other shapes take the two-pass form)
+            a, a_up = ops.bn_apply_up2x(y, co[0], co[1], relu, residual, align_corners=bool(up_out), out_dtype=ctx.dtype)
         else:
-            out_info = BnOut(y, co, relu)
-        if (defer and out_info is not None and residual is None and _FUSE_TRAIN_BN and ldt == torch.float32
-                and ctx.dtype == torch.float32):
-            a = out_info                                  # scale / shift / ReLU happen in the consumer's loader
-        else:
-            if (up_out is not None and _FUSE_UP2X_BF16 and ctx.dtype == torch.bfloat16 and y.is_contiguous()
-                    and (residual is None or residual.is_contiguous()) and y.shape[0] * 2 * y.shape[1] <= 65535
-                    and y.shape[3] % 4 == 0):         # (the fused kernel's channel-vector width; other shapes take the two-pass form)
-                a, a_up = ops.bn_apply_up2x(y, co[0], co[1], relu, residual, align_corners=bool(up_out), out_dtype=ctx.dtype)
-            else:
-                a = ops.bn_apply(y, co[0], co[1], relu, residual, out_dtype=ctx.dtype)
-            if out_info is not None and ctx.record and _FUSE_TRAIN_BN:
-                ctx.bn_src[id(a)] = out_info
+            a = ops.bn_apply(y, co[0], co[1], relu, residual, out_dtype=ctx.dtype)
+        if out_info is not None and ctx.record and _FUSE_TRAIN_BN:
+            ctx.bn_src[id(a)] = out_info
     # the layer's input is an upsampled tensor whose producer kept the low-resolution source (up_out above): a reflection-padded
     # layer's fold pass can write dL/d(source) directly
-    up_in = None
-    if (not isinstance(x, (BnOut, Up2x)) and x2 is None and reflect and not use_fft and conv.in_channels % 4 == 0
-            and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0):
-        up_in = ctx.up_src.get(id(x))
+    up_in = ctx.up_src.get(id(x)) if path.up_fold else None
     if ctx.record:
         in_hw = (x.shape[1], x.shape[2])
         bn_training = bn.training
@@ -661,15 +645,14 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                                "(requires_grad False on the conv and BN parameters): the guide network of --latent_grad")
             if residual is not None:
                 ctx.add_grad(residual, da)
-            dyb = None
-            if (bn_training and use_fft_only and _FUSE_TRAIN_BN and _FUSE["fft_dyb"] and da.is_contiguous()
-                    and da.dtype == torch.float32):
+            extra = {}
+            if bn_training and path.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32:
                 # frequency-domain layer: dy has one reader (the dy transform), which applies pass 3 of the BatchNorm
                 # backward while loading -- dy is never written
                 kk = ops.bn_bwd_coeffs(da, y, co, relu, bn.weight.grad if not frozen else None,
                                        bn.bias.grad if not frozen else None, partial=out_info.partial)
                 out_info.partial = None
-                dy, dyb = da, (y, co, kk, relu)
+                dy, extra["dyb"] = da, (y, co, kk, relu)
             elif bn_training:
                 dy = ops.bn_bwd(da, y, bn.weight.data, co, relu, bn.weight.grad if not frozen else None,
                                 bn.bias.grad if not frozen else None, out_dtype=ldt, partial=out_info.partial)
@@ -677,32 +660,24 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
             else:
                 dy = ops.bn_eval_bwd(da, y, co, (2 if fused else 1) if relu else 0, out_dtype=ldt)
             want_dx = need_dx and ctx.wants_dx(x)
-            if use_fft:
-                # one transform of dy feeds both gradients; the forward's input spectrum is reused for dw
-                gv = None
-                if not frozen:
-                    gv = tap_view(conv.weight.grad, isinstance(conv, torch.nn.ConvTranspose2d))
-                    if gv is None:
-                        raise GdnError("weight.grad is not tap-major")
+            if path.bwd is not None:
+                # one transform of dy feeds both gradients; the forward's transformed input is reused for dw
+                gv = None if frozen else _grad_tap(conv)
                 if gv is not None or want_dx:
                     bnb = None
-                    if (xin is not None and want_dx and xin.y.dtype == torch.float32
-                            and _FUSE["fft_bnb" if use_fft_only else "wino_bnb"]):
+                    if xin is not None and want_dx and xin.y.dtype == torch.float32:
                         # x = [relu](BN_train(xin.y)) and this data gradient is its final gradient: emit the producer's
                         # BatchNorm-backward partial sums from the epilogue that writes dx
-                        slots = bnb_slots(x.shape[0], x.shape[1], x.shape[2])
+                        slots = path.bnb_slots()
                         if slots > 0:
                             part = torch.empty((slots, 2, conv.in_channels), dtype=torch.float32, device=dy.device)
                             bnb = (xin.y, xin.co, xin.relu, part)
-                    extra = {"dyb": dyb} if dyb is not None else {}
-                    if bnb is not None:
-                        extra["bnb"] = bnb
                     gx = x                                  # the tensor whose gradient this layer's dx is
                     if up is not None:
                         extra["up2x"] = up.mode             # ... the low-resolution source of the deferred upsampling
                         gx = up.src
-                    dx = alt_bwd(dy, w, in_hw, dw_tap=gv, need_dx=want_dx, **{bstate_kw: xf},
-                                 addsrc=ctx.pop_grad_as(gx, ldt) if want_dx else None, **extra, **hint_kw)
+                    dx = path.bwd(dy, w, in_hw, state, dw_tap=gv, need_dx=want_dx,
+                                  addsrc=ctx.pop_grad_as(gx, ldt) if want_dx else None, bnb=bnb, **extra)
                     if want_dx:
                         ctx.grads[id(gx)] = (gx, dx)
                         if bnb is not None:
@@ -711,7 +686,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                     ctx.grads_done(bn.weight, bn.bias, conv.weight)
                 return
             if not frozen:
-                if use_c1 and dy.is_contiguous() and conv.in_channels == 1:
+                if path.c1_wgrad and dy.is_contiguous():
                     ops.conv_c1_wgrad(xt, dy, tap_view(conv.weight.grad, False), reflect=bool(reflect))
                 else:
                     _wgrad_into(ctx, conv, xt, dy, x2)
@@ -720,7 +695,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                 wt = ops.transpose_taps(_w_tap(conv)[0], dtype=ldt)
                 if x2 is None:
                     bnb = None
-                    if (xin is not None and ldt == torch.bfloat16 and xin.y.dtype == ldt and _FUSE_TRAIN_BN and _FUSE["ring_bnb"]
+                    if (xin is not None and ldt == torch.bfloat16 and xin.y.dtype == ldt and _FUSE_TRAIN_BN
                             and xin.y.is_contiguous()):
                         # x = [relu](BN_train(xin.y)) and this data gradient is its final gradient (we are its first consumer;
                         # the other consumers' gradients arrive as addsrc): the LDS-DMA ring kernel's epilogue emits the
@@ -778,7 +753,7 @@ def conv_head_tanh(ctx, x, conv):
             dpre = ops.tanh_bwd(do.contiguous(), out)
             # 64 -> 1 heads: both gradients are 1 <-> 64 channel correlations with the single-channel d(pre-tanh) as the
             # staged image (csrc/conv_c1.hip); a Conv2d head flips the taps, a ConvTranspose2d head does not
-            c1 = (_C1 and x.is_contiguous() and conv.out_channels == 1
+            c1 = (x.is_contiguous() and conv.out_channels == 1
                   and ops.c1_ok(dpre, conv.in_channels, conv.kernel_size[0], conv.stride[0], conv.padding[0]))
             if conv.weight.requires_grad:
                 if c1:

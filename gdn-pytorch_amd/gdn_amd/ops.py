@@ -159,7 +159,6 @@ def workspace(nbytes, device, tag="ws"):
 
 
 _side_streams = {}
-_FFT_OVERLAP = os.environ.get("GDN_FFT_NO_OVERLAP") is None
 
 
 def side_stream(device):
@@ -429,7 +428,8 @@ class Conv:
         up2x: the forward upsampled a low-resolution x on load; dx (and addsrc) are that tensor's gradient [B,H/2,W/2,Cin]
         (in_hw stays the convolution's input extent).
         bnb = (y_in, coeffs[4,Cin], relu, partial[fft_bnb_slots,2,Cin]): dx is the final gradient of this layer's input
-        [relu](BN_train(y_in)); the pass that writes dx fills `partial` with that BatchNorm's backward sums (bn_bwd `partial`)."""
+        [relu](BN_train(y_in)); the pass that writes dx fills `partial` with that BatchNorm's backward sums (bn_bwd `partial`);
+        it needs need_dx."""
         _chk(dy, "dy")
         B = dy.shape[0]
         H, W = in_hw
@@ -437,7 +437,9 @@ class Conv:
         nb = int(lib.gdn_fftconv_bwd_workspace_bytes(ref))
         if nb == 0:
             raise GdnError("fftconv: unsupported layer k=%d stride=%d" % (self.k, self.stride))
-        by, bco, brelu, bpart = bnb if (bnb is not None and need_dx) else (None, None, False, None)
+        if bnb is not None and not need_dx:
+            raise GdnError("fft_bwd: bnb needs the data gradient (need_dx)")
+        by, bco, brelu, bpart = bnb if bnb is not None else (None, None, False, None)
         if bpart is not None and (bpart.dtype != torch.float32 or not bpart.is_contiguous()
                                   or tuple(bpart.shape) != (int(lib.gdn_fftconv_bnb_slots(ref)), 2, self.cin)):
             raise GdnError("fft_bwd: bnb partial must be a dense float32 [%d, 2, %d]" % (int(lib.gdn_fftconv_bnb_slots(ref)), self.cin))
@@ -454,7 +456,7 @@ class Conv:
                                 _p(dw_tap), _p(yy), 0 if yy is None else _ld(yy), _p(yco), _p(ykk), 1 if yrelu else 0,
                                 _p(by), 0 if by is None else _ld(by), _p(bco), 1 if brelu else 0, _p(bpart),
                                 int(up2x), phases, _p(ws), nb, st)
-        if dw_tap is not None and need_dx and _FFT_OVERLAP:
+        if dw_tap is not None and need_dx:
             # the two chains only share the spectrum of dy and are each latency-bound: the weight-gradient chain runs on a
             # second stream of OURS next to the data-gradient chain (fork after the transform, join before returning)
             main = torch.cuda.current_stream(dy.device)
@@ -531,10 +533,12 @@ class Conv:
             raise GdnError("winoconv: unsupported layer k=%d stride=%d" % (self.k, self.stride))
         if tuple(dy.shape[1:]) != (Ho, Wo, self.cout):
             raise GdnError("wino_bwd: dy shape %s does not match layer output" % (tuple(dy.shape),))
+        if bnb is not None and not need_dx:
+            raise GdnError("wino_bwd: bnb needs the data gradient (need_dx)")
         dx = torch.empty((B, H // 2, W // 2, self.cin) if up2x else (B, H, W, self.cin), dtype=torch.float32,
                          device=dy.device) if need_dx else None
         ws = workspace(nb, dy.device, "fft")
-        by, bco, brelu, bpart = bnb if (bnb is not None and need_dx) else (None, None, False, None)
+        by, bco, brelu, bpart = bnb if bnb is not None else (None, None, False, None)
         lib.gdn_winoconv_bwd(ref, _p(dy), _ld(dy), _p(w_tap), _p(state), _p(dx), 0 if dx is None else _ld(dx), _p(addsrc),
                              0 if addsrc is None else _ld(addsrc), _p(dw_tap), _p(by), 0 if by is None else _ld(by), _p(bco),
                              1 if brelu else 0, _p(bpart), int(up2x), _p(ws), nb, stream())

@@ -192,23 +192,26 @@ def test_fftconv_is_deterministic(gpu):
         assert torch.equal(a, b)
 
 
-def test_engine_fft_switch_matches_direct(gpu, monkeypatch):
-    """One ResidualBlock-shaped layer through the engine with the frequency-domain path on and off."""
-    from gdn_amd import engine
+def test_engine_fft_path_matches_direct(gpu, monkeypatch):
+    """One ResidualBlock-shaped layer through the engine with the frequency-domain path on and off (off: fft_ok says no,
+    so the engine takes the direct kernels)."""
+    from gdn_amd import ops
     import gdn_amd.AE_model_unet as M
     torch.manual_seed(5)
     outs = {}
-    for min_k in (0, 5):
-        monkeypatch.setattr(engine, "_FFT_MIN_K", min_k)
-        torch.manual_seed(5)
-        blk = M.ResidualBlock(64, 64, 9, 4).to(gpu)
-        x = torch.randn(2, 64, 40, 72, device=gpu, requires_grad=True)
-        y = blk(x)
-        y.square().mean().backward()
-        outs[min_k] = (y.detach().clone(), x.grad.clone(), [p.grad.clone() for p in blk.parameters()])
-    close(outs[5][0], outs[0][0], what="block out")
-    close(outs[5][1], outs[0][1], what="block dx")
-    for a, b in zip(outs[5][2], outs[0][2]):
+    for on in (False, True):
+        with monkeypatch.context() as mp:
+            if not on:
+                mp.setattr(ops.Conv, "fft_ok", lambda self, *a, **k: False)
+            torch.manual_seed(5)
+            blk = M.ResidualBlock(64, 64, 9, 4).to(gpu)
+            x = torch.randn(2, 64, 40, 72, device=gpu, requires_grad=True)
+            y = blk(x)
+            y.square().mean().backward()
+            outs[on] = (y.detach().clone(), x.grad.clone(), [p.grad.clone() for p in blk.parameters()])
+    close(outs[True][0], outs[False][0], what="block out")
+    close(outs[True][1], outs[False][1], what="block dx")
+    for a, b in zip(outs[True][2], outs[False][2]):
         close(a, b, what="block param grad")
 
 
@@ -252,8 +255,10 @@ def test_input_affine_and_bn_backward_partials(gpu, path, k, C, B, H, W):
     (1) in_affine: conv(relu(y1*scale + shift)) with the affine applied in the patch loader == conv of the materialised
         activation (zero padding stays zero);
     (2) bnb: the data-gradient epilogue's per-slot partials sum to sum(dz), sum(dz*xhat) of the BatchNorm backward, dz
-        being the final dx (+ addsrc) masked by the producer's ReLU."""
+        being the final dx (+ addsrc) masked by the producer's ReLU; without a data gradient (need_dx False) bnb is an error,
+    not a partial buffer left unwritten."""
     from gdn_amd import ops
+    from gdn_amd._lib import GdnError
     g = torch.Generator().manual_seed(k * 100 + C)
     op = ops.Conv(C, C, k, 1, k // 2)
     y1 = torch.randn(B, H, W, C, generator=g).to(gpu)
@@ -309,6 +314,8 @@ def test_input_affine_and_bn_backward_partials(gpu, path, k, C, B, H, W):
         close(r1, r0, rtol=1e-4, atol_scale=1e-5, what=path + " bn_bwd dy from partials")
         close(dg1, dg0, rtol=1e-4, atol_scale=1e-5, what="dgamma")
         close(db1, db0, rtol=1e-4, atol_scale=1e-5, what="dbeta")
+    with pytest.raises(GdnError, match="need_dx"):
+        bwd(dy, w, (H, W), need_dx=False, bnb=(y1, co, True, torch.empty((slots, 2, C), device=gpu)))
 
 
 @pytest.mark.parametrize("C,k,B,H,W", [(64, 9, 1, 24, 1060), (128, 5, 1, 14, 1030)], ids=["k9_w1060", "k5_w1030"])

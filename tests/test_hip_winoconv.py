@@ -84,19 +84,22 @@ def test_winoconv_full_size_adjoint_and_direct(gpu, H, W):
     close(dw, dw_d, rtol=1e-4, atol_scale=2e-5, what="wgrad vs direct, full size")
 
 
-def test_engine_winograd_switch_matches_direct(gpu, monkeypatch):
-    """One 512-channel ResidualBlock through the engine with the Winograd path on and off."""
-    from gdn_amd import engine
+def test_engine_winograd_path_matches_direct(gpu, monkeypatch):
+    """One 512-channel ResidualBlock through the engine with the Winograd path on and off (off: wino_ok says no, so the
+    engine takes the direct kernels)."""
+    from gdn_amd import ops
     import gdn_amd.AE_model_unet as M
     outs = {}
     for on in (False, True):
-        monkeypatch.setattr(engine, "_WINOGRAD", on)
-        torch.manual_seed(11)
-        blk = M.ResidualBlock(512, 512, 3, 1).to(gpu)
-        x = torch.randn(2, 512, 8, 26, device=gpu, requires_grad=True)
-        y = blk(x)
-        y.square().mean().backward()
-        outs[on] = (y.detach().clone(), x.grad.clone(), [p.grad.clone() for p in blk.parameters()])
+        with monkeypatch.context() as mp:
+            if not on:
+                mp.setattr(ops.Conv, "wino_ok", lambda self, *a, **k: False)
+            torch.manual_seed(11)
+            blk = M.ResidualBlock(512, 512, 3, 1).to(gpu)
+            x = torch.randn(2, 512, 8, 26, device=gpu, requires_grad=True)
+            y = blk(x)
+            y.square().mean().backward()
+            outs[on] = (y.detach().clone(), x.grad.clone(), [p.grad.clone() for p in blk.parameters()])
     close(outs[True][0], outs[False][0], what="block out")
     close(outs[True][1], outs[False][1], what="block dx")
     for a, b in zip(outs[True][2], outs[False][2]):
