@@ -17,7 +17,9 @@ reference's sample contract ``(gt[B,1,H,W], rgb[B,3,H,W], sparse[B,1,H,W])`` in 
 Evaluation (--mode DtoD_test / RtoD_test, :234-307): ``--real_test`` evaluates KITTI on the Eigen test split
 (TestFolder) instead of val.txt; ``--dataset NYU`` evaluates the NYU Depth v2 test set with compute_errors_NYU;
 ``--img_save`` writes the output depth, ground truth and input colour of every test image as JPEG under --result_dir,
-from the validation pass itself.  NYU and Make3D training and Make3D evaluation are not implemented.
+from the validation pass itself.  NYU training: pass ``train_loader=datasets.GpuNYUAugmentLoader(...)`` (the NYU transform
+of :94-129 on the GPU) and a GpuCropLoader over the test set to run() with args.dataset == 'NYU'; the command line does
+not build them.  Make3D training and evaluation are not implemented.
 """
 import os
 import sys

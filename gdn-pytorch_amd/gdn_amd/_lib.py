@@ -116,6 +116,13 @@ _SIGS = {
     "gdn_depth_metrics_make3d": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _P, _P, _sz, _P]),
     "gdn_crop_normalize": (c_int32, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "gdn_bytescale_u8": (c_int32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
+    "gdn_nyu_augment_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "gdn_nyu_augment": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _P, _i32, _i32, _P, _P, _P, _sz, _P]),
+    "gdn_pil_resize_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "gdn_pil_resize_bilinear": (c_int32, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                          _P, _P, _sz, _P]),
+    "gdn_spline_rotate3_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "gdn_spline_rotate3": (c_int32, [_P, _i32, _i32, _i32, _i32, _P, _P, _i32, _P, _P, _sz, _P]),
     "gdn_adam_step": (c_int32, [_P, _P, _P, _P, _i64, _f, _f, _f, _f, _f, _i32, _f, _P]),
     "gdn_adam_step_dev": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),

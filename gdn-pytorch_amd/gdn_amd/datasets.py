@@ -11,6 +11,10 @@ in the reference's call order.
 Evaluation (GDN_main.py:64-79, :128-130): ``TestFolder`` reads the Eigen test split (KITTI files already at the network's
 size: the validation transform of gdn_kitti_augment applies), ``NYUdataset(train=False)`` the NYU Depth v2 test set, whose
 CenterCrop + ArrayToTensor + Normalize runs batched in ``GpuCropLoader`` (gdn_crop_normalize).
+
+NYU training (GDN_main.py:94-129, datasets_list.py:366-443): ``NYUdataset(train=True)`` reads the training split and
+``GpuNYUAugmentLoader`` runs its random crop / spline rotation / imresize / flip / colour transform in gdn_nyu_augment;
+the host decodes the files and makes the reference's draws (``draw_params_nyu``).
 """
 import concurrent.futures as cf
 import pathlib
@@ -112,19 +116,24 @@ class TestFolder:
 
 
 class NYUdataset:
-    """NYU Depth v2 test set (datasets_list.py:366-444, train=False): root/test/test_depths/*.png (16-bit depth) paired
-    in sorted order with root/test/test_colors/*.png.  Samples are the raw decoded (gt, rgb, gt) -- the same depth array
-    twice, as the reference returns it; GpuCropLoader applies the validation transform.  The order is the sorted one
-    (the reference shuffles unless --img_test).  train=True raises: NYU training is not implemented."""
+    """NYU Depth v2 (datasets_list.py:366-444).  train=False: root/test/test_depths/*.png (16-bit depth) paired in sorted
+    order with root/test/test_colors/*.png, in that order (the reference shuffles unless --img_test).  train=True:
+    root/train/train_depths/*.png and root/train/train_colors/*.png, sorted, paired, then shuffled with random.Random(seed)
+    (the reference seeds with time()).  Samples are the raw decoded (gt, rgb, gt) -- the same depth array twice, as the
+    reference returns it; GpuCropLoader applies the validation transform, GpuNYUAugmentLoader the training one."""
 
     def __init__(self, root, args=None, seed=None, train=False, transform=None, transform_2=None, mode="DtoD"):
-        if train:
-            raise GdnError("NYUdataset(train=True): NYU training (random crop / rotate / imresize) is not implemented; "
-                           "only the test set can be read")
         self.root = pathlib.Path(root)
         self.train, self.mode, self.args = train, mode, args
-        self.depth_folder = self.root / "test" / "test_depths"
-        self.img_folder = self.root / "test" / "test_colors"
+        split = "train" if train else "test"
+        self.depth_folder = self.root / split / (split + "_depths")
+        self.img_folder = self.root / split / (split + "_colors")
+        if train:
+            for d in (self.depth_folder, self.img_folder):
+                if not d.is_dir():
+                    raise GdnError("NYU training set: %s not found (expected root/train/train_depths/*.png and "
+                                   "root/train/train_colors/*.png)" % d)
+        self._rng = random.Random(seed)
         self.crawl_folders()
 
     def crawl_folders(self):
@@ -133,6 +142,8 @@ class NYUdataset:
         if len(gt) != len(rgbs):
             raise GdnError("%s has %d png, %s has %d" % (self.depth_folder, len(gt), self.img_folder, len(rgbs)))
         self.samples = [{"gt": g, "rgb": r} for g, r in zip(gt, rgbs)]
+        if self.train:
+            self._rng.shuffle(self.samples)
 
     def __getitem__(self, index):
         s = self.samples[index]
@@ -263,3 +274,73 @@ class GpuCropLoader(GpuAugmentLoader):
             third = gt if all(s[2] is s[0] for s in samples) else \
                 ops.crop_normalize(self._to_device([s[2] for s in samples]), H, W, off)
             yield gt, rgb, third
+
+
+NYU_CROP = ops.NYU_CROP
+
+
+def draw_params_nyu(h0, w0, mode, py_rng, np_rng):
+    """The reference's draws for one NYU training sample, in its call order (datasets_list.py:401-402, then
+    GDN_main.py:94-125 through transform_list.py): np.random.uniform(1, 1.2) -> img_s; np.random.uniform(1.0, 1.5) ->
+    scale; RandomCropNumpy's randint(s) on the int(img_s * 251) x int(img_s * 340) image (none when it is already
+    251 x 340; randint's upper bound is exclusive); RandomRotate's np.random.uniform(-4, 4) (DtoD) or (-5, 5) (RtoD);
+    RandomHorizontalFlip's random.random() < 0.5; RtoD only: RandomColor's np.random.uniform(0.8, 1.2).
+    The source size h0 x w0 enters no draw; it is checked only."""
+    if mode not in ("DtoD", "RtoD"):
+        raise GdnError("draw_params_nyu: mode must be DtoD or RtoD, got %r" % (mode,))
+    if h0 <= 0 or w0 <= 0:
+        raise GdnError("draw_params_nyu: empty source %dx%d" % (h0, w0))
+    th, tw = NYU_CROP
+    img_s = np_rng.uniform(1, 1.2)
+    scale = np_rng.uniform(1.0, 1.5)
+    h1, w1 = int(img_s * 251.0), int(img_s * 340.0)
+    y1 = x1 = 0
+    if h1 == th and w1 == tw:
+        pass
+    elif h1 == th:
+        x1 = int(np_rng.randint(0, w1 - tw))
+    elif w1 == tw:
+        y1 = int(np_rng.randint(0, h1 - th))
+    else:
+        y1 = int(np_rng.randint(0, h1 - th))
+        x1 = int(np_rng.randint(0, w1 - tw))
+    angle = np_rng.uniform(-4, 4) if mode == "DtoD" else np_rng.uniform(-5, 5)
+    flip = 1 if py_rng.random() < 0.5 else 0
+    mult = np_rng.uniform(0.8, 1.2) if mode == "RtoD" else 1.0
+    return dict(img_s=img_s, scale=scale, h1=h1, w1=w1, y1=y1, x1=x1, angle=angle, flip=flip, mult=mult)
+
+
+class GpuNYUAugmentLoader(GpuAugmentLoader):
+    """Batches of (gt, rgb, gt) as normalised NCHW float32 tensors on `device` with the reference's NYU training transform
+    (GDN_main.py:94-129, datasets_list.py:399-430) executed by gdn_nyu_augment: the host decodes the files and makes the
+    draws of draw_params_nyu per sample, in batch order; `last_params` keeps the last batch's draws.  Ordering, sharding
+    (rank / world / order_seed) and drop_last are GpuAugmentLoader's.  height x width <= 251 x 340."""
+
+    def __init__(self, dataset, batch_size, device, height, width, mode="DtoD", seed=None, workers=0, drop_last=False,
+                 rank=0, world=1, order_seed=None):
+        if mode not in ("DtoD", "RtoD"):
+            raise GdnError("GpuNYUAugmentLoader: mode must be DtoD or RtoD, got %r" % (mode,))
+        if not (0 < height <= NYU_CROP[0] and 0 < width <= NYU_CROP[1]):
+            raise GdnError("GpuNYUAugmentLoader: %dx%d does not fit the %dx%d crop" % ((height, width) + NYU_CROP))
+        super().__init__(dataset, batch_size, device, train=True, seed=seed, workers=workers, drop_last=drop_last,
+                         rank=rank, world=world, order_seed=order_seed)
+        self.size, self.mode = (int(height), int(width)), mode
+
+    def __iter__(self):
+        H, W = self.size
+        order = self._epoch_order()
+        for b in range(len(self)):
+            samples = self._fetch(order[b * self.bs:(b + 1) * self.bs])
+            H0, W0 = samples[0][1].shape[:2]
+            for s in samples:
+                if any(x.shape[:2] != (H0, W0) for x in s):
+                    raise GdnError("all images of a batch must share one size, got %s" % ([x.shape for x in s],))
+                if s[1].ndim != 3 or s[1].shape[2] != 3 or s[1].dtype != np.uint8:
+                    raise GdnError("NYU colour images must be 8-bit RGB, got %s %s" % (s[1].dtype, s[1].shape))
+            draws = [draw_params_nyu(H0, W0, self.mode, self.py_rng, self.np_rng) for _ in samples]
+            self.last_params = draws
+            depth = self._to_device([np.ascontiguousarray(s[0][:, :, 0] if s[0].ndim == 3 else s[0], dtype=np.float32)
+                                     for s in samples])
+            rgb = self._to_device([s[1] for s in samples])
+            gt, img = ops.nyu_augment(depth, rgb, draws, H, W, self.mode)
+            yield gt, img, gt

@@ -5,8 +5,10 @@ fp32, channel stride 1; a channel slice of a wider tensor is allowed (pixel
 pitch ``ld`` = stride(2)).  Everything launches on torch's current stream.
 """
 import ctypes
+import math
 import os
 
+import numpy as np
 import torch
 
 from ._lib import ConvGeom, GdnError, lib
@@ -1003,6 +1005,129 @@ def kitti_augment(src, params, train=True):
     ws = workspace(nb, src.device, "augment")
     lib.gdn_kitti_augment(_p(src), 1 if src.dtype == torch.float32 else 0, B, H, W, C, _p(params), 1 if train else 0,
                           _p(dst), _p(ws), nb, stream())
+    return dst
+
+
+NYU_CROP = (251, 340)          # RandomCropNumpy's window (GDN_main.py:99, :110)
+
+# gdn_nyu_aug_params (include/gdn_hip.h)
+NYU_PARAMS_DTYPE = np.dtype([("h1", "<i4"), ("w1", "<i4"), ("y1", "<i4"), ("x1", "<i4"), ("h2", "<i4"), ("w2", "<i4"),
+                             ("cy", "<i4"), ("cx", "<i4"), ("flip", "<i4"), ("reserved", "<i4"), ("scale", "<f8"),
+                             ("mult", "<f8"), ("m", "<f8", (4,)), ("off", "<f8", (2,)), ("zn1", "<f8", (2,))])
+assert NYU_PARAMS_DTYPE.itemsize == 120
+
+
+def spline_z_pow(n):
+    """z**n for the cubic B-spline pole z = sqrt(3) - 2, as the running product the device uses."""
+    z, p = math.sqrt(3.0) - 2.0, 1.0
+    for _ in range(n):
+        p = p * z
+    return p
+
+
+def rotate_matrix(angle, n0, n1):
+    """(matrix [4], offset [2]) that scipy.ndimage.rotate(reshape=False, axes=(0, 1)) computes for an n0 x n1 plane:
+    cosdg / sindg of the angle in degrees, and the offset that keeps the centre in place."""
+    try:
+        from scipy import special
+    except ImportError as e:
+        raise GdnError("rotate_matrix: scipy.special (cosdg / sindg) is required to reproduce scipy.ndimage.rotate") from e
+    c, s = special.cosdg(angle), special.sindg(angle)
+    rot = np.array([[c, s], [-s, c]])
+    shape = np.array([n0, n1])
+    out_center = rot @ ((shape - 1) / 2)
+    in_center = (shape - 1) / 2
+    offset = in_center - out_center
+    return [float(v) for v in rot.ravel()], [float(v) for v in offset]
+
+
+def nyu_params(draws, H, W, mode):
+    """The per-sample gdn_nyu_aug_params (host numpy array) of draws made by datasets.draw_params_nyu."""
+    ch, cw = NYU_CROP
+    p = np.zeros(len(draws), NYU_PARAMS_DTYPE)
+    for b, d in enumerate(draws):
+        w2, h2 = (np.array([cw, ch]) * d["scale"]).astype(int)     # imresize(a, scale): (array(im.size) * scale).astype(int)
+        h1, w1, y1, x1 = (int(d[k]) for k in ("h1", "w1", "y1", "x1"))
+        if not (h1 >= ch and w1 >= cw and 0 <= y1 <= h1 - ch and 0 <= x1 <= w1 - cw and h2 >= ch and w2 >= cw):
+            raise GdnError("nyu_params: sample %d: inconsistent draws %s" % (b, d))
+        cy, cx = center_crop_offsets(ch, cw, H, W) if mode == "DtoD" else center_crop_offsets(int(h2), int(w2), H, W)
+        m, off = rotate_matrix(d["angle"], ch, cw)
+        p[b] = (h1, w1, y1, x1, h2, w2, cy, cx, 1 if d["flip"] else 0, 0, d["scale"], d.get("mult", 1.0), m, off,
+                (spline_z_pow(ch - 1), spline_z_pow(cw - 1)))
+    return p
+
+
+def nyu_augment(depth, rgb, draws, H, W, mode):
+    """The NYU training transform (GDN_main.py:94-129) of a batch on the device.
+    depth [B,H0,W0] or [B,H0,W0,1] float32, rgb [B,H0,W0,3] uint8, both on the GPU; draws: one dict per sample from
+    datasets.draw_params_nyu, or those draws already packed by nyu_params and copied to the device (a uint8 tensor).
+    Returns (depth [B,1,H,W], rgb [B,3,H,W]) float32, normalised."""
+    if mode not in ("DtoD", "RtoD"):
+        raise GdnError("nyu_augment: mode must be DtoD or RtoD, got %r" % (mode,))
+    if depth.dim() == 4 and depth.shape[3] == 1:
+        depth = depth[..., 0]
+    if not (depth.is_cuda and rgb.is_cuda and depth.dtype == torch.float32 and rgb.dtype == torch.uint8 and
+            depth.dim() == 3 and rgb.dim() == 4 and rgb.shape[3] == 3 and tuple(rgb.shape[:3]) == tuple(depth.shape)):
+        raise GdnError("nyu_augment: depth must be [B,H0,W0] float32 and rgb [B,H0,W0,3] uint8, on the GPU")
+    B, H0, W0 = depth.shape
+    if not (0 < H <= NYU_CROP[0] and 0 < W <= NYU_CROP[1]):
+        raise GdnError("nyu_augment: output %dx%d must fit the %dx%d crop" % ((H, W) + NYU_CROP))
+    if isinstance(draws, torch.Tensor):
+        if not (draws.is_cuda and draws.dtype == torch.uint8 and draws.numel() == B * NYU_PARAMS_DTYPE.itemsize):
+            raise GdnError("nyu_augment: packed params must be a device uint8 tensor of %d bytes" %
+                           (B * NYU_PARAMS_DTYPE.itemsize))
+        params = draws.contiguous()
+    else:
+        if len(draws) != B:
+            raise GdnError("nyu_augment: %d draws for a batch of %d" % (len(draws), B))
+        host = torch.from_numpy(nyu_params(draws, H, W, mode).view(np.uint8))
+        params = host.pin_memory().to(depth.device, non_blocking=True)
+    depth, rgb = depth.contiguous(), rgb.contiguous()
+    d_out = torch.empty((B, 1, H, W), dtype=torch.float32, device=depth.device)
+    c_out = torch.empty((B, 3, H, W), dtype=torch.float32, device=depth.device)
+    rtod = 1 if mode == "RtoD" else 0
+    nb = int(lib.gdn_nyu_augment_workspace_bytes(B, H0, W0, rtod))
+    ws = workspace(nb, depth.device, "nyu_augment")
+    lib.gdn_nyu_augment(_p(depth), _p(rgb), B, H0, W0, rtod, _p(params), H, W, _p(d_out), _p(c_out), _p(ws), nb, stream())
+    return d_out, c_out
+
+
+def pil_resize(src, out_h, out_w, window=None, f_mode=False, bytescale=None):
+    """Pillow BILINEAR resize of a [B,H0,W0,C] uint8/float32 device batch to out_h x out_w, computing only `window`
+    (y, x, h, w; default the whole output).  f_mode: Pillow 'F' on float32 data; else 8 bpc, with scipy's bytescale first
+    when `bytescale` (default: for float32 sources).  Returns [B,h,w,C] float32 ('F') or uint8."""
+    if not src.is_cuda or src.dtype not in (torch.uint8, torch.float32) or src.dim() != 4:
+        raise GdnError("pil_resize: src must be a [B,H0,W0,C] uint8/float32 tensor on the GPU")
+    src = src.contiguous()
+    B, H0, W0, C = src.shape
+    f32 = src.dtype == torch.float32
+    if bytescale is None:
+        bytescale = f32 and not f_mode
+    wy, wx, wh, ww = (0, 0, out_h, out_w) if window is None else window
+    dst = torch.empty((B, wh, ww, C), dtype=torch.float32 if f_mode else torch.uint8, device=src.device)
+    nb = int(lib.gdn_pil_resize_workspace_bytes(B, H0, C, ww))
+    ws = workspace(max(nb, 1), src.device, "pil_resize")
+    lib.gdn_pil_resize_bilinear(_p(src), 1 if f32 else 0, B, H0, W0, C, 1 if f_mode else 0, 1 if bytescale else 0,
+                                int(out_h), int(out_w), int(wy), int(wx), int(wh), int(ww), _p(dst), _p(ws), nb, stream())
+    return dst
+
+
+def spline_rotate(src, angle=None, matrix=None, offset=None, clip=True):
+    """scipy.ndimage.rotate(plane, angle, reshape=False, order=3, mode='constant') of every plane of a [B,C,H,W] float32
+    device batch (or the affine map `matrix`, `offset` given directly); clip: to each sample's input min/max."""
+    if not src.is_cuda or src.dtype != torch.float32 or src.dim() != 4:
+        raise GdnError("spline_rotate: src must be a [B,C,H,W] float32 tensor on the GPU")
+    src = src.contiguous()
+    B, C, H, W = src.shape
+    if matrix is None:
+        matrix, offset = rotate_matrix(angle, H, W)
+    m = (ctypes.c_double * 4)(*[float(v) for v in matrix])
+    o = (ctypes.c_double * 2)(*[float(v) for v in offset])
+    dst = torch.empty_like(src)
+    nb = int(lib.gdn_spline_rotate3_workspace_bytes(B, C, H, W))
+    ws = workspace(max(nb, 1), src.device, "spline_rotate")
+    lib.gdn_spline_rotate3(_p(src), B, C, H, W, ctypes.cast(m, ctypes.c_void_p), ctypes.cast(o, ctypes.c_void_p),
+                           1 if clip else 0, _p(dst), _p(ws), nb, stream())
     return dst
 
 

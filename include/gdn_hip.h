@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 const char* gdn_strerror(int status);
@@ -577,6 +577,61 @@ size_t gdn_kitti_augment_workspace_bytes(int32_t B);
 int gdn_kitti_augment(const void* src, int32_t src_is_f32, int32_t B, int32_t H, int32_t W, int32_t C,
                       const int32_t* params, int32_t train, float* dst,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * NYU Depth v2 training-time augmentation on the device (GDN_main.py:94-129, datasets_list.py:399-430), bit-exact with
+ * the host pipeline: imresize (bytescale + Pillow BILINEAR, or Pillow 'F' for depth) to img_s x (251, 340), depth /
+ * scale, RandomCropNumpy(251, 340), RandomRotate (scipy.ndimage.rotate, order 3, mode 'constant', reshape=False, clipped
+ * to the input's range over all channels), imresize by `scale`, CenterCrop (offsets from the colour image), flip,
+ * RandomColor (RtoD), ArrayToTensor, Normalize.  DtoD rotates the depth alone and resizes the colour image once, to
+ * 251 x 340; RtoD rotates colour and depth together (Merge) and resizes both again.
+ * One struct per sample, in DEVICE memory, filled by the host from the reference's random draws.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+    int32_t h1, w1;       /* first resize: int(img_s * 251) x int(img_s * 340) */
+    int32_t y1, x1;       /* RandomCropNumpy: the 251 x 340 window inside h1 x w1 */
+    int32_t h2, w2;       /* second resize: int(251 * scale) x int(340 * scale) */
+    int32_t cy, cx;       /* CenterCrop offsets: round-half-even of ((251 - H) / 2, (340 - W) / 2) in DtoD, of
+                             ((h2 - H) / 2, (w2 - W) / 2) in RtoD; the same window is cut from every image */
+    int32_t flip;         /* RandomHorizontalFlip */
+    int32_t reserved;     /* 0 */
+    double scale;         /* the depth is divided by (float)scale after the first resize */
+    double mult;          /* RandomColor multiplier (RtoD; unused in DtoD) */
+    double m[4];          /* rotation, as scipy computes it: input (r, c) = (m0 y + m1 x + off0, m2 y + m3 x + off1) */
+    double off[2];
+    double zn1[2];        /* z^250, z^339 for the spline pole z = sqrt(3) - 2, as running products */
+} gdn_nyu_aug_params;
+
+/*   depth      [B][H0][W0] float32 (16-bit depth as decoded);  rgb [B][H0][W0][3] uint8
+ *   rtod       0: DtoD (angle range +-4, no RandomColor), 1: RtoD
+ *   H, W       output size, H <= 251, W <= 340
+ *   depth_out  [B][1][H][W] float32,  rgb_out [B][3][H][W] float32, both (v/255 - 0.5)/0.5 */
+size_t gdn_nyu_augment_workspace_bytes(int32_t B, int32_t H0, int32_t W0, int32_t rtod);
+int gdn_nyu_augment(const float* depth, const uint8_t* rgb, int32_t B, int32_t H0, int32_t W0, int32_t rtod,
+                    const gdn_nyu_aug_params* params, int32_t H, int32_t W, float* depth_out, float* rgb_out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* Building block: Pillow's bilinear resampler (Image.resize(..., BILINEAR)) for any scale, batched.
+ *   src        [B][H0][W0][C] uint8, or float32 when src_is_f32; 1 <= C <= 4, channels resized independently
+ *   f_mode     1: Pillow 'F' (float32 source, double weights normalised to 1, double sums, float32 between the passes);
+ *              0: 8 bpc (22-bit fixed point, horizontal pass rounded to uint8)
+ *   bytescale  8 bpc only: scipy's bytescale with each sample's min/max over all channels first (required for float32)
+ *   out_h x out_w  the size resized to; only the window (win_y, win_x, win_h, win_w), which must lie inside it, is computed
+ *   dst        [B][win_h][win_w][C]: float32 ('F') or uint8 (8 bpc) */
+size_t gdn_pil_resize_workspace_bytes(int32_t B, int32_t H0, int32_t C, int32_t win_w);
+int gdn_pil_resize_bilinear(const void* src, int32_t src_is_f32, int32_t B, int32_t H0, int32_t W0, int32_t C,
+                            int32_t f_mode, int32_t bytescale, int32_t out_h, int32_t out_w, int32_t win_y,
+                            int32_t win_x, int32_t win_h, int32_t win_w, void* dst, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* Building block: scipy.ndimage.rotate / affine_transform of order 3, mode 'constant', on float32 planes.
+ *   src, dst   [B][C][H][W] float32, H, W >= 4; every plane gets the same HOST matrix[4] and offset[2]:
+ *              output (y, x) reads the input at (m0 y + m1 x + off0, m2 y + m3 x + off1), 0 outside the plane
+ *   clip       1: clip each sample to the min/max of its C input planes (RandomRotate), 0: no clip */
+size_t gdn_spline_rotate3_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int gdn_spline_rotate3(const float* src, int32_t B, int32_t C, int32_t H, int32_t W, const double* matrix,
+                       const double* offset, int32_t clip, float* dst, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* ------------------------------------------------------------------------
  * Fused Adam with coupled L2 weight decay over one flat arena
