@@ -7,6 +7,8 @@
 // thread rebuilds the <= 3 horizontally filtered bytes it needs and filters them vertically: 9 source reads
 // per output pixel, no intermediate image.  HBM-bound byte work: 1 B/channel read (L2-resident re-reads),
 // 4 B/channel written.
+// aug_resident_kernel is the same per-pixel code over a batch picked by index from device-resident pools (three images per
+// launch, one set of coefficients per pixel); gather_* copy whole samples out of such pools for the NYU transform.
 #include "common.h"
 
 namespace {
@@ -79,6 +81,48 @@ __device__ __forceinline__ float normalize01(float v) {
     return __fdiv_rn(__fdiv_rn(v, 255.0f) - 0.5f, 0.5f);        // ArrayToTensor /255, Normalize (t - 0.5) / 0.5
 }
 
+// Validation transform of one pixel: the C channels at `px` (element offset of the pixel's first channel) normalised.
+__device__ __forceinline__ void val_pixel(const void* __restrict__ src, int f32, size_t px, int C, size_t plane,
+                                          float* __restrict__ out) {
+    for (int c = 0; c < C; ++c) {
+        const float v = f32 ? reinterpret_cast<const float*>(src)[px + c]
+                            : (float)reinterpret_cast<const unsigned char*>(src)[px + c];
+        out[(size_t)c * plane] = normalize01(v);
+    }
+}
+
+// Training transform of one output pixel of one image: the C channels through the two filter passes with the pixel's
+// coefficients ky, kx (which depend on the draws and the pixel only, not on the image).  `img` is the element offset of
+// the image in src; `sx0` the source column when the width does not change.
+__device__ __forceinline__ void aug_pixel(const void* __restrict__ src, int f32, size_t img, int H, int W, int C, int flip,
+                                          int sh, int sw, int sx0, const AxisK& ky, const AxisK& kx, float cmin, float bscale,
+                                          float* __restrict__ out) {
+    for (int c = 0; c < C; ++c) {
+        long long v = 1ll << (AUG_PREC - 1);
+        for (int r = 0; r < ky.n; ++r) {
+            const int sy = ky.x0 + r;
+            int hb;
+            if (sw != W) {                      // horizontal pass (only when the width changes, as Pillow does)
+                long long hsum = 1ll << (AUG_PREC - 1);
+                for (int j = 0; j < kx.n; ++j) {
+                    int sx = kx.x0 + j;
+                    if (flip) sx = W - 1 - sx;
+                    hsum += (long long)src_byte(src, f32, img + ((size_t)sy * W + sx) * C + c, cmin, bscale) * kx.k[j];
+                }
+                hb = clip8(hsum);
+            } else {
+                int sx = sx0;
+                if (flip) sx = W - 1 - sx;
+                hb = src_byte(src, f32, img + ((size_t)sy * W + sx) * C + c, cmin, bscale);
+            }
+            if (sh == H) { v = (long long)hb << AUG_PREC; break; }
+            v += (long long)hb * ky.k[r];
+        }
+        const int ob = sh == H ? (int)(v >> AUG_PREC) : clip8(v);
+        out[(size_t)c * H * W] = normalize01((float)ob);
+    }
+}
+
 __global__ __launch_bounds__(256) void aug_kernel(const void* __restrict__ src, int f32, int B, int H, int W, int C,
                                                   const int* __restrict__ params, int train,
                                                   const float* __restrict__ mm, float* __restrict__ dst) {
@@ -90,12 +134,7 @@ __global__ __launch_bounds__(256) void aug_kernel(const void* __restrict__ src, 
         const size_t img = (size_t)b * H * W * C;
         float* out = dst + (size_t)b * C * H * W + (size_t)oy * W + ox;
         if (!train) {
-            for (int c = 0; c < C; ++c) {
-                const size_t idx = img + ((size_t)oy * W + ox) * C + c;
-                const float v = f32 ? reinterpret_cast<const float*>(src)[idx]
-                                    : (float)reinterpret_cast<const unsigned char*>(src)[idx];
-                out[(size_t)c * H * W] = normalize01(v);
-            }
+            val_pixel(src, f32, img + ((size_t)oy * W + ox) * C, C, (size_t)H * W, out);
             continue;
         }
         const int* pr = params + b * 5;
@@ -109,31 +148,78 @@ __global__ __launch_bounds__(256) void aug_kernel(const void* __restrict__ src, 
         }
         const AxisK ky = axis_coeffs(H, sh, oy + offy);
         const AxisK kx = axis_coeffs(W, sw, ox + offx);
-        for (int c = 0; c < C; ++c) {
-            long long v = 1ll << (AUG_PREC - 1);
-            for (int r = 0; r < ky.n; ++r) {
-                const int sy = ky.x0 + r;
-                int hb;
-                if (sw != W) {                      // horizontal pass (only when the width changes, as Pillow does)
-                    long long hsum = 1ll << (AUG_PREC - 1);
-                    for (int j = 0; j < kx.n; ++j) {
-                        int sx = kx.x0 + j;
-                        if (flip) sx = W - 1 - sx;
-                        hsum += (long long)src_byte(src, f32, img + ((size_t)sy * W + sx) * C + c, cmin, bscale) * kx.k[j];
-                    }
-                    hb = clip8(hsum);
-                } else {
-                    int sx = ox + offx;
-                    if (flip) sx = W - 1 - sx;
-                    hb = src_byte(src, f32, img + ((size_t)sy * W + sx) * C + c, cmin, bscale);
-                }
-                if (sh == H) { v = (long long)hb << AUG_PREC; break; }
-                v += (long long)hb * ky.k[r];
-            }
-            const int ob = sh == H ? (int)(v >> AUG_PREC) : clip8(v);
-            out[(size_t)c * H * W] = normalize01((float)ob);
-        }
+        aug_pixel(src, f32, img, H, W, C, flip, sh, sw, ox + offx, ky, kx, cmin, bscale, out);
     }
+}
+
+// The same transform for a batch assembled from device-resident uint8 pools: sample sel[b][0] of each of the three pools,
+// one launch for the three tensors.  The filter coefficients of a pixel are computed once and serve every channel of the
+// three images.  Pool offsets are 64-bit: a colour pool at 128x416 passes 2^32 bytes at 26,888 samples.
+__global__ __launch_bounds__(256) void aug_resident_kernel(const unsigned char* __restrict__ p0, int C0,
+                                                           const unsigned char* __restrict__ p1, int C1,
+                                                           const unsigned char* __restrict__ p2, int C2, int B, int H, int W,
+                                                           const int* __restrict__ sel, int train, float* __restrict__ d0,
+                                                           float* __restrict__ d1, float* __restrict__ d2) {
+    const int64_t total = (int64_t)B * H * W;
+    const size_t plane = (size_t)H * W;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int ox = (int)(i % W);
+        const int oy = (int)((i / W) % H);
+        const int b = (int)(i / ((int64_t)W * H));
+        const int* pr = sel + b * 6;
+        const size_t smp = (size_t)pr[0] * plane;                 // pixels before the sample in every pool
+        const size_t pix = (size_t)oy * W + ox;
+        float* o0 = d0 + (size_t)b * C0 * plane + pix;
+        float* o1 = d1 + (size_t)b * C1 * plane + pix;
+        float* o2 = d2 + (size_t)b * C2 * plane + pix;
+        if (!train) {
+            val_pixel(p0, 0, (smp + pix) * C0, C0, plane, o0);
+            val_pixel(p1, 0, (smp + pix) * C1, C1, plane, o1);
+            val_pixel(p2, 0, (smp + pix) * C2, C2, plane, o2);
+            continue;
+        }
+        const int flip = pr[1], sh = pr[2], sw = pr[3], offy = pr[4], offx = pr[5];
+        const AxisK ky = axis_coeffs(H, sh, oy + offy);
+        const AxisK kx = axis_coeffs(W, sw, ox + offx);
+        aug_pixel(p0, 0, smp * C0, H, W, C0, flip, sh, sw, ox + offx, ky, kx, 0.f, 1.f, o0);
+        aug_pixel(p1, 0, smp * C1, H, W, C1, flip, sh, sw, ox + offx, ky, kx, 0.f, 1.f, o1);
+        aug_pixel(p2, 0, smp * C2, H, W, C2, flip, sh, sw, ox + offx, ky, kx, 0.f, 1.f, o2);
+    }
+}
+
+// dst[b] = pool[idx[b]] for samples of sample_bytes bytes; `bps` blocks share a sample.  16-byte copies when the sample's
+// source and destination are both 16-byte aligned, bytes for the tail (or for the whole sample otherwise).
+__global__ __launch_bounds__(256) void gather_copy_kernel(const unsigned char* __restrict__ pool, const int* __restrict__ idx,
+                                                          size_t sample_bytes, int bps, unsigned char* __restrict__ dst) {
+    const int b = blockIdx.x / bps, blk = blockIdx.x % bps;
+    const unsigned char* s = pool + (size_t)idx[b] * sample_bytes;
+    unsigned char* d = dst + (size_t)b * sample_bytes;
+    const size_t step = (size_t)bps * 256, first = (size_t)blk * 256 + threadIdx.x;
+    const bool vec = (((uintptr_t)s | (uintptr_t)d) & 15) == 0;
+    const size_t nvec = vec ? sample_bytes / 16 : 0;
+    for (size_t i = first; i < nvec; i += step)
+        reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(s)[i];
+    for (size_t i = nvec * 16 + first; i < sample_bytes; i += step) d[i] = s[i];
+}
+
+// the same gather widening uint16 to float32 (exact): 8 elements per 16-byte load, two 16-byte stores
+__global__ __launch_bounds__(256) void gather_u16_f32_kernel(const unsigned short* __restrict__ pool,
+                                                             const int* __restrict__ idx, size_t per_sample, int bps,
+                                                             float* __restrict__ dst) {
+    const int b = blockIdx.x / bps, blk = blockIdx.x % bps;
+    const unsigned short* s = pool + (size_t)idx[b] * per_sample;
+    float* d = dst + (size_t)b * per_sample;
+    const size_t step = (size_t)bps * 256, first = (size_t)blk * 256 + threadIdx.x;
+    const bool vec = (((uintptr_t)s | (uintptr_t)d) & 15) == 0;
+    const size_t nvec = vec ? per_sample / 8 : 0;
+    for (size_t i = first; i < nvec; i += step) {
+        const uint4 u = reinterpret_cast<const uint4*>(s)[i];
+        const f32x4 lo = {(float)(u.x & 0xffffu), (float)(u.x >> 16), (float)(u.y & 0xffffu), (float)(u.y >> 16)};
+        const f32x4 hi = {(float)(u.z & 0xffffu), (float)(u.z >> 16), (float)(u.w & 0xffffu), (float)(u.w >> 16)};
+        reinterpret_cast<f32x4*>(d)[2 * i] = lo;
+        reinterpret_cast<f32x4*>(d)[2 * i + 1] = hi;
+    }
+    for (size_t i = nvec * 8 + first; i < per_sample; i += step) d[i] = (float)s[i];
 }
 
 }  // namespace
@@ -156,5 +242,38 @@ extern "C" int gdn_kitti_augment(const void* src, int32_t src_is_f32, int32_t B,
     const int blocks = (int)(cdiv64(total, 256) < 4096 ? cdiv64(total, 256) : 4096);
     hipLaunchKernelGGL(aug_kernel, dim3(blocks), dim3(256), 0, st, src, src_is_f32, B, H, W, C, (const int*)params, train,
                        (const float*)mm, dst);
+    return gdn_launch_status();
+}
+
+extern "C" int gdn_kitti_augment_resident(const uint8_t* gt_pool, int32_t Cg, const uint8_t* rgb_pool, int32_t Cr,
+                                          const uint8_t* sparse_pool, int32_t Cs, int32_t H, int32_t W, const int32_t* sel,
+                                          int32_t B, int32_t train, float* gt_out, float* rgb_out, float* sparse_out,
+                                          void* stream) {
+    (void)hipGetLastError();
+    if (!gt_pool || !rgb_pool || !sparse_pool || !sel || !gt_out || !rgb_out || !sparse_out) return GDN_ERR_BAD_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || Cg <= 0 || Cg > 4 || Cr <= 0 || Cr > 4 || Cs <= 0 || Cs > 4) return GDN_ERR_BAD_ARG;
+    const int64_t total = (int64_t)B * H * W;
+    const int blocks = (int)(cdiv64(total, 256) < 4096 ? cdiv64(total, 256) : 4096);
+    hipLaunchKernelGGL(aug_resident_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gt_pool, Cg, rgb_pool, Cr,
+                       sparse_pool, Cs, B, H, W, (const int*)sel, train, gt_out, rgb_out, sparse_out);
+    return gdn_launch_status();
+}
+
+extern "C" int gdn_gather_samples(const void* pool, int32_t elem_bytes, const int32_t* idx, int32_t B, int64_t per_sample,
+                                  int32_t to_f32, void* dst, void* stream) {
+    (void)hipGetLastError();
+    if (!pool || !idx || !dst || B <= 0 || per_sample <= 0) return GDN_ERR_BAD_ARG;
+    if (elem_bytes != 1 && elem_bytes != 2) return GDN_ERR_BAD_ARG;
+    if (to_f32 && elem_bytes != 2) return GDN_ERR_BAD_ARG;
+    // 4 KiB (256 threads x 16 bytes) per block and pass; at most 64 blocks per sample
+    const int64_t chunks = cdiv64(per_sample * elem_bytes, 4096);
+    int bps = (int)(chunks < 64 ? chunks : 64);
+    if ((int64_t)B * bps > 0x7fffffffll) return GDN_ERR_BAD_ARG;
+    if (to_f32)
+        hipLaunchKernelGGL(gather_u16_f32_kernel, dim3(B * bps), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned short*)pool, (const int*)idx, (size_t)per_sample, bps, (float*)dst);
+    else
+        hipLaunchKernelGGL(gather_copy_kernel, dim3(B * bps), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)pool,
+                           (const int*)idx, (size_t)per_sample * elem_bytes, bps, (unsigned char*)dst);
     return gdn_launch_status();
 }

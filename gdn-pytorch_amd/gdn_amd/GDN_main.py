@@ -17,8 +17,10 @@ reference's sample contract ``(gt[B,1,H,W], rgb[B,3,H,W], sparse[B,1,H,W])`` in 
 Evaluation (--mode DtoD_test / RtoD_test, :234-307): ``--real_test`` evaluates KITTI on the Eigen test split
 (TestFolder) instead of val.txt; ``--dataset NYU`` evaluates the NYU Depth v2 test set with compute_errors_NYU;
 ``--img_save`` writes the output depth, ground truth and input colour of every test image as JPEG under --result_dir,
-from the validation pass itself.  NYU training: pass ``train_loader=datasets.GpuNYUAugmentLoader(...)`` (the NYU transform
-of :94-129 on the GPU) and a GpuCropLoader over the test set to run() with args.dataset == 'NYU'; the command line does
+from the validation pass itself.  ``--resident`` (KITTI file pipeline, training and ``--real_test``) decodes every file once
+and keeps the set in device memory (datasets.GpuResidentLoader); ``--resident_gb`` caps it.
+NYU training: pass ``train_loader=datasets.GpuNYUAugmentLoader(...)`` (the NYU transform of :94-129 on the GPU; or its
+device-resident form GpuNYUResidentLoader) and a GpuCropLoader over the test set to run() with args.dataset == 'NYU'; the command line does
 not build them.  Make3D training and evaluation are not implemented.
 """
 import os
@@ -42,8 +44,15 @@ def _make_optimizer(model, args):
 
 def _check_dataset(args):
     """What the file pipeline can read, checked before anything touches the GPU."""
+    resident = getattr(args, "resident", False)
+    if resident and args.synthetic:
+        raise RuntimeError("--resident keeps a set of FILES in device memory; it does not apply to --synthetic batches "
+                           "(drop one of the two flags)")
     if args.synthetic:
         return
+    if resident and args.dataset != "KITTI":
+        raise RuntimeError("--resident is implemented for the KITTI file pipeline only (the NYU resident loader, "
+                           "datasets.GpuNYUResidentLoader, is handed to run() like the NYU training loader)")
     if args.dataset == "Make3D":
         raise RuntimeError("--dataset Make3D is not supported: the reference's Make3D loader resizes with cv2.INTER_AREA "
                            "to 232x176, a size the U-Net cannot take (compute_errors_Make3D itself is available in "
@@ -98,8 +107,13 @@ def run(args, train_loader=None, val_loader=None):
         print('=> number of GPU processes: ', world)
         print("=> creating model")
     if train_loader is None:
-        from .datasets import GpuAugmentLoader, SequenceFolder, SyntheticRawKitti
+        from .datasets import GpuAugmentLoader, GpuResidentLoader, SequenceFolder, SyntheticRawKitti
         steps = args.epoch_size or 100
+        file_loader, budget = GpuAugmentLoader, {}
+        if getattr(args, "resident", False):
+            # --resident: every rank preloads the whole set (its shard of the common shuffle changes every epoch)
+            gb = getattr(args, "resident_gb", None)
+            file_loader, budget = GpuResidentLoader, {"max_bytes": None if gb is None else int(gb * 1e9)}
         if not args.synthetic and os.path.isdir(str(args.data)) and args.mode in TEST_MODES and \
                 (args.dataset == "NYU" or args.real_test):
             # evaluation only: the NYU test set (datasets_list.py:366-444) or the Eigen test split (:111-189); no train set
@@ -108,8 +122,8 @@ def run(args, train_loader=None, val_loader=None):
                 val_loader = GpuCropLoader(NYUdataset(args.data, args, seed=args.seed, train=False, mode=args.mode),
                                            args.batch_size, dev, H, W, workers=args.workers)
             else:
-                val_loader = GpuAugmentLoader(TestFolder(args.data, args, seed=args.seed, train=False, mode=args.mode),
-                                              args.batch_size, dev, train=False, workers=args.workers)
+                val_loader = file_loader(TestFolder(args.data, args, seed=args.seed, train=False, mode=args.mode),
+                                         args.batch_size, dev, train=False, workers=args.workers, **budget)
             train_loader = val_loader
             if rank == 0:
                 print("=> test on %s: %d samples" % ("the NYU Depth v2 test set" if args.dataset == "NYU"
@@ -126,10 +140,10 @@ def run(args, train_loader=None, val_loader=None):
                 val_set = SequenceFolder(args.data, args, seed=args.seed, train=False, mode=args.mode)
             # data parallelism: a common shuffle, rank r takes samples r, r + world, ... (each sample once per epoch);
             # --batch_size is per GPU, so the global batch is world * batch_size at the given learning rate
-            train_loader = GpuAugmentLoader(train_set, args.batch_size, dev, train=True, seed=args.seed + rank,
-                                            workers=args.workers, drop_last=True, rank=rank, world=world,
-                                            order_seed=args.seed + 1)
-            val_loader = GpuAugmentLoader(val_set, args.batch_size, dev, train=False, workers=args.workers)
+            train_loader = file_loader(train_set, args.batch_size, dev, train=True, seed=args.seed + rank,
+                                       workers=args.workers, drop_last=True, rank=rank, world=world,
+                                       order_seed=args.seed + 1, **budget)
+            val_loader = file_loader(val_set, args.batch_size, dev, train=False, workers=args.workers, **budget)
         elif not args.synthetic:
             raise RuntimeError("dataset directory %r not found; pass a KITTI root laid out like the reference's "
                                "(train.txt, val.txt, <scene>/*.jpg, color_gt2/, gt/) or --synthetic" % (args.data,))

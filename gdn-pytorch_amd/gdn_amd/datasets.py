@@ -15,10 +15,17 @@ CenterCrop + ArrayToTensor + Normalize runs batched in ``GpuCropLoader`` (gdn_cr
 NYU training (GDN_main.py:94-129, datasets_list.py:366-443): ``NYUdataset(train=True)`` reads the training split and
 ``GpuNYUAugmentLoader`` runs its random crop / spline rotation / imresize / flip / colour transform in gdn_nyu_augment;
 the host decodes the files and makes the reference's draws (``draw_params_nyu``).
+
+Device-resident sets (no reference counterpart): ``ResidentPools`` decodes every file ONCE and keeps the raw bytes in device
+memory; ``GpuResidentLoader`` / ``GpuNYUResidentLoader`` then assemble each batch on the device (gdn_kitti_augment_resident,
+gdn_gather_samples) from the sample indices and the same host draws, in the same order, as their parents: the host's work
+per batch is the draws and one small copy.
 """
 import concurrent.futures as cf
+import os
 import pathlib
 import random
+import time
 
 import numpy as np
 import torch
@@ -342,5 +349,227 @@ class GpuNYUAugmentLoader(GpuAugmentLoader):
             depth = self._to_device([np.ascontiguousarray(s[0][:, :, 0] if s[0].ndim == 3 else s[0], dtype=np.float32)
                                      for s in samples])
             rgb = self._to_device([s[1] for s in samples])
+            gt, img = ops.nyu_augment(depth, rgb, draws, H, W, self.mode)
+            yield gt, img, gt
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device-resident training sets
+
+STAGING_BYTES = 64 << 20       # the one pinned host buffer every upload of a preload goes through
+_FILE_KEYS = {SequenceFolder: ("gt", "rgb", "gt_np"), TestFolder: ("gt_color", "rgb", "gt"), NYUdataset: ("gt", "rgb", "gt")}
+
+
+def resident_bytes(n, shapes, itemsizes=None):
+    """Device bytes the pools of n samples hold: `shapes` are the array shapes of one sample, `itemsizes` their element
+    sizes in bytes (default 1 each: uint8).  KITTI at 128x416: resident_bytes(n, [(128, 416, 1), (128, 416, 3),
+    (128, 416, 1)]) = n * 266,240."""
+    shapes = [tuple(int(d) for d in sh) for sh in shapes]
+    itemsizes = [1] * len(shapes) if itemsizes is None else [int(i) for i in itemsizes]
+    if n < 0 or len(itemsizes) != len(shapes) or any(d <= 0 for sh in shapes for d in sh) or any(i <= 0 for i in itemsizes):
+        raise GdnError("resident_bytes: bad arguments n=%r shapes=%r itemsizes=%r" % (n, shapes, itemsizes))
+    return int(n) * sum(int(np.prod(sh, dtype=np.int64)) * i for sh, i in zip(shapes, itemsizes))
+
+
+def preload_threads(workers=0):
+    """Decode threads of a preload: the CPUs this process may run on, 16 at the most (never the machine's CPU count)."""
+    return max(1, min(workers or 16, 16, len(os.sched_getaffinity(0))))
+
+
+class ResidentPools:
+    """Every sample of an indexable dataset (SequenceFolder, TestFolder, SyntheticRawKitti: kind 'kitti'; NYUdataset: kind
+    'nyu'), decoded once by a thread pool and held in device memory as raw bytes:
+      kitti: tensors = (gt [N,H,W,Cg], rgb [N,H,W,Cr], sparse [N,H,W,Cs]) uint8 -- all images of one size, uint8, one channel
+             count per pool; a float / 16-bit source raises (the per-image bytescale is not carried);
+      nyu:   tensors = (depth [N,H0,W0] uint16, rgb [N,H0,W0,3] uint8) -- every depth value integral in [0, 65535].
+    A violation raises GdnError naming the first offending file.  resident_bytes() of the set is compared with max_bytes
+    (default: half of the device's free memory) BEFORE anything is allocated.  Uploads go through one pinned staging buffer
+    of at most STAGING_BYTES."""
+
+    def __init__(self, dataset, device, kind=None, workers=0, max_bytes=None):
+        t0 = time.time()
+        self.dev = torch.device(device)
+        self.kind = kind or ("nyu" if isinstance(dataset, NYUdataset) else "kitti")
+        if self.kind not in ("kitti", "nyu"):
+            raise GdnError("ResidentPools: kind must be 'kitti' or 'nyu', got %r" % (kind,))
+        self.n = len(dataset)
+        if self.n == 0:
+            raise GdnError("ResidentPools: the dataset is empty")
+        self._ds = dataset
+        first = self._arrays(0, dataset[0], None)
+        self.shapes = [a.shape for a in first]
+        self.itemsizes = [a.dtype.itemsize for a in first]
+        self.size = tuple(first[-1].shape[:2])
+        self.nbytes = resident_bytes(self.n, self.shapes, self.itemsizes)
+        cuda = self.dev.type == "cuda"
+        if max_bytes is None:
+            if not cuda:
+                raise GdnError("ResidentPools: max_bytes is required off the GPU")
+            max_bytes = torch.cuda.mem_get_info(self.dev)[0] // 2
+        if self.nbytes > max_bytes:
+            raise GdnError("resident set needs %.3f GB (%d samples x %d bytes) but the budget is %.3f GB; raise it "
+                           "(--resident_gb) or train without --resident" %
+                           (self.nbytes / 1e9, self.n, self.nbytes // self.n, max_bytes / 1e9))
+        sample_bytes = self.nbytes // self.n
+        if sample_bytes > STAGING_BYTES:
+            raise GdnError("ResidentPools: one sample (%d bytes) exceeds the staging buffer" % sample_bytes)
+        per = min(self.n, STAGING_BYTES // sample_bytes)          # samples per staged chunk
+        dtypes = [torch.uint8 if i == 1 else torch.uint16 for i in self.itemsizes]
+        self.tensors = tuple(torch.empty((self.n,) + sh, dtype=dt, device=self.dev) for sh, dt in zip(self.shapes, dtypes))
+        staging = torch.empty(per * sample_bytes, dtype=torch.uint8, pin_memory=cuda)
+        views, off = [], 0
+        for sh, i, dt in zip(self.shapes, self.itemsizes, dtypes):       # [per, ...] windows of the staging buffer, 2-byte pools first
+            nb = per * int(np.prod(sh)) * i
+            views.append(staging[off:off + nb].view(dt).view((per,) + sh))
+            off += nb
+        self.threads = preload_threads(workers)
+        with cf.ThreadPoolExecutor(self.threads) as ex:
+            for s in range(0, self.n, per):
+                m = min(per, self.n - s)
+                raw = list(ex.map(dataset.__getitem__, range(max(s, 1), s + m)))
+                chunk = ([first] if s == 0 else []) + [self._arrays(i, r, self.shapes) for i, r in
+                                                      zip(range(max(s, 1), s + m), raw)]
+                if cuda:
+                    torch.cuda.current_stream(self.dev).synchronize()     # the previous chunk has left the staging buffer
+                for j, v in enumerate(views):
+                    hv = v.numpy()
+                    for k, arrs in enumerate(chunk):
+                        hv[k] = arrs[j]
+                    self.tensors[j][s:s + m].copy_(v[:m], non_blocking=True)
+        if cuda:
+            torch.cuda.current_stream(self.dev).synchronize()
+        del self._ds
+        self.seconds = time.time() - t0
+        from . import distributed as D
+        if D.rank() == 0:
+            print("=> resident %s set: %d samples, %.3f GB on %s, preloaded in %.1f s by %d threads" %
+                  (self.kind, self.n, self.nbytes / 1e9, self.dev, self.seconds, self.threads))
+
+    def _name(self, i, j):
+        keys = _FILE_KEYS.get(type(self._ds))
+        samples = getattr(self._ds, "samples", None)
+        if keys and samples is not None:
+            return str(samples[i][keys[j]])
+        return "sample %d, image %d" % (i, j)
+
+    def _arrays(self, i, sample, shapes):
+        """The arrays of sample i as the pools store them, checked (against `shapes` once the first sample has set them)."""
+        if self.kind == "kitti":
+            out = []
+            for j, a in enumerate(sample):
+                if a.dtype != np.uint8:
+                    raise GdnError("%s: resident mode holds uint8 images only (this one decodes to %s: a float or 16-bit "
+                                   "source needs the per-image bytescale of the non-resident loader)" % (self._name(i, j), a.dtype))
+                if a.ndim != 3 or not 1 <= a.shape[2] <= 4:
+                    raise GdnError("%s: expected an HxWxC image with C <= 4, got shape %s" % (self._name(i, j), a.shape))
+                want = shapes[j] if shapes is not None else sample[1].shape[:2] + (a.shape[2],)
+                if a.shape != tuple(want):
+                    raise GdnError("%s: shape %s differs from the set's %s (all images of a resident set share one size "
+                                   "and one channel count per pool)" % (self._name(i, j), a.shape, tuple(want)))
+                out.append(a)
+            return out
+        d, c = sample[0], sample[1]
+        d = d[:, :, 0] if d.ndim == 3 and d.shape[2] == 1 else d
+        if d.ndim != 2 or not ((d >= 0).all() and (d <= 65535).all() and (d == np.floor(d)).all()):
+            raise GdnError("%s: NYU depth must be one channel of integral values in [0, 65535] (shape %s, %s)" %
+                           (self._name(i, 0), d.shape, d.dtype))
+        if c.ndim != 3 or c.shape[2] != 3 or c.dtype != np.uint8:
+            raise GdnError("%s: NYU colour images must be 8-bit RGB, got %s %s" % (self._name(i, 1), c.dtype, c.shape))
+        if c.shape[:2] != d.shape or (shapes is not None and (d.shape != tuple(shapes[0]) or c.shape != tuple(shapes[1]))):
+            raise GdnError("%s: size %s / %s differs from the set's (all images of a resident set share one size)" %
+                           (self._name(i, 0), d.shape, c.shape))
+        return [d.astype(np.uint16), c]
+
+
+class _UploadRing:
+    """A few pinned int32 host buffers used in turn for the small per-batch host-to-device copies: a slot is rewritten only
+    after the asynchronous copy that last read it has completed (its event), so the host never waits for the GPU's queue."""
+
+    def __init__(self, device, shape, slots=4):
+        self.dev = torch.device(device)
+        self.cuda = self.dev.type == "cuda"
+        self.bufs = [torch.empty(shape, dtype=torch.int32, pin_memory=self.cuda) for _ in range(slots)]
+        self.events = [None] * slots
+        self.k = 0
+
+    def upload(self, rows):
+        if not self.cuda:
+            return torch.from_numpy(np.array(rows, dtype=np.int32))
+        k, self.k = self.k, (self.k + 1) % len(self.bufs)
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        host = self.bufs[k][:rows.shape[0]]
+        host.copy_(torch.from_numpy(rows))
+        out = host.to(self.dev, non_blocking=True)
+        self.events[k] = torch.cuda.Event()
+        self.events[k].record(torch.cuda.current_stream(self.dev))
+        return out
+
+
+def _pools_for(dataset, device, kind, pools, workers, max_bytes):
+    if pools is None:
+        pools = ResidentPools(dataset, device, kind=kind, workers=workers, max_bytes=max_bytes)
+    if pools.kind != kind or pools.n != len(dataset):
+        raise GdnError("resident loader: the pools hold %d %s samples, the dataset has %d (%s expected)" %
+                       (pools.n, pools.kind, len(dataset), kind))
+    return pools
+
+
+class GpuResidentLoader(GpuAugmentLoader):
+    """GpuAugmentLoader over a device-resident set: the same order, sharding, drop_last, draws (draw_params, in the same
+    order) and last_params, and bit-identical batches, but the dataset is decoded once, at construction (ResidentPools,
+    or `pools` built before), and never indexed again.  Per batch the host builds the int32 rows {sample index, five
+    draws}, copies them to the device once and gdn_kitti_augment_resident makes the three tensors in one launch.
+    `workers` sizes the preload's thread pool; `max_bytes` is its budget."""
+
+    def __init__(self, dataset, batch_size, device, train=True, seed=None, shuffle=None, workers=0, drop_last=False,
+                 rank=0, world=1, order_seed=None, pools=None, max_bytes=None):
+        super().__init__(dataset, batch_size, device, train=train, seed=seed, shuffle=shuffle, workers=0,
+                         drop_last=drop_last, rank=rank, world=world, order_seed=order_seed)
+        self.pools = _pools_for(dataset, self.dev, "kitti", pools, workers, max_bytes)
+        self._ring = _UploadRing(self.dev, (self.bs, 6))
+
+    def __iter__(self):
+        H, W = self.pools.size
+        order = self._epoch_order()
+        for b in range(len(self)):
+            idxs = order[b * self.bs:(b + 1) * self.bs]
+            rows = np.empty((len(idxs), 6), np.int32)
+            rows[:, 0] = idxs
+            rows[:, 1:] = (0, H, W, 0, 0)
+            if self.train:
+                host = [draw_params(H, W, self.py_rng, self.np_rng) for _ in idxs]
+                self.last_params = host
+                rows[:, 1:] = host
+            sel = self._ring.upload(ops.check_sel(rows, self.pools.n, H, W, self.train))
+            yield ops.kitti_augment_resident(self.pools.tensors, sel, self.train)
+
+
+class GpuNYUResidentLoader(GpuNYUAugmentLoader):
+    """GpuNYUAugmentLoader over a device-resident set (uint16 depth pool, uint8 colour pool): gdn_gather_samples copies the
+    batch's samples out of the pools, widening the depth to float32 as decoding does, and feeds the parent's
+    gdn_nyu_augment with the parent's draws (draw_params_nyu, same order).  Bit-identical batches; the dataset is never
+    indexed after construction."""
+
+    def __init__(self, dataset, batch_size, device, height, width, mode="DtoD", seed=None, workers=0, drop_last=False,
+                 rank=0, world=1, order_seed=None, pools=None, max_bytes=None):
+        super().__init__(dataset, batch_size, device, height, width, mode=mode, seed=seed, workers=0, drop_last=drop_last,
+                         rank=rank, world=world, order_seed=order_seed)
+        self.pools = _pools_for(dataset, self.dev, "nyu", pools, workers, max_bytes)
+        self._ring = _UploadRing(self.dev, (self.bs,))
+
+    def __iter__(self):
+        H, W = self.size
+        H0, W0 = self.pools.size
+        order = self._epoch_order()
+        for b in range(len(self)):
+            idxs = np.asarray(order[b * self.bs:(b + 1) * self.bs], dtype=np.int32)
+            if idxs.min() < 0 or idxs.max() >= self.pools.n:
+                raise GdnError("sample index outside the %d resident samples" % self.pools.n)
+            draws = [draw_params_nyu(H0, W0, self.mode, self.py_rng, self.np_rng) for _ in idxs]
+            self.last_params = draws
+            idx = self._ring.upload(idxs)
+            depth = ops.gather_samples(self.pools.tensors[0], idx, to_f32=True)
+            rgb = ops.gather_samples(self.pools.tensors[1], idx)
             gt, img = ops.nyu_augment(depth, rgb, draws, H, W, self.mode)
             yield gt, img, gt

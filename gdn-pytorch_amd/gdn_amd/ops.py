@@ -1008,6 +1008,81 @@ def kitti_augment(src, params, train=True):
     return dst
 
 
+def check_sel(rows, n, H, W, train=True):
+    """Host-side check of batch-assembly rows before they are uploaded (the device does not check): `rows` is an integer
+    [B,6] array {sample index, flip, scaled_h, scaled_w, off_y, off_x}; every index must address one of the n resident
+    samples and, for training, the draws must describe a crop window inside the scaled image.  Returns int32 rows."""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    if rows.ndim != 2 or rows.shape[1] != 6 or rows.shape[0] == 0:
+        raise GdnError("check_sel: rows must be a non-empty [B,6] integer array, got shape %s" % (rows.shape,))
+    idx = rows[:, 0]
+    if int(idx.min()) < 0 or int(idx.max()) >= n:
+        raise GdnError("check_sel: sample index %d is outside the %d resident samples" %
+                       (int(idx.min()) if idx.min() < 0 else int(idx.max()), n))
+    if train:
+        flip, sh, sw, oy, ox = (rows[:, k] for k in range(1, 6))
+        ok = ((flip == 0) | (flip == 1)) & (sh >= H) & (sw >= W) & (oy >= 0) & (oy <= sh - H) & (ox >= 0) & (ox <= sw - W)
+        if not ok.all():
+            b = int(np.argmin(ok))
+            raise GdnError("check_sel: row %d %s is not a flip / scale-up / crop of a %dx%d image" % (b, rows[b, 1:].tolist(), H, W))
+    return rows
+
+
+def kitti_augment_resident(pools, sel, train=True):
+    """Assemble a batch from device-resident pools in one launch: pools = (gt, rgb, sparse), dense uint8 [N,H,W,C] device
+    tensors of one N, H, W; sel = int32 [B,6] {sample index, flip, scaled_h, scaled_w, off_y, off_x} -- a device tensor
+    whose rows the caller has passed through check_sel, or a host array / CPU tensor, checked and copied here.
+    Returns the three normalised NCHW float32 tensors (bit-identical to kitti_augment on the gathered samples)."""
+    if len(pools) != 3 or any(not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 4 or
+                              not p.is_contiguous() or not 1 <= p.shape[3] <= 4 for p in pools):
+        raise GdnError("kitti_augment_resident: pools must be three dense [N,H,W,C<=4] uint8 tensors on the GPU")
+    N, H, W = pools[0].shape[:3]
+    if N == 0 or any(tuple(p.shape[:3]) != (N, H, W) or p.device != pools[0].device for p in pools):
+        raise GdnError("kitti_augment_resident: the pools must hold the same samples at one size on one device, got %s" %
+                       ([tuple(p.shape) for p in pools],))
+    dev = pools[0].device
+    if not (isinstance(sel, torch.Tensor) and sel.is_cuda):
+        host = check_sel(sel.numpy() if isinstance(sel, torch.Tensor) else sel, N, H, W, train)
+        sel = torch.from_numpy(host).to(dev)
+    if sel.dtype != torch.int32 or sel.dim() != 2 or sel.shape[1] != 6 or sel.shape[0] == 0 or not sel.is_contiguous() or \
+            sel.device != dev:
+        raise GdnError("kitti_augment_resident: sel must be a dense int32 [B,6] tensor on the pools' device")
+    B = sel.shape[0]
+    outs = tuple(torch.empty((B, p.shape[3], H, W), dtype=torch.float32, device=dev) for p in pools)
+    lib.gdn_kitti_augment_resident(_p(pools[0]), pools[0].shape[3], _p(pools[1]), pools[1].shape[3], _p(pools[2]),
+                                   pools[2].shape[3], H, W, _p(sel), B, 1 if train else 0, _p(outs[0]), _p(outs[1]),
+                                   _p(outs[2]), stream())
+    return outs
+
+
+def gather_samples(pool, idx, to_f32=False):
+    """pool[idx] for a dense uint8 / uint16 device pool [N, ...]: idx is an int32 [B] device tensor the caller has
+    range-checked, or a host array / CPU tensor / list, checked and copied here.  to_f32 (uint16 pools): the result is
+    float32, every value widened exactly.  Returns [B, ...]."""
+    if not isinstance(pool, torch.Tensor) or not pool.is_cuda or pool.dtype not in (torch.uint8, torch.uint16) or \
+            pool.dim() < 1 or not pool.is_contiguous() or pool.shape[0] == 0:
+        raise GdnError("gather_samples: pool must be a dense uint8/uint16 [N,...] tensor on the GPU")
+    if to_f32 and pool.dtype != torch.uint16:
+        raise GdnError("gather_samples: to_f32 widens uint16 pools only, got %s" % (pool.dtype,))
+    N = pool.shape[0]
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda):
+        host = np.ascontiguousarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx)
+        if host.ndim != 1 or host.size == 0 or host.dtype.kind not in "iu":
+            raise GdnError("gather_samples: idx must be a non-empty 1-D integer array")
+        if int(host.min()) < 0 or int(host.max()) >= N:
+            raise GdnError("gather_samples: index outside the %d resident samples" % N)
+        idx = torch.from_numpy(host.astype(np.int32)).to(pool.device)
+    if idx.dtype != torch.int32 or idx.dim() != 1 or idx.numel() == 0 or not idx.is_contiguous() or idx.device != pool.device:
+        raise GdnError("gather_samples: idx must be a dense int32 [B] tensor on the pool's device")
+    B = idx.numel()
+    per_sample = pool[0].numel()
+    if per_sample == 0:
+        raise GdnError("gather_samples: empty samples")
+    dst = torch.empty((B,) + tuple(pool.shape[1:]), dtype=torch.float32 if to_f32 else pool.dtype, device=pool.device)
+    lib.gdn_gather_samples(_p(pool), pool.element_size(), _p(idx), B, per_sample, 1 if to_f32 else 0, _p(dst), stream())
+    return dst
+
+
 NYU_CROP = (251, 340)          # RandomCropNumpy's window (GDN_main.py:99, :110)
 
 # gdn_nyu_aug_params (include/gdn_hip.h)

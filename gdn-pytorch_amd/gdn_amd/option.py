@@ -1,5 +1,5 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
-plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu).
+plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -55,6 +55,12 @@ def build_parser():
                         'batched encoder-only pass, identical features)')
     p.add_argument('--global_berhu', action='store_true',
                    help='all-reduce(MAX) the BerHu threshold like DataParallel\'s gathered batch (SURVEY 8(e))')
+    p.add_argument('--resident', action='store_true',
+                   help='KITTI file pipeline: decode every file once, keep the raw images in device memory and assemble each '
+                        'batch there (one kernel launch and one small copy per batch instead of decoding 3 x batch_size files)')
+    p.add_argument('--resident_gb', type=float, default=None, metavar='GB',
+                   help='with --resident: the most device memory (GB, 1e9 bytes) one preloaded set may take '
+                        '(default: half of the free memory)')
     return p
 
 

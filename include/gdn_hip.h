@@ -579,6 +579,29 @@ int gdn_kitti_augment(const void* src, int32_t src_is_f32, int32_t B, int32_t H,
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Batch assembly from a device-resident training set (no reference counterpart: the reference decodes every file of
+ * every batch on the host).  The decoded uint8 images of ALL samples stay in three device pools; one launch picks the
+ * batch's samples by index and applies gdn_kitti_augment's transform (the same device code: bit-identical results) to
+ * the three images of each, computing a pixel's filter coefficients once for all their channels.
+ *   gt_pool [N][H][W][Cg], rgb_pool [N][H][W][Cr], sparse_pool [N][H][W][Cs]  uint8, each C <= 4
+ *   sel     device int32 [B][6] = {sample index, flip, scaled_h, scaled_w, off_y, off_x}; when train == 0 only the
+ *           index is read.  0 <= index < N is the CALLER's check, made on the host before the rows are uploaded.
+ *   gt_out [B][Cg][H][W], rgb_out [B][Cr][H][W], sparse_out [B][Cs][H][W]  float32 = (v/255 - 0.5)/0.5
+ * Offsets into the pools are 64-bit.
+ * ---------------------------------------------------------------------- */
+int gdn_kitti_augment_resident(const uint8_t* gt_pool, int32_t Cg, const uint8_t* rgb_pool, int32_t Cr,
+                               const uint8_t* sparse_pool, int32_t Cs, int32_t H, int32_t W, const int32_t* sel,
+                               int32_t B, int32_t train, float* gt_out, float* rgb_out, float* sparse_out,
+                               void* stream);
+
+/* Indexed copy of whole samples: dst[b] = pool[idx[b]], b < B, samples of per_sample elements of elem_bytes (1 or 2)
+ * bytes; idx is a device int32 [B] the caller has range-checked.  to_f32 (elem_bytes 2 only): dst is float32 and every
+ * uint16 is widened on the way (exact) -- what decoding a 16-bit PNG to float32 gives.  16-byte accesses where a
+ * sample's source and destination are both 16-byte aligned, element-wise for the tail and otherwise; 64-bit offsets. */
+int gdn_gather_samples(const void* pool, int32_t elem_bytes, const int32_t* idx, int32_t B, int64_t per_sample,
+                       int32_t to_f32, void* dst, void* stream);
+
+/* ------------------------------------------------------------------------
  * NYU Depth v2 training-time augmentation on the device (GDN_main.py:94-129, datasets_list.py:399-430), bit-exact with
  * the host pipeline: imresize (bytescale + Pillow BILINEAR, or Pillow 'F' for depth) to img_s x (251, 340), depth /
  * scale, RandomCropNumpy(251, 340), RandomRotate (scipy.ndimage.rotate, order 3, mode 'constant', reshape=False, clipped
