@@ -246,6 +246,8 @@ struct FftGeom {
     int k, pad, T, tiles_y, tiles_x, M;      // M = B * tiles_y * tiles_x
     int reflect;                             // input border: 0 zeros, 1 reflection (ReflectionPad2d(pad) + conv)
     int flip;                                // stride-1 ConvTranspose2d: correlation with the flipped taps
+    int fwd_only;                            // ... given as a transposed = 1 geometry: forward (inference) only; the same layer
+                                             // given as the convolution it is (GDN_HINT_FLIP_TAPS) has the full backward
 };
 
 // weights: DFT of the k*k taps at every kept bin.  With Wc = conj(DFT(w[n][c])) (correlation) the three real planes of
@@ -650,12 +652,16 @@ __global__ __launch_bounds__(256) void fft_wgrad_taps_kernel(const float* __rest
 }
 
 // dw[tap][n][c] = scale * (part[0] + part[1] + ... + part[G-1]) (fixed order); n4 = K*K*N*C / 4
+// taps > 0 (a flipped-tap layer, GDN_HINT_FLIP_TAPS): the sums are the gradient of the taps the kernels correlated with, the
+// stored ones in reverse order -- tap t is written to slot taps - 1 - t of the module's [tap][n][c] gradient (bs4 = N*C / 4)
 __global__ __launch_bounds__(256) void fft_taps_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int64_t n4, int G,
-                                                              float scale) {
+                                                              float scale, int taps, int64_t bs4) {
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4 v = reinterpret_cast<const f32x4*>(part)[i];
         for (int g = 1; g < G; ++g) v += reinterpret_cast<const f32x4*>(part)[(int64_t)g * n4 + i];
-        reinterpret_cast<f32x4*>(dw)[i] = v * scale;
+        int64_t o = i;
+        if (taps) { const int64_t t = i / bs4; o = (taps - 1 - t) * bs4 + (i - t * bs4); }
+        reinterpret_cast<f32x4*>(dw)[o] = v * scale;
     }
 }
 
@@ -1188,6 +1194,7 @@ __global__ __launch_bounds__(256) void fft_overlap_gather_kernel(const float* __
 bool fft_geom(const gdn_conv_geom* g, FftGeom& f) {
     if (!g || g->stride != 1 || g->k < 3 || g->k > 9 || (g->k & 1) == 0) return false;
     if (g->pad != g->k / 2 || (g->transposed && g->pad_mode != 0)) return false;
+    if ((g->hints & GDN_HINT_FLIP_TAPS) && (g->transposed || g->pad_mode != 0)) return false;
     if (g->pad_mode == 1 && (g->pad >= g->H || g->pad >= g->W)) return false;
     if ((g->Cin % 64) || (g->Cout % 64) || g->Cin > 256 || g->Cout > 256) return false;
     f.B = g->B; f.H = g->H; f.W = g->W; f.C = g->Cin; f.N = g->Cout; f.k = g->k; f.pad = g->pad;
@@ -1216,7 +1223,8 @@ bool fft_geom(const gdn_conv_geom* g, FftGeom& f) {
     f.tiles_y = cdiv(g->H, f.T); f.tiles_x = cdiv(g->W, f.T);
     f.M = g->B * f.tiles_y * f.tiles_x;
     f.reflect = g->pad_mode == 1;
-    f.flip = g->transposed ? 1 : 0;
+    f.flip = (g->transposed || (g->hints & GDN_HINT_FLIP_TAPS)) ? 1 : 0;
+    f.fwd_only = g->transposed ? 1 : 0;
     return true;
 }
 
@@ -1354,7 +1362,7 @@ extern "C" int gdn_fftconv_fwd(const gdn_conv_geom* g, const float* x, int32_t l
 extern "C" size_t gdn_fftconv_bwd_workspace_bytes(const gdn_conv_geom* g) {
     FftGeom f;
     if (!fft_geom(g, f)) return 0;
-    if (f.flip) return 0;                  // stride-1 ConvTranspose2d: forward (inference) only
+    if (f.fwd_only) return 0;              // a transposed = 1 geometry: forward (inference) only
     if (f.C != 64 && f.C != 128 && f.C != 256) return 0;   // the inverse kernels of the data gradient index channels by shifts: a
                                                            // caller asking "is the backward supported" (ops.fft_ok) takes another path
     const size_t cm = f.C > f.N ? f.C : f.N;
@@ -1372,7 +1380,7 @@ static int fft_gather_blocks(const FftGeom& f) {
 }
 extern "C" int64_t gdn_fftconv_bnb_slots(const gdn_conv_geom* g) {
     FftGeom f;
-    if (!fft_geom(g, f) || f.flip) return 0;
+    if (!fft_geom(g, f) || f.fwd_only) return 0;
     if (f.C != 64 && f.C != 128 && f.C != 256) return 0;
     return fft_gather_blocks(f);
 }
@@ -1386,7 +1394,7 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
                                size_t workspace_bytes, void* stream) {
     (void)hipGetLastError();
     FftGeom f;
-    if (!fft_geom(g, f) || f.flip) return GDN_ERR_UNSUPPORTED;
+    if (!fft_geom(g, f) || f.fwd_only) return GDN_ERR_UNSUPPORTED;
     if (dyb_y && (!dyb_co || !dyb_kk)) return GDN_ERR_BAD_ARG;
     if (bnb_y && (!dx || !bnb_co || !bnb_partial || (ld_bnb % 4))) return GDN_ERR_BAD_ARG;
     if (bnb_y && (fft_gather_blocks(f) == 0 || (ldx % 4) || (addsrc && (ld_add % 4)))) return GDN_ERR_UNSUPPORTED;
@@ -1434,7 +1442,7 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
         }
         const int64_t n4 = (int64_t)f.k * f.k * f.N * f.C / 4;
         hipLaunchKernelGGL(fft_taps_reduce_kernel, dim3(blocks(n4)), dim3(256), 0, st, (const float*)part, dw, n4, taps_groups(f),
-                           1.0f / (f.np * f.np));
+                           1.0f / (f.np * f.np), f.flip ? f.k * f.k : 0, (int64_t)f.N * f.C / 4);
 #undef GDN_TAPS
     }
     if (dx && (phases & GDN_FFT_BWD_DX)) {

@@ -1453,6 +1453,7 @@ extern "C" int gdn_conv_fwd(const gdn_conv_geom* g, const void* xv, int32_t ldx,
     const bool bf = (tile_cfg & CFG_BF16) != 0;
     const uint64_t es = bf ? 2 : 4;
     if (!geom_ok(g) || !x || !w || !y) return GDN_ERR_BAD_ARG;
+    if (g && (g->hints & GDN_HINT_FLIP_TAPS)) return GDN_ERR_UNSUPPORTED;   // transform-domain form only: the direct kernels take the layer as transposed = 1
     if ((ep_scale == nullptr) != (ep_shift == nullptr)) return GDN_ERR_BAD_ARG;
     if (g->Cout == 1 && !x2 && !stats && !addsrc && !ep_scale && !(act & GDN_ACT_RELU) && (tile_cfg & ~CFG_BF16) == 0) {
         // 1-channel heads: with GDN_CFG_BF16 only x is bf16 -- weights and the depth map stay fp32
@@ -1563,6 +1564,7 @@ extern "C" int gdn_conv_dgrad(const gdn_conv_geom* g, const void* dyv, int32_t l
     const bool bf = (tile_cfg & CFG_BF16) != 0;
     const uint64_t es = bf ? 2 : 4;
     if (!dy || !wt || !dx) return GDN_ERR_BAD_ARG;
+    if (g && (g->hints & GDN_HINT_FLIP_TAPS)) return GDN_ERR_UNSUPPORTED;   // transform-domain form only, as in gdn_conv_fwd
     hipStream_t st = (hipStream_t)stream;
     IgemmParams P{};
     bool fold, scalar;

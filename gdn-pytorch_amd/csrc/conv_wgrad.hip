@@ -504,6 +504,7 @@ extern "C" int gdn_conv_wgrad(const gdn_conv_geom* g, const void* xv, int32_t ld
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     const float *x = (const float*)xv, *dy = (const float*)dyv;
     if (!x || !dy || !dw) return GDN_ERR_BAD_ARG;
+    if (g && (g->hints & GDN_HINT_FLIP_TAPS)) return GDN_ERR_UNSUPPORTED;   // transform-domain form only: the direct kernels take the layer as transposed = 1
     WgradPlan pl;
     if (!make_plan(g, Cx, pl)) return GDN_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < pl.ws_bytes) return GDN_ERR_WORKSPACE;

@@ -468,6 +468,7 @@ extern "C" int gdn_conv_wgrad_bf16(const gdn_conv_geom* g, const void* x, int32_
                                    size_t workspace_bytes, int32_t cfg, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!x || !dy || !dw) return GDN_ERR_BAD_ARG;
+    if (g && (g->hints & GDN_HINT_FLIP_TAPS)) return GDN_ERR_UNSUPPORTED;   // transform-domain form only: the direct kernels take the layer as transposed = 1
     hipStream_t st = (hipStream_t)stream;
     PlanRing pr;
     if (((cfg & 7) == 0 || (cfg & 7) == 4) && make_plan_ring(g, Cx, (cfg & 7) == 4, pr)) {

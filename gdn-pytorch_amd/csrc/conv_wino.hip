@@ -29,6 +29,7 @@ struct WinoGeom {
     int tiles_y, tiles_x, M;      // 2x2 output tiles; M = B * tiles_y * tiles_x
     int cq_shift, nq_shift;       // log2(C / 64), log2(N / 64)
     int x3;                       // per-bin GEMMs as bf16 x 3 split products (gemm_x3.h) unless the caller set GDN_HINT_NO_X3
+    int flip;                     // 0, or WINO_FLIP: a stride-1 ConvTranspose2d given as the convolution it is (GDN_HINT_FLIP_TAPS)
     int T, bins;                  // outputs per tile side and transform bins: F(2x2,3x3) T = 2, 16 bins; F(4x4,3x3) T = 4, 36 bins
 };
 
@@ -130,6 +131,8 @@ __global__ __launch_bounds__(256) void wino_dy_kernel(const float* __restrict__ 
     }
 }
 
+constexpr int WINO_FLIP = 2;      // bit 1 of the weight kernels' `swap` arguments: a flipped-tap layer (GDN_HINT_FLIP_TAPS)
+
 // U = G g G^T.  swap = 0: U[bin][n][c] from w[tap][n][c] (forward);  swap = 1: U[bin][c][n] from the flipped taps
 // (data gradient: correlation of dy with w[n][c][2 - ty][2 - tx], output channel c)
 // Uswap != NULL (forward of a layer that will run backward): the data gradient's set (taps flipped: bins permuted
@@ -140,12 +143,14 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* __restri
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N * C) return;
     const int c = i % C, n = i / C;
+    const int rev = (swap & 1) ^ (swap >> 1);       // WINO_FLIP: the layer correlates with the stored taps in reverse order
+    swap &= 1;
     float gk[3][3];
 #pragma unroll
     for (int ty = 0; ty < 3; ++ty)
 #pragma unroll
         for (int tx = 0; tx < 3; ++tx) {
-            const int tap = swap ? (2 - ty) * 3 + (2 - tx) : ty * 3 + tx;
+            const int tap = rev ? (2 - ty) * 3 + (2 - tx) : ty * 3 + tx;
             gk[ty][tx] = w[((size_t)tap * N + n) * C + c];
         }
     float r[4][3];
@@ -192,7 +197,8 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* __restri
 __global__ __launch_bounds__(256) void wino_weights_x3_kernel(const float* __restrict__ w, unsigned char* __restrict__ Up0, int N, int C,
                                                               int swap0, unsigned char* __restrict__ Up1, int swap1) {
     unsigned char* __restrict__ Up = blockIdx.y ? Up1 : Up0;
-    const int swap = blockIdx.y ? swap1 : swap0;
+    const int swapf = blockIdx.y ? swap1 : swap0;
+    const int swap = swapf & 1, rev = swap ^ (swapf >> 1);       // WINO_FLIP, as in wino_weights_kernel
     const int rows = swap ? C : N, K = swap ? N : C, k8n = K / 8;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= rows * k8n) return;
@@ -204,7 +210,7 @@ __global__ __launch_bounds__(256) void wino_weights_x3_kernel(const float* __res
     for (int ty = 0; ty < 3; ++ty)
 #pragma unroll
         for (int tx = 0; tx < 3; ++tx) {
-            const int tap = swap ? (2 - ty) * 3 + (2 - tx) : ty * 3 + tx;
+            const int tap = rev ? (2 - ty) * 3 + (2 - tx) : ty * 3 + tx;
             if (swap) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) gk[e][ty][tx] = w[((size_t)tap * N + k8 * 8 + e) * C + row];
@@ -314,8 +320,9 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
 }
 
 // dW[tap][n][c] = (G^T P G)[ty][tx]
+// flip (a flipped-tap layer): tap t is the gradient of stored tap 8 - t
 __global__ __launch_bounds__(256) void wino_wgrad_output_kernel(const float* __restrict__ P, float* __restrict__ dw, int N, int C,
-                                                                int nsplit) {
+                                                                int nsplit, int flip) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N * C) return;
     float p[4][4];
@@ -338,9 +345,10 @@ __global__ __launch_bounds__(256) void wino_wgrad_output_kernel(const float* __r
     }
 #pragma unroll
     for (int ty = 0; ty < 3; ++ty) {
-        dw[(size_t)(ty * 3 + 0) * bs + i] = r[ty][0] + 0.5f * (r[ty][1] + r[ty][2]);
-        dw[(size_t)(ty * 3 + 1) * bs + i] = 0.5f * (r[ty][1] - r[ty][2]);
-        dw[(size_t)(ty * 3 + 2) * bs + i] = 0.5f * (r[ty][1] + r[ty][2]) + r[ty][3];
+        const int t0 = ty * 3;
+        dw[(size_t)(flip ? 8 - t0 : t0) * bs + i] = r[ty][0] + 0.5f * (r[ty][1] + r[ty][2]);
+        dw[(size_t)(flip ? 7 - t0 : t0 + 1) * bs + i] = 0.5f * (r[ty][1] - r[ty][2]);
+        dw[(size_t)(flip ? 6 - t0 : t0 + 2) * bs + i] = 0.5f * (r[ty][1] + r[ty][2]) + r[ty][3];
     }
 }
 
@@ -493,7 +501,8 @@ __global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void wino4_weights_x3_kernel(const float* __restrict__ w, unsigned char* __restrict__ Up0, int N, int C,
                                                                int swap0, unsigned char* __restrict__ Up1, int swap1) {
     unsigned char* __restrict__ Up = blockIdx.y ? Up1 : Up0;
-    const int swap = blockIdx.y ? swap1 : swap0;
+    const int swapf = blockIdx.y ? swap1 : swap0;
+    const int swap = swapf & 1, rev = swap ^ (swapf >> 1);       // WINO_FLIP, as in wino_weights_kernel
     const int rows = swap ? C : N, K = swap ? N : C, k8n = K / 8;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= rows * k8n) return;
@@ -506,7 +515,7 @@ __global__ __launch_bounds__(256) void wino4_weights_x3_kernel(const float* __re
         float gk[8][3];
 #pragma unroll
         for (int ty = 0; ty < 3; ++ty) {
-            const int tap = swap ? (2 - ty) * 3 + (2 - tx) : ty * 3 + tx;
+            const int tap = rev ? (2 - ty) * 3 + (2 - tx) : ty * 3 + tx;
             if (swap) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) gk[e][ty] = w[((size_t)tap * N + k8 * 8 + e) * C + row];
@@ -625,7 +634,7 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
 
 // dW[tap][n][c] = (A_w^T P A_w)[ty][tx], the split partial products summed in order
 __global__ __launch_bounds__(256) void wino4_wgrad_output_kernel(const float* __restrict__ P, float* __restrict__ dw, int N, int C,
-                                                                 int nsplit) {
+                                                                 int nsplit, int flip) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N * C) return;
     const float* src = P + i;
@@ -655,12 +664,14 @@ __global__ __launch_bounds__(256) void wino4_wgrad_output_kernel(const float* __
         float o[3];
         w4_awt(r[ty], o);
 #pragma unroll
-        for (int tx = 0; tx < 3; ++tx) dw[(size_t)(ty * 3 + tx) * bs + i] = o[tx];
+        for (int tx = 0; tx < 3; ++tx) dw[(size_t)(flip ? 8 - (ty * 3 + tx) : ty * 3 + tx) * bs + i] = o[tx];
     }
 }
 
 bool wino_geom(const gdn_conv_geom* g, WinoGeom& f) {
     if (!g || g->transposed || g->stride != 1 || g->k != 3 || g->pad != 1) return false;
+    if ((g->hints & GDN_HINT_FLIP_TAPS) && g->pad_mode != 0) return false;
+    f.flip = (g->hints & GDN_HINT_FLIP_TAPS) ? WINO_FLIP : 0;
     if (g->pad_mode == 1 && (g->H < 4 || g->W < 4)) return false;        // mirrored rows 1 and H-2 must be distinct interior rows
     if ((g->Cin % 64) || (g->Cout % 64) || g->Cin > 512 || g->Cout > 512) return false;
     auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
@@ -753,7 +764,7 @@ extern "C" int gdn_winoconv_fwd(const gdn_conv_geom* g, const float* x, int32_t 
         hipLaunchKernelGGL(wino4_input_kernel, dim3(cdiv(f.M, 4) << f.cq_shift), dim3(256), 0, st, x, ldx, V, f, in_scale, in_shift,
                            in_relu, in_up2x);
         hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256), Usw ? 2 : 1), dim3(256), 0, st, w, (unsigned char*)U, f.N,
-                           f.C, 0, (unsigned char*)Usw, 1);
+                           f.C, f.flip, (unsigned char*)Usw, 1 | f.flip);
         launch_gemm_x3_nt((const float*)V, U, Mo, f.bins, f.M, f.N, f.C, st);
         hipLaunchKernelGGL(wino4_output_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, (const float*)Mo, y, ldy, addsrc,
                            ld_add, stats, ep_scale, ep_shift, act, f, f.N, f.nq_shift, (const float*)nullptr, 0,
@@ -767,15 +778,15 @@ extern "C" int gdn_winoconv_fwd(const gdn_conv_geom* g, const float* x, int32_t 
     const bool x3f = f.x3 && gemm_x3_ok(f.M, f.N, f.C), x3d = f.x3 && gemm_x3_ok(f.M, f.C, f.N);
     if (!x3f || (Usw && !x3d))
         hipLaunchKernelGGL(wino_weights_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, w, x3f ? (float*)nullptr : U, f.N,
-                           f.C, 0, x3d ? (float*)nullptr : Usw);
+                           f.C, f.flip, x3d ? (float*)nullptr : Usw);
     if (x3f && Usw && x3d)
-        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256), 2), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 0,
-                           (unsigned char*)Usw, 1);
+        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256), 2), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, f.flip,
+                           (unsigned char*)Usw, 1 | f.flip);
     else if (x3f)
-        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 0,
+        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, f.flip,
                            (unsigned char*)nullptr, 0);
     else if (Usw && x3d)
-        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)Usw, f.N, f.C, 1,
+        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)Usw, f.N, f.C, 1 | f.flip,
                            (unsigned char*)nullptr, 0);
     if (x3f) launch_gemm_x3_nt((const float*)V, U, Mo, WINO_BINS, f.M, f.N, f.C, st);
     else launch_wino_gemm((const float*)V, (const float*)U, Mo, f.M, f.N, f.C, st);
@@ -830,7 +841,7 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
             hipLaunchKernelGGL(wino4_dy_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, dy, ldy, Vd, f);
             const int ns = tn_splits(f);
             launch_gemm_x3_tn((const float*)Vd, (const float*)state, Eo, f.bins, f.M, f.N, f.C, ns, st);
-            hipLaunchKernelGGL(wino4_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)Eo, dw, f.N, f.C, ns);
+            hipLaunchKernelGGL(wino4_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)Eo, dw, f.N, f.C, ns, f.flip ? 1 : 0);
         }
         if (dx) {
             WinoGeom fd = f;
@@ -839,7 +850,7 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
                                (const float*)nullptr, (const float*)nullptr, 0, 0);
             const float* Ud = U;
             if (state) Ud = (const float*)((const char*)state + v_bytes(f));      // transformed by the forward's launch
-            else hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1,
+            else hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1 | f.flip,
                                     (unsigned char*)nullptr, 0);
             launch_gemm_x3_nt((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, st);
             hipLaunchKernelGGL(wino4_output_kernel, dim3(cdiv(fd.M, 4) << fd.nq_shift), dim3(256), 0, st, (const float*)Eo, dx, ldx,
@@ -853,7 +864,7 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
         const int ns = tn_splits(f);
         if (tn_x3(f)) launch_gemm_x3_tn((const float*)Vd, (const float*)state, Eo, WINO_BINS, f.M, f.N, f.C, ns, st);
         else launch_wino_gemm_tn((const float*)Vd, (const float*)state, Eo, f.M, f.N, f.C, ns, st);
-        hipLaunchKernelGGL(wino_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)Eo, dw, f.N, f.C, ns);
+        hipLaunchKernelGGL(wino_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)Eo, dw, f.N, f.C, ns, f.flip ? 1 : 0);
     }
     if (dx) {
         // the data gradient of a 3x3 layer is the same kind of convolution of dy with flipped, role-swapped taps: pad 1 onto
@@ -876,9 +887,9 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
         // reflection layer has more tiles but the same N and K, so eligibility is the same)
         const bool x3d = f.x3 && gemm_x3_ok(f.M, f.C, f.N);
         if (state) Ud = (const float*)((const char*)state + v_bytes(f));      // transformed by the forward's launch
-        else if (x3d) hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1,
+        else if (x3d) hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1 | f.flip,
                                          (unsigned char*)nullptr, 0);
-        else hipLaunchKernelGGL(wino_weights_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, w, U, f.N, f.C, 1, (float*)nullptr);
+        else hipLaunchKernelGGL(wino_weights_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, w, U, f.N, f.C, 1 | f.flip, (float*)nullptr);
         if (x3d) launch_gemm_x3_nt((const float*)Vd, Ud, Eo, WINO_BINS, fd.M, f.C, f.N, st);
         else launch_wino_gemm((const float*)Vd, Ud, Eo, fd.M, f.C, f.N, st);
         hipLaunchKernelGGL(wino_output_kernel, dim3(cdiv(fd.M, 4) << fd.nq_shift), dim3(256), 0, st, (const float*)Eo, out, ld_out,

@@ -940,6 +940,10 @@ extern "C" int gdn_clock_probe_stop(uint64_t* buf, void* stream) {
 }
 
 extern "C" int gdn_version(void) { return 223; }
+extern "C" int gdn_hints_supported(void) {
+    return GDN_HINT_TRAIN | GDN_HINT_NO_X3 | GDN_HINT_NO_WINO_F4 | GDN_HINT_FFT_NP32 | GDN_HINT_FFT_NP40 | GDN_HINT_FLIP_TAPS |
+           GDN_HINT_PLAN_BATCH(0xff) | GDN_HINT_PLAN_CUS(2040);
+}
 
 extern "C" const char* gdn_strerror(int status) {
     switch (status) {

@@ -334,10 +334,13 @@ class AutoEncoder_DtoD(_EncDec):
 
 
 class AutoEncoder(_HipModule):
-    """Legacy colour->depth network used for inference. Reference AE_model_unet.py:96-261.
+    """Legacy colour->depth network: the one the published GDN_RtoD_pretrained.pkl belongs to. Reference
+    AE_model_unet.py:96-261.
 
-    Inference-only on the HIP path (the reference itself only instantiates it in
-    RtoD_test / depth_extract.py)."""
+    In train() mode with grad enabled the forward records a tape, so the network trains and fine-tunes like the other two
+    (BatchNorm only; its three stride-1 ConvTranspose2d decoder layers then run as flipped-tap convolutions in a transform
+    domain, engine._flip_op).  In eval() mode or under no_grad nothing is recorded: the inference path the reference uses it
+    for (RtoD_test / depth_extract.py)."""
 
     def __init__(self, init_weights=True, norm='Batch', height=128, width=416):
         super().__init__()
@@ -398,7 +401,11 @@ class AutoEncoder(_HipModule):
         if (x.shape[2], x.shape[3]) != (self.height, self.width):
             raise GdnError("input is %dx%d but the model was built for %dx%d" %
                            (x.shape[2], x.shape[3], self.height, self.width))
-        with torch.no_grad():
+        record = self.training and torch.is_grad_enabled()
+        if record and isinstance(self.N64_down, nn.InstanceNorm2d):
+            raise GdnError("AutoEncoder(norm='Instance') is inference-only on the HIP path: train-mode InstanceNorm is not "
+                           "implemented for this network (build it with norm='Batch', or call eval())")
+        with torch.enable_grad() if record else torch.no_grad():
             if istrain is True:
                 return self._forward_impl(x, tuple(range(8)))
             return self._forward_impl(x, (7,))

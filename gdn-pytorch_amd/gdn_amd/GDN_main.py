@@ -22,6 +22,10 @@ and keeps the set in device memory (datasets.GpuResidentLoader); ``--resident_gb
 NYU training: pass ``train_loader=datasets.GpuNYUAugmentLoader(...)`` (the NYU transform of :94-129 on the GPU; or its
 device-resident form GpuNYUResidentLoader) and a GpuCropLoader over the test set to run() with args.dataset == 'NYU'; the command line does
 not build them.  Make3D training and evaluation are not implemented.
+``--rtod_arch {unet,legacy}`` picks the colour-to-depth network of the RtoD modes (default: AutoEncoder_2 for training, the
+legacy AutoEncoder for RtoD_test, as ever), so a checkpoint either mode trains can be evaluated by ``--mode RtoD_test``;
+``--init_from X.pkl`` loads a state dict into the network being trained before the first step (fine-tuning the published
+GDN_RtoD_pretrained.pkl: ``--mode RtoD --rtod_arch legacy --init_from GDN_RtoD_pretrained.pkl``).
 """
 import os
 import sys
@@ -40,6 +44,25 @@ TEST_MODES = ('DtoD_test', 'RtoD_test')
 
 def _make_optimizer(model, args):
     return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4)
+
+
+def _rtod_network(args, H, W):
+    """The colour-to-depth network of the RtoD modes (option.rtod_arch): AutoEncoder_2, or the legacy AutoEncoder."""
+    if option.rtod_arch(args) == 'legacy':
+        return AutoEncoder(norm=args.norm, height=H, width=W)
+    return AutoEncoder_2(norm=args.norm, input_dim=3, height=H, width=W)
+
+
+def _init_from(model, args, rank):
+    """--init_from: the fine-tuning entry.  A missing file is an error, never a silent random initialisation."""
+    path = getattr(args, "init_from", None)
+    if not path:
+        return
+    if not os.path.isfile(path):
+        raise FileNotFoundError("--init_from %r: no such file" % (path,))
+    load_checkpoint(model, path)
+    if rank == 0:
+        print("=> initialised %s from %s" % (type(model).__name__, path))
 
 
 def _check_dataset(args):
@@ -163,6 +186,7 @@ def run(args, train_loader=None, val_loader=None):
 
     if args.mode == 'DtoD':
         G = AutoEncoder_DtoD(norm=args.norm, input_dim=1, height=H, width=W).to(dev).compute_dtype(args.dtype)
+        _init_from(G, args, rank)
         D.broadcast_parameters(G)             # rank 0's weights / BN buffers everywhere (identical seeds make this a no-op)
         opt = _make_optimizer(G, args)
         loss = train_AE_DtoD(args, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
@@ -181,7 +205,8 @@ def run(args, train_loader=None, val_loader=None):
             G.eval()
             if getattr(args, "latent_grad", False):
                 G.requires_grad_(False)       # the guide only passes d(latent)/d(outputs) through
-        R = AutoEncoder_2(norm=args.norm, input_dim=3, height=H, width=W).to(dev).compute_dtype(args.dtype)
+        R = _rtod_network(args, H, W).to(dev).compute_dtype(args.dtype)
+        _init_from(R, args, rank)
         D.broadcast_parameters(R)
         opt = _make_optimizer(R, args)
         return train_AE_RtoD(args, R, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
@@ -191,7 +216,7 @@ def run(args, train_loader=None, val_loader=None):
             model = AutoEncoder_DtoD(norm=args.norm, input_dim=1, height=H, width=W).to(dev).compute_dtype(args.dtype)
             ckpt = args.model_dir
         else:
-            model = AutoEncoder(norm=args.norm, height=H, width=W).to(dev).compute_dtype(args.dtype)
+            model = _rtod_network(args, H, W).to(dev).compute_dtype(args.dtype)
             ckpt = args.RtoD_model_dir
         if os.path.exists(ckpt):
             load_checkpoint(model, ckpt)

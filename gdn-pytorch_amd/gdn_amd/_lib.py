@@ -30,6 +30,7 @@ _i32, _i64, _f, _sz = c_int32, c_int64, c_float, c_size_t
 # name -> (restype, argtypes); status-returning functions are wrapped to raise.
 _SIGS = {
     "gdn_version": (c_int32, []),
+    "gdn_hints_supported": (c_int32, []),
     "gdn_strerror": (c_char_p, [c_int32]),
     "gdn_device_info": (c_int32, [c_char_p, c_int32]),
     "gdn_conv_out_dims": (c_int32, [_PG, POINTER(c_int32), POINTER(c_int32)]),
@@ -131,7 +132,7 @@ _SIGS = {
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),
 }
-_STATUS_FUNCS = {n for n, (r, _) in _SIGS.items() if r is c_int32} - {"gdn_version", "gdn_device_info"}
+_STATUS_FUNCS = {n for n, (r, _) in _SIGS.items() if r is c_int32} - {"gdn_version", "gdn_device_info", "gdn_hints_supported"}
 
 EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --

@@ -1,8 +1,9 @@
 """Demo inference on image files with the HIP path (counterpart of the reference's depth_extract.py:60-150).
 
-    python -m gdn_amd.depth_extract --model_dir X.pkl --img_dir ./imgs --out_dir ./depth [--batch 8]
+    python -m gdn_amd.depth_extract --model_dir X.pkl --img_dir ./imgs --out_dir ./depth [--batch 8] [--arch unet]
 
-Loads a reference-format checkpoint (``module.``-prefixed keys of the legacy ``AutoEncoder``), resizes
+Loads a reference-format checkpoint (``module.``-prefixed keys of the legacy ``AutoEncoder``; ``--arch unet``: of the
+``AutoEncoder_2`` that ``--mode RtoD`` trains by default), resizes
 each image to 128x416 (PIL bilinear; the reference used the since-removed scipy.misc.imresize), maps
 to [-1,1] exactly like ArrayToTensor + Normalize (transform_list.py:89-113), runs the forward on the
 GPU and writes the depth map resized back to the source resolution as 16-bit PNG.  Unlike the
@@ -16,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from .AE_model_unet import AutoEncoder
+from .AE_model_unet import AutoEncoder, AutoEncoder_2
 from .trainer import load_checkpoint
 
 EXTS = (".png", ".jpg", ".jpeg", ".bmp")
@@ -40,10 +41,15 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=416)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--arch", default="legacy", choices=["legacy", "unet"],
+                    help="network the checkpoint belongs to: legacy = AutoEncoder (the published weights), unet = AutoEncoder_2")
     a = ap.parse_args(argv)
     from PIL import Image
     dev = torch.device("cuda", 0)
-    model = AutoEncoder(height=a.height, width=a.width)
+    if a.arch == "legacy":
+        model = AutoEncoder(height=a.height, width=a.width)
+    else:
+        model = AutoEncoder_2(input_dim=3, height=a.height, width=a.width)
     if a.model_dir:
         load_checkpoint(model, a.model_dir)
     else:
@@ -59,7 +65,8 @@ def main(argv=None):
         x = torch.stack([t for t, _ in loaded]).to(dev)
         torch.cuda.synchronize()
         t0 = time.time()
-        d = model(x, istrain=False)
+        with torch.no_grad():
+            d = model(x, istrain=False)
         torch.cuda.synchronize()
         total += time.time() - t0
         n += len(chunk)

@@ -22,6 +22,10 @@ _FFT_MIN_K = 5
 # (csrc/conv_wino2.hip) when both channel counts reach this value: the transforms move ~1.8x the layer's
 # activations (measured: a gain on every such layer of G, the smallest at 64 channels, tests/diag/wino2_time.py)
 _WINO2_MIN_C = 64
+# window sizes of the stride-1 ConvTranspose2d layers that train in a transform domain as flipped-tap convolutions (_flip_op):
+# the three the legacy AutoEncoder has, each measured against the direct kernels (tests/diag/legacy_layer_time.py, DESIGN.md
+# 2.16).  The kernels also take 9x9; no network here has such a layer, so it is not measured and not selected.
+_FLIP_TAPS_K = (3, 5, 7)
 # The three fusions below are on; the tests switch them off to compare against the unfused form, which is also what a
 # layer that cannot fuse runs.
 # train-mode BatchNorm: scale/shift/ReLU of a ResidualBlock's first half applied in the consumer's loader, BatchNorm-backward
@@ -394,6 +398,30 @@ def _conv_op(mod, reflect):
     return op
 
 
+def _flip_op(ctx, conv, bn, ldt, x2):
+    """A stride-1 ConvTranspose2d(k, padding=k // 2) with odd k IS a convolution: the correlation with its stored taps in
+    reverse order, and its tap-major buffer [k*k][Cout][Cin] is already laid out like a Conv2d's.  Written that way
+    (ops.Conv(flip_taps=True): a transposed = 0 geometry carrying GDN_HINT_FLIP_TAPS) the frequency-domain and Winograd paths
+    run it forward and backward.  Returns that op for a layer whose backward is being recorded -- the legacy
+    AutoEncoder's three decoder layers under training -- or None: without a tape (inference), in bf16, with a concatenated
+    input or in front of a train-mode InstanceNorm the layer stays the transposed op it always was.  conv_bn_act keeps the op
+    only where _conv_path then picks a transform-domain path for it."""
+    if not (ctx.record and isinstance(conv, torch.nn.ConvTranspose2d) and x2 is None
+            and ldt == torch.float32 and ctx.dtype == torch.float32):
+        return None
+    k = conv.kernel_size[0]
+    if (conv.stride[0] != 1 or k not in _FLIP_TAPS_K or conv.padding[0] != k // 2 or conv.output_padding[0] != 0
+            or conv.dilation[0] != 1 or conv.groups != 1 or conv.kernel_size[1] != k):
+        return None
+    if bn.training and isinstance(bn, torch.nn.InstanceNorm2d):
+        return None
+    op = getattr(conv, "_gdn_op_flip", None)
+    if op is None:
+        op = ops.Conv(conv.in_channels, conv.out_channels, k, 1, k // 2, flip_taps=True)
+        conv._gdn_op_flip = op
+    return op
+
+
 def _w_tap(mod):
     tr = isinstance(mod, torch.nn.ConvTranspose2d)
     v = tap_view(mod.weight.data, tr)
@@ -572,7 +600,13 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
     ldt = _layer_dtype(ctx, conv)
     if x.dtype != ldt:
         raise GdnError("layer %d->%d computes in %s but its input is %s" % (conv.in_channels, conv.out_channels, ldt, x.dtype))
-    path = _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect)
+    fop = _flip_op(ctx, conv, bn, ldt, x2)
+    path = _conv_path(ctx, x, conv, bn, fop or op, ldt, x2, reflect)
+    if fop is not None:
+        if path.name in ("fft", "wino"):
+            op = fop
+        else:                            # no transform-domain path takes this geometry: the transposed op, as ever
+            path = _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect)
     up = None
     if isinstance(x, Up2x):
         # training needs the fold pass of a reflection-padded layer for the adjoint of the interpolation
@@ -775,10 +809,34 @@ def conv_plain(ctx, x, conv, x2=None):
     """Bare convolution without norm/activation (legacy AutoEncoder 1x1 after cat, :210)."""
     op = _conv_op(conv, 0)
     ctx.claim(x)
-    w, tr = _w_for(ctx, conv, _layer_dtype(ctx, conv))
+    if x2 is not None:
+        ctx.claim(x2)
+    ldt = _layer_dtype(ctx, conv)
+    w, tr = _w_for(ctx, conv, ldt)
     y = op.fwd(x, w, x2=x2)
     if ctx.record:
-        raise GdnError("legacy AutoEncoder is inference-only on the HIP path")
+        in_hw = (x.shape[1], x.shape[2])
+
+        def bwd():
+            dy = ctx.pop_grad(y)
+            if dy is None:
+                return
+            dy = _dense(dy)
+            if dy.dtype != ldt:
+                dy = ops.cast(dy, ldt)
+            if conv.weight.requires_grad:
+                _wgrad_into(ctx, conv, x, dy, x2)
+                ctx.grads_done(conv.weight)
+            wt = ops.transpose_taps(_w_tap(conv)[0], dtype=ldt)
+            if x2 is None:
+                if ctx.wants_dx(x):
+                    ctx.grads[id(x)] = (x, op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(x, ldt)))
+            else:
+                dcat = op.dgrad(dy, wt, in_hw)
+                c1 = x.shape[3]
+                ctx.add_grad(x, dcat[..., :c1])
+                ctx.add_grad(x2, dcat[..., c1:])
+        ctx.tape.append(bwd)
     return y
 
 

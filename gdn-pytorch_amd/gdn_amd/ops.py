@@ -47,6 +47,7 @@ def _chk(t, name="tensor", bf16_ok=False):
 
 CFG_BF16 = 0x10000      # GDN_CFG_BF16
 HINT_TRAIN, HINT_NO_X3, HINT_NO_WINO_F4, HINT_FFT_NP32, HINT_FFT_NP40 = 1, 2, 4, 8, 16      # GDN_HINT_* bits of gdn_conv_geom.hints
+HINT_FLIP_TAPS = 32
 
 
 def plan_override_hints():
@@ -251,11 +252,22 @@ class ShaderClock:
 class Conv:
     """Geometry + launch helper for one Conv2d / ConvTranspose2d layer.
 
-    Weights are tap-major [k*k, Cout, Cin] (see AE_model_unet._tap_view)."""
+    Weights are tap-major [k*k, Cout, Cin] (see AE_model_unet._tap_view).
 
-    def __init__(self, cin, cout, k, stride=1, pad=0, reflect=False, transposed=False):
+    flip_taps: a stride-1 ConvTranspose2d(cin, cout, k, 1, k // 2) given as the convolution it is (GDN_HINT_FLIP_TAPS: the
+    correlation with the stored taps in reverse order) -- the form in which the transform-domain paths (fft_* / wino_*) run it
+    forward AND backward; w_tap / dw_tap are the module's own tap-major weight and gradient.  The direct entry points (fwd /
+    dgrad / wgrad) take the same layer as transposed=True."""
+
+    def __init__(self, cin, cout, k, stride=1, pad=0, reflect=False, transposed=False, flip_taps=False):
+        if flip_taps:
+            if transposed or reflect or stride != 1 or k % 2 == 0 or pad != k // 2:
+                raise GdnError("flip_taps describes a stride-1 ConvTranspose2d with odd k and padding k // 2 as a plain "
+                               "convolution: transposed / reflect must be off")
+            if not int(lib.gdn_hints_supported()) & HINT_FLIP_TAPS:
+                raise GdnError("libgdn_hip.so does not implement GDN_HINT_FLIP_TAPS; rebuild it")
         self.cin, self.cout, self.k, self.stride, self.pad = cin, cout, k, stride, pad
-        self.reflect, self.transposed = bool(reflect and pad > 0), transposed
+        self.reflect, self.transposed, self.flip_taps = bool(reflect and pad > 0), transposed, bool(flip_taps)
         self._geom = {}
         self._fwd_ws = {}
         self._slots = {}
@@ -267,6 +279,8 @@ class Conv:
         if not (_f4 if f4 is None else f4):
             hints |= HINT_NO_WINO_F4
         hints |= plan_override_hints()
+        if self.flip_taps:
+            hints |= HINT_FLIP_TAPS
         key = (B, H, W, hints)
         g = self._geom.get(key)
         if g is None:
@@ -372,7 +386,7 @@ class Conv:
     # ---- FFT-domain path (csrc/conv_fft.hip): stride-1 zero-padded fp32 layers with 64..256 channels ----
     def fft_ok(self, B, H, W, backward=False, train=False):
         """True when gdn_fftconv_fwd (and, with `backward`, gdn_fftconv_bwd) supports this layer at this input size.
-        Stride-1 ConvTranspose2d layers are forward-only.  train (here and in fft_fwd / fft_bwd, the same value for one
+        Stride-1 ConvTranspose2d layers are forward-only as transposed=True and have the backward as flip_taps=True.  train (here and in fft_fwd / fft_bwd, the same value for one
         layer instance): GDN_HINT_TRAIN -- forward + backward of a trained layer, tiled for the sum of both."""
         _, ref, _, _ = self.geom(B, H, W, 1 if train else 0)
         if backward:
@@ -487,8 +501,11 @@ class Conv:
         lib.gdn_fftconv_cgemm_shape(ref, ctypes.byref(bins), ctypes.byref(M), ctypes.byref(npnt))
         return ws, bins.value, M.value, npnt.value
 
-    def wino_ok(self, B, H, W):
+    def wino_ok(self, B, H, W, backward=False):
+        """True when gdn_winoconv_fwd (and, with `backward`, gdn_winoconv_bwd) supports this layer at this input size."""
         _, ref, _, _ = self.geom(B, H, W)
+        if backward:
+            return int(lib.gdn_winoconv_bwd_workspace_bytes(ref)) > 0
         return int(lib.gdn_winoconv_state_bytes(ref)) > 0
 
     def wino_fwd(self, x, w_tap, stats=False, addsrc=None, state=False, affine=None, act=ACT_NONE, in_affine=None,

@@ -1,5 +1,6 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
-plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident).
+plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
+--init_from).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -61,7 +62,27 @@ def build_parser():
     p.add_argument('--resident_gb', type=float, default=None, metavar='GB',
                    help='with --resident: the most device memory (GB, 1e9 bytes) one preloaded set may take '
                         '(default: half of the free memory)')
+    p.add_argument('--rtod_arch', default=None, choices=['unet', 'legacy'],
+                   help='colour-to-depth network of the RtoD modes: unet = AutoEncoder_2, legacy = AutoEncoder (the network of '
+                        'the published GDN_RtoD_pretrained.pkl).  Default: what each mode always built -- unet for RtoD / '
+                        'RtoD_single, legacy for RtoD_test')
+    p.add_argument('--init_from', type=str, default=None, metavar='PATH',
+                   help='DtoD / RtoD / RtoD_single: load this state dict (reference format with module. prefixes, or bare) into '
+                        'the network being trained before the first step -- fine-tuning; a missing file is an error')
     return p
+
+
+RTOD_ARCH_DEFAULT = {'RtoD': 'unet', 'RtoD_single': 'unet', 'RtoD_test': 'legacy'}
+
+
+def rtod_arch(args):
+    """'unet' (AutoEncoder_2) or 'legacy' (AutoEncoder): --rtod_arch, or the mode's historical network."""
+    arch = getattr(args, 'rtod_arch', None)
+    if arch is None:
+        arch = RTOD_ARCH_DEFAULT.get(args.mode, 'unet')
+    if arch not in ('unet', 'legacy'):
+        raise ValueError("--rtod_arch %r is not one of unet / legacy" % (arch,))
+    return arch
 
 
 parser = build_parser()

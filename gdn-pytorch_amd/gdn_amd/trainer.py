@@ -218,6 +218,10 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
             errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
             if _is_main():
                 print(' * Avg ' + ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
+    if loss is not None and model_num == 0:
+        # no cadence save happened (the reference's per-epoch save is commented out, trainer.py:877-887): a run shorter than
+        # 700 steps per epoch -- a fine-tune, a trial -- leaves the weights it ends with instead of nothing
+        _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
     return loss, output_loss, latent
 
 

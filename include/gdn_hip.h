@@ -40,9 +40,12 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
+/* The GDN_HINT_* bits (below) this library acts on.  A binding that sets a bit that CHANGES WHAT IS COMPUTED (GDN_HINT_FLIP_TAPS)
+ * checks it here first: a library that predates the bit would silently ignore it. */
+int gdn_hints_supported(void);
 const char* gdn_strerror(int status);
 /* Fills name[] with the HIP device name of the current device; returns CU count (<0 on error). */
 int gdn_device_info(char* name, int name_len);
@@ -71,7 +74,15 @@ typedef struct {
  * frequency-domain path then tiles for the sum of both passes: 40-point tiles (32 valid outputs of a 9x9 window: 128 x 416
  * is exactly 4 x 13 of them, 26 % fewer transformed points) shorten the three per-bin GEMM chains of a training step by a
  * quarter but make the forward's single-pass transforms slower, so inference / frozen layers keep the 32-point tiles. */
-enum { GDN_HINT_TRAIN = 1, GDN_HINT_NO_X3 = 2, GDN_HINT_NO_WINO_F4 = 4, GDN_HINT_FFT_NP32 = 8, GDN_HINT_FFT_NP40 = 16 };
+enum { GDN_HINT_TRAIN = 1, GDN_HINT_NO_X3 = 2, GDN_HINT_NO_WINO_F4 = 4, GDN_HINT_FFT_NP32 = 8, GDN_HINT_FFT_NP40 = 16,
+       GDN_HINT_FLIP_TAPS = 32 };
+/* GDN_HINT_FLIP_TAPS (transposed == 0, zero padding, stride 1, odd k, pad == k / 2; gdn_fftconv_* and gdn_winoconv_* only):
+ * the layer is a stride-1 nn.ConvTranspose2d(Cin, Cout, k, 1, k / 2) written as the convolution it is -- the correlation with
+ * the stored taps in reverse order.  `w` is that module's tap-major buffer [k*k][Cout][Cin] as stored, and `dw` receives the
+ * gradient of the STORED taps (the weight-gradient output pass writes tap t to slot k*k - 1 - t), so the caller hands in
+ * the module's own weight and gradient slices.  Unlike the other hints this one changes what is computed, not how: it is
+ * part of the layer's definition.  The direct entry points (gdn_conv_fwd / _dgrad / _wgrad / _wgrad_bf16) refuse it with
+ * GDN_ERR_UNSUPPORTED rather than compute the un-flipped layer; they take the same layer as a transposed == 1 geometry, for which the transform-domain paths remain forward-only (fft) or refuse (wino). */
 /* Plan overrides (tests, measurements; 0 = none), fields of `hints`: the library itself reads no environment variable.
  *   GDN_HINT_PLAN_BATCH(n), bits 8..15: every plan that depends on the batch size is made as if the batch were n (1..255), so
  *                           a batch-1 call takes the plans of a batch-n call and an image compares bitwise across batch sizes;
