@@ -909,6 +909,68 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
     return gdn_launch_status();
 }
 
+// ---- F(4x4,3x3) backward with both gradients, in phases a caller can put on two streams ----
+// workspace: Vd [36][M][N], Dv [36][M][N], P (tn_splits_max sets of [36][N][C]), Eo [36][M][C] -- four SEPARATE regions, where
+// gdn_winoconv_bwd lets Vd / Dv and P / Eo share: the weight-gradient chain (Dv -> P -> dw) and the data-gradient chain
+// (Vd -> Eo -> dx) touch disjoint memory once both transforms of dy have run.
+namespace {
+inline size_t pair_vd_bytes(const WinoGeom& f) { return al256((size_t)f.bins * f.M * f.N * 4); }
+inline size_t pair_p_bytes(const WinoGeom& f) { return (size_t)tn_splits_max(f) * al256((size_t)f.bins * f.N * f.C * 4); }
+inline size_t pair_eo_bytes(const WinoGeom& f) { return al256((size_t)f.bins * f.M * f.C * 4); }
+// the layers the two-chain form is for: F(4x4,3x3) plans (zero padding, every GEMM bf16 x 3)
+inline bool pair_geom(const gdn_conv_geom* g, WinoGeom& f) { return wino_geom(g, f) && f.T == 4; }
+}  // namespace
+
+extern "C" size_t gdn_winoconv_bwd_pair_workspace_bytes(const gdn_conv_geom* g) {
+    WinoGeom f;
+    if (!pair_geom(g, f)) return 0;
+    return 2 * pair_vd_bytes(f) + pair_p_bytes(f) + pair_eo_bytes(f);
+}
+
+extern "C" int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, int32_t ldy, const float* w, const void* state,
+                                     float* dx, int32_t ldx, const float* addsrc, int32_t ld_add, float* dw,
+                                     const float* bnb_y, int32_t ld_bnb, const float* bnb_co, int32_t bnb_relu,
+                                     float* bnb_partial, int32_t dx_up2x, int32_t phases, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    (void)hipGetLastError();
+    (void)w;                                   // (the data gradient's weight set comes with the forward's state)
+    WinoGeom f;
+    if (!pair_geom(g, f)) return GDN_ERR_UNSUPPORTED;
+    if (!dy || !dx || !dw || !state) return GDN_ERR_BAD_ARG;
+    if (bnb_y && (!bnb_co || !bnb_partial)) return GDN_ERR_BAD_ARG;
+    if (dx_up2x < 0 || dx_up2x > 2) return GDN_ERR_BAD_ARG;
+    if (dx_up2x) return GDN_ERR_UNSUPPORTED;   // (as gdn_winoconv_bwd: only the fold pass of a reflection layer carries the adjoint)
+    if (phases < 0 || phases > 7) return GDN_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < gdn_winoconv_bwd_pair_workspace_bytes(g)) return GDN_ERR_WORKSPACE;
+    if (!phases) phases = 7;
+    hipStream_t st = (hipStream_t)stream;
+    char* p = (char*)workspace;
+    float* Vd = (float*)p; p += pair_vd_bytes(f);
+    float* Dv = (float*)p; p += pair_vd_bytes(f);
+    float* P = (float*)p; p += pair_p_bytes(f);
+    float* Eo = (float*)p;
+    WinoGeom fd = f;
+    fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift;
+    if (phases & 1) {
+        hipLaunchKernelGGL(wino4_input_kernel, dim3(cdiv(fd.M, 4) << fd.cq_shift), dim3(256), 0, st, dy, ldy, Vd, fd,
+                           (const float*)nullptr, (const float*)nullptr, 0, 0);
+        hipLaunchKernelGGL(wino4_dy_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, dy, ldy, Dv, f);
+    }
+    if (phases & 2) {
+        const int ns = tn_splits(f);
+        launch_gemm_x3_tn((const float*)Dv, (const float*)state, P, f.bins, f.M, f.N, f.C, ns, st);
+        hipLaunchKernelGGL(wino4_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)P, dw, f.N, f.C, ns, f.flip ? 1 : 0);
+    }
+    if (phases & 4) {
+        const float* Ud = (const float*)((const char*)state + v_bytes(f));
+        launch_gemm_x3_nt((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, st);
+        hipLaunchKernelGGL(wino4_output_kernel, dim3(cdiv(fd.M, 4) << fd.nq_shift), dim3(256), 0, st, (const float*)Eo, dx, ldx,
+                           addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0,
+                           fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu);
+    }
+    return gdn_launch_status();
+}
+
 // Measurement hook (bench.py roofline, tools/): the 16 per-bin GEMMs of one forward alone, on already transformed operands
 // V [16][M][Cin] and U [16][Cout][Cin]  ->  Mo [16][M][Cout].
 extern "C" int gdn_winoconv_gemm(const gdn_conv_geom* g, const float* V, const float* U, float* Mo, void* stream) {

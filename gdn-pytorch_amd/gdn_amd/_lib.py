@@ -63,6 +63,9 @@ _SIGS = {
     "gdn_winoconv_bnb_slots": (_i64, [_PG]),
     "gdn_winoconv_gemm": (c_int32, [_PG, _P, _P, _P, _P]),
     "gdn_winoconv_bwd": (c_int32, [_PG, _P, _i32, _P, _P, _P, _i32, _P, _i32, _P, _P, _i32, _P, _i32, _P, _i32, _P, _sz, _P]),
+    "gdn_winoconv_bwd_pair_workspace_bytes": (_sz, [_PG]),
+    "gdn_winoconv_bwd_pair": (c_int32, [_PG, _P, _i32, _P, _P, _P, _i32, _P, _i32, _P, _P, _i32, _P, _i32, _P, _i32, _i32, _P, _sz,
+                                        _P]),
     "gdn_wino2conv_fwd_workspace_bytes": (_sz, [_PG]),
     "gdn_wino2conv_state_bytes": (_sz, [_PG]),
     "gdn_wino2conv_stats_slots": (_i64, [_PG]),

@@ -556,8 +556,28 @@ class Conv:
             raise GdnError("wino_bwd: bnb needs the data gradient (need_dx)")
         dx = torch.empty((B, H // 2, W // 2, self.cin) if up2x else (B, H, W, self.cin), dtype=torch.float32,
                          device=dy.device) if need_dx else None
-        ws = workspace(nb, dy.device, "fft")
         by, bco, brelu, bpart = bnb if bnb is not None else (None, None, False, None)
+        npair = int(lib.gdn_winoconv_bwd_pair_workspace_bytes(ref)) if dw_tap is not None and need_dx and not up2x else 0
+        if npair and state is not None:
+            # F(4x4,3x3) with both gradients: the weight-gradient chain and the data-gradient chain share only the read of
+            # dy, and each GEMM leaves part of the chip idle in its last round of workgroups -- the weight-gradient chain runs
+            # on the second stream of OURS next to the data-gradient chain, as in fft_bwd.  The join before returning keeps a
+            # 16-bit-matrix kernel from running beside the next layer's kernels and makes the shared workspace safe.
+            ws = workspace(npair, dy.device, "fft")
+
+            def call(phases, st):
+                lib.gdn_winoconv_bwd_pair(ref, _p(dy), _ld(dy), _p(w_tap), _p(state), _p(dx), _ld(dx), _p(addsrc),
+                                          0 if addsrc is None else _ld(addsrc), _p(dw_tap), _p(by), 0 if by is None else _ld(by),
+                                          _p(bco), 1 if brelu else 0, _p(bpart), 0, phases, _p(ws), npair, st)
+            main = torch.cuda.current_stream(dy.device)
+            side = side_stream(dy.device)
+            call(1, main.cuda_stream)
+            side.wait_stream(main)
+            call(2, side.cuda_stream)
+            call(4, main.cuda_stream)
+            main.wait_stream(side)
+            return dx
+        ws = workspace(nb, dy.device, "fft")
         lib.gdn_winoconv_bwd(ref, _p(dy), _ld(dy), _p(w_tap), _p(state), _p(dx), 0 if dx is None else _ld(dx), _p(addsrc),
                              0 if addsrc is None else _ld(addsrc), _p(dw_tap), _p(by), 0 if by is None else _ld(by), _p(bco),
                              1 if brelu else 0, _p(bpart), int(up2x), _p(ws), nb, stream())

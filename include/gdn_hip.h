@@ -293,6 +293,25 @@ int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t ldy, const
                      const void* state, float* dx, int32_t ldx, const float* addsrc, int32_t ld_add,
                      float* dw, const float* bnb_y, int32_t ld_bnb, const float* bnb_co, int32_t bnb_relu,
                      float* bnb_partial, int32_t dx_up2x, void* workspace, size_t workspace_bytes, void* stream);
+/* The F(4x4,3x3) backward with BOTH gradients, in phases a caller can issue on two streams of its own.  Arguments as
+ * gdn_winoconv_bwd; dx, dw and state are all required (w is not read).  The workspace query returns 0 unless the layer plans
+ * F(4x4,3x3): F(2x2,3x3) and reflection-padded layers, and calls that want one gradient only, stay with gdn_winoconv_bwd
+ * (GDN_ERR_UNSUPPORTED / GDN_ERR_BAD_ARG here).  phases is a mask:
+ *   1  both transforms of dy: Vd = B^T d B of the 6x6 patches (data gradient) and Dv = G_w y G_w^T of their inner 4x4 (weight gradient)
+ *   2  weight gradient: the reduction GEMM over tiles, then the fold of the 36 bins into dw
+ *   4  data gradient: the per-bin GEMMs, then the output transform into dx (+ addsrc, bnb_* partials)
+ *   0  all three, in that order, on `stream`
+ * Phases 2 and 4 only read what phase 1 wrote and touch disjoint memory otherwise, so they may run on two streams once
+ * phase 1 is complete; both must be complete before the workspace, dx or dw is used again.  Workspace layout (every
+ * region rounded up to 256 bytes; tiles = B * ceil(H/4) * ceil(W/4)): Vd [36][tiles][Cout], Dv [36][tiles][Cout], the
+ * reduction's partial product sets (splits x [36][Cout][Cin]), the data gradient's GEMM output [36][tiles][Cin].
+ * Results are bit-identical to gdn_winoconv_bwd's. */
+size_t gdn_winoconv_bwd_pair_workspace_bytes(const gdn_conv_geom* g);
+int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, int32_t ldy, const float* w,
+                          const void* state, float* dx, int32_t ldx, const float* addsrc, int32_t ld_add,
+                          float* dw, const float* bnb_y, int32_t ld_bnb, const float* bnb_co, int32_t bnb_relu,
+                          float* bnb_partial, int32_t dx_up2x, int32_t phases, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* Winograd F(3x3,2x2) for the 4x4 stride-2 pad-1 layers of G (ConvBlock(k4,s2,p1) AE_model_unet.py:497-500 with
  * ReflectionPad2d(1) or zero padding; ConvTBlock = ConvTranspose2d(k4,s2,p1) :517-520), fp32: the layer is a 2x2
