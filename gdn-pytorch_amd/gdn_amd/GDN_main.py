@@ -26,6 +26,8 @@ not build them.  Make3D training and evaluation are not implemented.
 legacy AutoEncoder for RtoD_test, as ever), so a checkpoint either mode trains can be evaluated by ``--mode RtoD_test``;
 ``--init_from X.pkl`` loads a state dict into the network being trained before the first step (fine-tuning the published
 GDN_RtoD_pretrained.pkl: ``--mode RtoD --rtod_arch legacy --init_from GDN_RtoD_pretrained.pkl``).
+``--save_state`` / ``--save_state_every N`` write the rolling ``<save_dir>/train_state.pt`` (weights, optimizer, loader and
+schedule state); ``--resume PATH`` with the otherwise unchanged command line continues that run bit for bit.
 """
 import os
 import sys
@@ -37,7 +39,8 @@ from . import option
 from .AE_model_unet import AutoEncoder, AutoEncoder_2, AutoEncoder_DtoD
 from .optim import Adam
 from .synthetic import SyntheticLoader
-from .trainer import load_checkpoint, train_AE_DtoD, train_AE_RtoD, validate, validate_NYU
+from .trainer import (load_checkpoint, load_training_state, read_training_state, train_AE_DtoD, train_AE_RtoD, validate,
+                      validate_NYU)
 
 TEST_MODES = ('DtoD_test', 'RtoD_test')
 
@@ -63,6 +66,32 @@ def _init_from(model, args, rank):
     load_checkpoint(model, path)
     if rank == 0:
         print("=> initialised %s from %s" % (type(model).__name__, path))
+
+
+def _check_resume(args):
+    """--resume, checked before anything touches the GPU: it continues a run, so it excludes --init_from (which starts
+    one), and a missing file is an error, never a silent fresh start."""
+    path = getattr(args, "resume", None)
+    if not path:
+        return
+    if getattr(args, "init_from", None):
+        raise RuntimeError("--resume continues a run with its own weights; --init_from starts one: drop one of the two")
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--resume continues a training run; --mode %s trains nothing" % args.mode)
+    if not os.path.isfile(path):
+        raise FileNotFoundError("--resume %r: no such file" % (path,))
+
+
+def _resume(args, model, opt, train_loader, rank):
+    """--resume: weights, optimizer, loader and progress from the state file; None without the flag."""
+    path = getattr(args, "resume", None)
+    if not path:
+        return None
+    progress = load_training_state(read_training_state(path), model, opt, train_loader)
+    if rank == 0:
+        print("=> resumed %s from %s: epoch %d, batch %d, step %d, lr %g" % (type(model).__name__, path, progress["epoch"] + 1,
+                                                                         progress["i"] + 1, progress["step"], progress["lr"]))
+    return progress
 
 
 def _check_dataset(args):
@@ -114,6 +143,7 @@ class ImageSaver:
 def run(args, train_loader=None, val_loader=None):
     if train_loader is None:
         _check_dataset(args)
+    _check_resume(args)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num
@@ -190,7 +220,7 @@ def run(args, train_loader=None, val_loader=None):
         D.broadcast_parameters(G)             # rank 0's weights / BN buffers everywhere (identical seeds make this a no-op)
         opt = _make_optimizer(G, args)
         loss = train_AE_DtoD(args, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
-                             args.lr, logger, None)
+                             args.lr, logger, None, progress=_resume(args, G, opt, train_loader, rank))
         if rank == 0 and loss is not None:
             print('Final loss:', loss.item())
         return loss
@@ -210,7 +240,7 @@ def run(args, train_loader=None, val_loader=None):
         D.broadcast_parameters(R)
         opt = _make_optimizer(R, args)
         return train_AE_RtoD(args, R, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
-                             args.lr, logger, None)
+                             args.lr, logger, None, progress=_resume(args, R, opt, train_loader, rank))
     if args.mode in ('DtoD_test', 'RtoD_test'):
         if args.mode == 'DtoD_test':
             model = AutoEncoder_DtoD(norm=args.norm, input_dim=1, height=H, width=W).to(dev).compute_dtype(args.dtype)

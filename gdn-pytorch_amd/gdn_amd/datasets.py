@@ -214,6 +214,52 @@ class GpuAugmentLoader:
         self.order_rng = random.Random(order_seed)
         self.pool = cf.ThreadPoolExecutor(workers) if workers > 0 else None
         self.last_params = None
+        # resume (state_dict / load_state_dict): the order stream's state before the current epoch's shuffle, the batch last
+        # handed out in it (-1: none yet) and, after a load, the batch the next __iter__ starts with
+        self._order_start, self._pos, self._resume = None, -1, None
+
+    def _begin_epoch(self):
+        """(sample order of the epoch that starts now, its first batch): batch 0 of a fresh shuffle, or -- once, after
+        load_state_dict() -- the batch after the saved one in the saved epoch's order.  The skipped batches are neither
+        fetched nor drawn for: the draw streams were saved after them."""
+        first, self._resume = self._resume or 0, None
+        self._order_start = self.order_rng.getstate()
+        self._pos = first - 1
+        return self._epoch_order(), first
+
+    def _identity(self):
+        return {"rank": self.rank, "world": self.world, "n": len(self.ds), "batch_size": self.bs}
+
+    def state_dict(self, epoch_done=False):
+        """Position and RNG state, nothing else (a resident loader keeps its pools).  Call it between two batches: the draw
+        streams are saved as the last batch handed out left them, the order stream as it was before the current epoch's
+        shuffle, so the epoch can be rebuilt.  epoch_done=True: the current epoch is over (the training loops leave it
+        early with `break`), the next __iter__ of the restored loader starts a fresh one."""
+        fresh = epoch_done or self._order_start is None
+        np_state = self.np_rng.get_state()
+        out = self._identity()
+        out.update({"order_rng": self.order_rng.getstate() if fresh else self._order_start, "pos": -1 if fresh else self._pos,
+                    "py_rng": self.py_rng.getstate(),
+                    "np_rng": (np_state[0], [int(x) for x in np_state[1]], int(np_state[2]), int(np_state[3]), float(np_state[4]))})
+        return out
+
+    def load_state_dict(self, state):
+        """Continue where state_dict() was taken: the next __iter__ rebuilds that epoch's order and starts with the batch after
+        the saved one; later epochs go on as if the loader had never stopped.  rank, world, dataset length and batch size must
+        be the saved ones."""
+        mine = self._identity()
+        for key, what in (("world", "world size"), ("n", "dataset length"), ("batch_size", "batch size"), ("rank", "rank")):
+            if int(state[key]) != mine[key]:
+                raise GdnError("loader state was saved with %s %d, this loader has %d" % (what, int(state[key]), mine[key]))
+
+        def tup(x):
+            return tuple(tup(y) for y in x) if isinstance(x, (list, tuple)) else x
+        self.order_rng.setstate(tup(state["order_rng"]))
+        self.py_rng.setstate(tup(state["py_rng"]))
+        name, keys, pos, has_gauss, cached = state["np_rng"]
+        self.np_rng.set_state((name, np.asarray(keys, dtype=np.uint32), int(pos), int(has_gauss), float(cached)))
+        self._order_start, self._pos = self.order_rng.getstate(), int(state["pos"])
+        self._resume = self._pos + 1
 
     def _shard_len(self):
         n = len(self.ds)
@@ -242,8 +288,9 @@ class GpuAugmentLoader:
         return order
 
     def __iter__(self):
-        order = self._epoch_order()
-        for b in range(len(self)):
+        order, first = self._begin_epoch()
+        for b in range(first, len(self)):
+            self._pos = b
             idxs = order[b * self.bs:(b + 1) * self.bs]
             samples = self._fetch(idxs)
             H, W = samples[0][1].shape[:2]
@@ -254,7 +301,9 @@ class GpuAugmentLoader:
             if self.train:
                 host = [draw_params(H, W, self.py_rng, self.np_rng) for _ in samples]
                 self.last_params = host
-                params = torch.tensor(host, dtype=torch.int32).pin_memory().to(self.dev, non_blocking=True)
+                params = torch.tensor(host, dtype=torch.int32)
+                if self.dev.type == "cuda":
+                    params = params.pin_memory().to(self.dev, non_blocking=True)
             yield tuple(ops.kitti_augment(self._to_device([s[j] for s in samples]), params, self.train) for j in range(3))
 
 
@@ -269,8 +318,9 @@ class GpuCropLoader(GpuAugmentLoader):
 
     def __iter__(self):
         H, W = self.size
-        order = self._epoch_order()
-        for b in range(len(self)):
+        order, first = self._begin_epoch()
+        for b in range(first, len(self)):
+            self._pos = b
             samples = self._fetch(order[b * self.bs:(b + 1) * self.bs])
             H0, W0 = samples[0][1].shape[:2]
             for s in samples:
@@ -335,8 +385,9 @@ class GpuNYUAugmentLoader(GpuAugmentLoader):
 
     def __iter__(self):
         H, W = self.size
-        order = self._epoch_order()
-        for b in range(len(self)):
+        order, first = self._begin_epoch()
+        for b in range(first, len(self)):
+            self._pos = b
             samples = self._fetch(order[b * self.bs:(b + 1) * self.bs])
             H0, W0 = samples[0][1].shape[:2]
             for s in samples:
@@ -531,8 +582,9 @@ class GpuResidentLoader(GpuAugmentLoader):
 
     def __iter__(self):
         H, W = self.pools.size
-        order = self._epoch_order()
-        for b in range(len(self)):
+        order, first = self._begin_epoch()
+        for b in range(first, len(self)):
+            self._pos = b
             idxs = order[b * self.bs:(b + 1) * self.bs]
             rows = np.empty((len(idxs), 6), np.int32)
             rows[:, 0] = idxs
@@ -561,8 +613,9 @@ class GpuNYUResidentLoader(GpuNYUAugmentLoader):
     def __iter__(self):
         H, W = self.size
         H0, W0 = self.pools.size
-        order = self._epoch_order()
-        for b in range(len(self)):
+        order, first = self._begin_epoch()
+        for b in range(first, len(self)):
+            self._pos = b
             idxs = np.asarray(order[b * self.bs:(b + 1) * self.bs], dtype=np.int32)
             if idxs.min() < 0 or idxs.max() >= self.pools.n:
                 raise GdnError("sample index outside the %d resident samples" % self.pools.n)

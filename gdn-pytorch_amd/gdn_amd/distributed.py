@@ -325,6 +325,17 @@ def broadcast_parameters(model, src=0):
         dist.broadcast(b, src)
 
 
+def gather_objects(obj, dst=0):
+    """Every rank's picklable `obj` as a list in rank order on rank `dst`, None on the others ([obj] without a process
+    group).  Collective: every rank calls it.  For the small per-rank state of a checkpoint (the loaders' positions and
+    RNG streams), not for tensors on the hot path."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return [obj]
+    out = [None] * dist.get_world_size() if dist.get_rank() == dst else None
+    dist.gather_object(obj, out, dst=dst)
+    return out
+
+
 def allreduce_max_scalar(t):
     """4-byte MAX all-reduce (the optional global BerHu threshold)."""
     if active():

@@ -20,6 +20,10 @@ class Adam(torch.optim.Optimizer):
         # capturable: the step counter, beta^t and the hyper-parameters live in device memory (gdn_adam_step_dev), so
         # step() can be captured in a hipGraph and replayed; call refresh_hyper() after changing lr outside a capture
         self.capturable = bool(capturable)
+        # load_state_dict() parks what it read here until the store it belongs to exists (the arena is built by the first
+        # forward, the stores by the first step): id(param) -> {"step","m","v"} in LOGICAL layout, and the device step state
+        # of the capturable path per store, keyed by the store's first parameter
+        self._pending, self._pending_dev = {}, {}
 
     def refresh_hyper(self):
         """Push (lr, betas, eps, weight_decay, grad_scale) to the device buffers of the capturable path if they changed."""
@@ -66,7 +70,8 @@ class Adam(torch.optim.Optimizer):
         powers on the host first)."""
         if "hyper" not in st:
             st["hyper"] = torch.zeros(6, dtype=torch.float32, device=device)
-            st["state"] = self._dev_state(group, steps_taken, device)
+            if "state" not in st:          # (a loaded checkpoint brings the device's own bytes: _fill_arena / _fill_loose)
+                st["state"] = self._dev_state(group, steps_taken, device)
             st["group"] = group
         self._push_hyper(st, group)
 
@@ -156,6 +161,7 @@ class Adam(torch.optim.Optimizer):
                     st = {"m": ops.zeros((ar.numel,), ar.device), "v": ops.zeros((ar.numel,), ar.device), "step": 0,
                           "pstep": None}
                     self._flat[id(ar)] = st
+                    self._fill_arena(ar, st)          # a checkpoint loaded before this store existed
                 if st["pstep"] is None and all(p.grad is not None for p in ps):
                     st["step"] += 1
                     self._apply(ar.data, ar.grad, st, group, ar.device)
@@ -176,6 +182,7 @@ class Adam(torch.optim.Optimizer):
                     st["step"] = 0
                     st["m"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["v"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    self._fill_loose(p, st)
                 st["step"] += 1
                 g = p.grad
                 if g.stride() != p.stride():
@@ -184,3 +191,221 @@ class Adam(torch.optim.Optimizer):
                 if getattr(p, "_gdn_arena", None) is not None:
                     p._gdn_arena.touch()
         return loss
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # state exchange: torch.optim.Adam's format ({'state': {index: {'step','exp_avg','exp_avg_sq'}}, 'param_groups'}),
+    # moments in each parameter's LOGICAL shape, plus a private 'gdn' key for what that format has no place for
+    # ------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _refuse_capture(what):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise GdnError("optimizer %s inside a graph capture" % what)
+
+    @staticmethod
+    def _f32(x):
+        """`x` as the kernels receive it: rounded to float32."""
+        import struct
+        return struct.unpack("<f", struct.pack("<f", float(x)))[0]
+
+    @staticmethod
+    def _dev_count(state):
+        """The step count a device step state holds (the int32 after the two doubles of _dev_state)."""
+        import struct
+        return struct.unpack_from("<i", state.cpu().numpy().tobytes(), 16)[0]
+
+    def _stores(self):
+        """(kind, store, arena or None, [params]) for every state store, parameters in param_groups order within a store."""
+        out = []
+        for group in self.param_groups:
+            arenas, loose = self._arena_groups(group)
+            for ar, ps in arenas.values():
+                st = self._flat.get(id(ar))
+                if st is not None and len(ps) == len(ar.items):
+                    out.append(("arena", st, ar, [p for p, _, _, _ in ar.items]))
+                else:
+                    loose.extend(ps)
+            for p in loose:
+                st = self.state.get(p)
+                if st:
+                    out.append(("loose", st, None, [p]))
+        return out
+
+    def _count(self, st, p, memo):
+        """Updates parameter `p` of store `st` has taken: the device's count where the capturable path keeps one (graph
+        replays advance it behind the host's back), the host's otherwise."""
+        def dev(t):
+            if id(t) not in memo:
+                memo[id(t)] = self._dev_count(t)
+            return memo[id(t)]
+        pstep = st.get("pstep")
+        if "state" in st:
+            if pstep is None:
+                return dev(st["state"])
+            own = st.get("pdev", {}).get(id(p))
+            if own is not None:
+                return dev(own)
+            if st.get("full_dev"):
+                return dev(st["state"])       # no counter of its own yet: the arena's, frozen when coverage split
+        return st["step"] if pstep is None else pstep[id(p)]
+
+    def state_dict(self):
+        """torch.optim.Adam's state_dict with the real moments (logical shape, contiguous; 'step' a float32 scalar tensor like
+        torch's) and a 'gdn' key: host step counts, grad_scale and -- capturable path -- the device step state's bytes."""
+        self._refuse_capture("state_dict()")
+        index, k = {}, 0
+        for g in self.param_groups:
+            for p in g["params"]:
+                index[id(p)] = k
+                k += 1
+        groups = []
+        for g in self.param_groups:
+            packed = {key: v for key, v in g.items() if key != "params"}
+            # the betas the moments were accumulated with: the kernels take them as float32, and 1 - beta2 is where that shows
+            # (1 - float32(0.999) is 1.29e-5 below 0.001); an optimizer that goes on from these moments with the rounded
+            # values continues the same Adam run to rounding
+            packed["betas"] = tuple(self._f32(b) for b in g["betas"])
+            packed["params"] = [index[id(p)] for p in g["params"]]
+            groups.append(packed)
+        state, recs, memo = {}, [], {}
+        for kind, st, ar, ps in self._stores():
+            if kind == "arena":
+                views = {id(p): (ar._view(st["m"], o, p.shape, tr), ar._view(st["v"], o, p.shape, tr)) for p, o, n, tr in ar.items}
+            else:
+                views = {id(ps[0]): (st["m"], st["v"])}
+            for p in ps:
+                m, v = views[id(p)]
+                state[index[id(p)]] = {"step": torch.tensor(float(self._count(st, p, memo))),
+                                       "exp_avg": m.detach().clone(memory_format=torch.contiguous_format),
+                                       "exp_avg_sq": v.detach().clone(memory_format=torch.contiguous_format)}
+            pstep = st.get("pstep")
+            recs.append({"kind": kind, "params": [index[id(p)] for p in ps], "step": int(st["step"]),
+                         "pstep": None if pstep is None else [int(pstep[id(p)]) for p in ps],
+                         "full_dev": bool(st.get("full_dev")),
+                         "state": st["state"].detach().cpu().clone() if "state" in st else None,
+                         "pdev": {index[id(p)]: st["pdev"][id(p)].detach().cpu().clone() for p in ps
+                                  if id(p) in st.get("pdev", {})}})
+        # loaded, but no step since: hand back what was loaded
+        byid = {id(p): p for g in self.param_groups for p in g["params"]}
+        for pid, s in self._pending.items():
+            if pid in byid and index[pid] not in state:
+                state[index[pid]] = {"step": torch.tensor(float(s["step"])),
+                                     "exp_avg": s["m"].detach().clone(memory_format=torch.contiguous_format),
+                                     "exp_avg_sq": s["v"].detach().clone(memory_format=torch.contiguous_format)}
+        for rec in self._pending_dev.values():
+            recs.append(dict(rec, params=[index[i] for i in rec["params"]],
+                             pdev={index[i]: t for i, t in rec["pdev"].items()}))
+        return {"state": dict(sorted(state.items())), "param_groups": groups,
+                "gdn": {"version": 1, "capturable": self.capturable, "grad_scale": float(self.grad_scale), "stores": recs}}
+
+    def load_state_dict(self, state_dict):
+        """Restore a state_dict() of this class or of torch.optim.Adam over the same parameters (count and shapes are
+        checked).  Works before the first step: what was read waits until its store exists.  A store that exists already is
+        rewritten in place, moments in the arena's physical layout.  With the 'gdn' key of a capturable optimizer the
+        device step state is restored byte for byte; without it (a torch checkpoint) it is recomputed on the host from
+        'step'.  Hyper-parameters of the groups are taken from the checkpoint (betas only if they differ in float32).  Not inside a graph capture; a graph captured
+        before the load still holds the old device step state -- capture after loading."""
+        self._refuse_capture("load_state_dict()")
+        groups = state_dict["param_groups"]
+        mine = [len(g["params"]) for g in self.param_groups]
+        theirs = [len(g["params"]) for g in groups]
+        if mine != theirs:
+            raise GdnError("optimizer state for %d parameters in groups %s loaded into an optimizer with %d parameters in "
+                           "groups %s" % (sum(theirs), theirs, sum(mine), mine))
+        params = [p for g in self.param_groups for p in g["params"]]
+        by_saved = dict(zip([i for g in groups for i in g["params"]], params))
+        pending = {}
+        for key, s in state_dict["state"].items():
+            p = by_saved.get(key)
+            if p is None:
+                raise GdnError("optimizer state entry %r belongs to no parameter of the checkpoint's param_groups" % (key,))
+            for name in ("exp_avg", "exp_avg_sq"):
+                if tuple(s[name].shape) != tuple(p.shape):
+                    raise GdnError("optimizer state %r of parameter %r has shape %s, the parameter has %s" %
+                                   (name, key, tuple(s[name].shape), tuple(p.shape)))
+            pending[id(p)] = {"step": int(round(float(s["step"]))), "m": s["exp_avg"].detach(), "v": s["exp_avg_sq"].detach()}
+        for g, saved in zip(self.param_groups, groups):
+            for key, v in saved.items():
+                if key == "betas":
+                    # betas that round to this optimizer's own in float32 are the same to the kernels: keep the own spelling (the
+                    # capturable path computes its host-side powers from it, as the uninterrupted run does)
+                    if [self._f32(b) for b in v] != [self._f32(b) for b in g["betas"]]:
+                        g["betas"] = tuple(v)
+                elif key != "params":
+                    g[key] = v
+        priv = state_dict.get("gdn") or {}
+        self.grad_scale = float(priv.get("grad_scale", self.grad_scale))
+        pending_dev = {}
+        for rec in priv.get("stores", []):
+            ids = [id(by_saved[i]) for i in rec["params"] if i in by_saved]
+            if len(ids) != len(rec["params"]) or not ids:
+                continue
+            pending_dev[ids[0]] = dict(rec, params=ids, pdev={id(by_saved[i]): t for i, t in rec["pdev"].items()})
+        self._pending, self._pending_dev = pending, pending_dev
+        # stores that exist: rewrite them now; parameters without a saved state start over
+        for kind, st, ar, ps in self._stores():
+            if kind == "arena":
+                self._fill_arena(ar, st, reset=True)
+            else:
+                self._fill_loose(ps[0], st, reset=True)
+        for p in params:
+            ar = getattr(p, "_gdn_arena", None)
+            if ar is not None:
+                ar.touch()
+
+    def _take_dev(self, st, rec, device):
+        """Host counts and -- capturable -- the device step state of a store, from its 'gdn' record.  False: no usable record
+        (a torch checkpoint, or device counts saved by a capturable optimizer and read by a host-side one), the counts come
+        from 'step'."""
+        for key in ("hyper", "hyper_host", "state", "pdev", "full_dev", "group"):
+            st.pop(key, None)
+        if rec is None or (rec.get("state") is not None and not self.capturable):
+            return False
+        st["step"] = int(rec["step"])
+        st["pstep"] = None if rec["pstep"] is None else dict(zip(rec["params"], [int(c) for c in rec["pstep"]]))
+        if rec.get("state") is not None:
+            st["state"] = rec["state"].to(device=device, copy=True)        # the device's own bytes, verbatim
+            st["full_dev"] = bool(rec["full_dev"])
+            if rec["pstep"] is not None:
+                st["pdev"] = {pid: t.to(device=device, copy=True) for pid, t in rec["pdev"].items()}
+        return True
+
+    def _fill_arena(self, ar, st, reset=False):
+        """Write what load_state_dict() read for this arena's parameters into its flat store: each moment through the
+        parameter's own view of the flat buffer (tap-major for convolution weights), never under a logical shape."""
+        ids = [id(p) for p, _, _, _ in ar.items]
+        if not reset and not any(i in self._pending for i in ids):
+            return
+        st["m"].zero_()
+        st["v"].zero_()
+        counts = {}
+        for p, o, n, tr in ar.items:
+            s = self._pending.pop(id(p), None)
+            counts[id(p)] = s["step"] if s else 0
+            if s:
+                ar._view(st["m"], o, p.shape, tr).copy_(s["m"])
+                ar._view(st["v"], o, p.shape, tr).copy_(s["v"])
+        rec = self._pending_dev.pop(ids[0], None)
+        if rec is not None and (rec["kind"] != "arena" or rec["params"] != ids):
+            rec = None
+        if not self._take_dev(st, rec, ar.device):
+            level = set(counts.values())
+            if len(level) == 1:
+                st["step"], st["pstep"] = level.pop(), None
+            else:
+                st["step"], st["pstep"] = max(level), counts
+
+    def _fill_loose(self, p, st, reset=False):
+        s = self._pending.pop(id(p), None)
+        if s is None and not reset:
+            return
+        st["m"].zero_()
+        st["v"].zero_()
+        st["step"] = s["step"] if s else 0
+        if s:
+            st["m"].copy_(s["m"])
+            st["v"].copy_(s["v"])
+        rec = self._pending_dev.pop(id(p), None)
+        if rec is not None and (rec["kind"] != "loose" or rec["params"] != [id(p)]):
+            rec = None
+        self._take_dev(st, rec, p.device)
+        st.pop("pstep", None)

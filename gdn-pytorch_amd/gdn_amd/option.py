@@ -1,6 +1,6 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
---init_from).
+--init_from, --save_state, --save_state_every, --resume).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -69,6 +69,15 @@ def build_parser():
     p.add_argument('--init_from', type=str, default=None, metavar='PATH',
                    help='DtoD / RtoD / RtoD_single: load this state dict (reference format with module. prefixes, or bare) into '
                         'the network being trained before the first step -- fine-tuning; a missing file is an error')
+    p.add_argument('--save_state', action='store_true',
+                   help='training: whenever a weight checkpoint is written, also write the rolling <save_dir>/train_state.pt '
+                        '(weights, Adam moments and step state, loader position and RNG streams, epoch / iteration / learning '
+                        'rate: about three times the weights) that --resume continues from')
+    p.add_argument('--save_state_every', type=int, default=0, metavar='N',
+                   help='training: also write train_state.pt every N iterations (counted over the whole run)')
+    p.add_argument('--resume', type=str, default=None, metavar='PATH',
+                   help='DtoD / RtoD / RtoD_single: continue the run that wrote this train_state.pt, bit for bit as if it had '
+                        'never stopped (same command line otherwise); a missing file is an error, and so is --init_from with it')
     return p
 
 

@@ -43,6 +43,129 @@ def load_checkpoint(model, path, map_location="cpu"):
     return model
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# resume: everything a run needs to go on bit for bit as if it had never stopped
+STATE_FILE = "train_state.pt"
+PROGRESS_KEYS = ("epoch", "i", "lr", "model_num", "seen", "step")
+
+
+def _cpu_copy(x):
+    if torch.is_tensor(x):
+        return x.detach().to("cpu", copy=True)
+    if isinstance(x, dict):
+        return {k: _cpu_copy(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_cpu_copy(v) for v in x)
+    return x
+
+
+def training_state(model, optimizer, loader, progress):
+    """A plain dict (tensors on the host) of the model's state_dict under bare keys, the optimizer's state_dict
+    (optim.Adam: real moments and the device step state), the loader's state of every rank, the torch RNG state and
+    `progress`: 'epoch', 'i' (the batch of that epoch the last completed step used; -1: the epoch is about to start),
+    'lr', 'model_num', 'seen', 'step' (iterations over the whole run).  The guide network of RtoD is frozen and not part
+    of it.  Collective under data parallelism: every rank calls it, the loader states are gathered to rank 0, which gets
+    the dict; the other ranks get None (weights and moments are identical on all ranks)."""
+    i = int(progress.get("i", -1))
+    mine = None
+    if loader is not None:
+        if not hasattr(loader, "state_dict"):
+            raise U.GdnError("%s has no state_dict(): a resumed run would replay its first batches" % type(loader).__name__)
+        mine = loader.state_dict(epoch_done=i < 0)
+    loaders = D.gather_objects(mine)
+    if loaders is None:
+        return None
+    state = {"format": 1, "world": D.world_size(), "model": _cpu_copy(dict(model.state_dict())),
+             "optimizer": _cpu_copy(optimizer.state_dict()), "loader": loaders,
+             "torch_rng": torch.get_rng_state(),
+             "cuda_rng": torch.cuda.get_rng_state() if torch.cuda.is_available() and torch.cuda.is_initialized() else None}
+    defaults = {"epoch": 0, "i": -1, "lr": optimizer.param_groups[0]["lr"], "model_num": 0, "seen": 0, "step": 0}
+    for k in PROGRESS_KEYS:
+        v = progress.get(k, defaults[k])
+        state[k] = float(v) if k == "lr" else int(v)
+    return state
+
+
+def load_training_state(state, model, optimizer, loader):
+    """Put a training_state() dict back into newly built objects and return its progress dict for the training loops.
+    Every rank reads the same dict and takes its own loader entry; a world size other than the saved one is refused."""
+    world, saved = D.world_size(), int(state.get("world", 1))
+    if saved != world:
+        raise U.GdnError("training state was saved by %d rank(s), this run has %d: the loaders' shards and streams do not "
+                         "carry over" % (saved, world))
+    model.load_state_dict(state["model"])
+    ar = getattr(model, "_gdn_param_arena", None)
+    if ar is not None:
+        ar.touch()               # bf16 shadows of the weights are stale
+    optimizer.load_state_dict(state["optimizer"])
+    if loader is not None:
+        mine = state["loader"][D.rank()]
+        if mine is None:
+            raise U.GdnError("the training state holds no loader state for rank %d" % D.rank())
+        loader.load_state_dict(mine)
+    torch.set_rng_state(state["torch_rng"])
+    if state.get("cuda_rng") is not None and torch.cuda.is_available():
+        torch.cuda.set_rng_state(state["cuda_rng"])
+    return {k: state[k] for k in PROGRESS_KEYS}
+
+
+def save_training_state(path, model, optimizer, loader, progress, writer=torch.save):
+    """training_state() written to `path` by rank 0: to a temporary name in the same directory, then os.replace(), so a kill
+    during the write leaves the previous file, never a truncated one.  Returns the path (None on the other ranks)."""
+    state = training_state(model, optimizer, loader, progress)
+    if state is None:
+        return None
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    try:
+        with open(tmp, "wb") as f:
+            writer(state, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    return path
+
+
+def read_training_state(path):
+    """The dict save_training_state() wrote (tensors, numbers, strings, lists and tuples only: no code is unpickled)."""
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+class _StateSaver:
+    """--save_state / --save_state_every of one training loop: the rolling <save_dir>/train_state.pt."""
+
+    def __init__(self, args, save_dir, model, optimizer, loader):
+        self.on_checkpoint = bool(getattr(args, "save_state", False))
+        self.every = max(0, int(getattr(args, "save_state_every", 0) or 0))
+        self.path = save_dir + '/' + STATE_FILE
+        self.objs = (model, optimizer, loader)
+        self.batches = len(loader) if hasattr(loader, "__len__") else None
+
+    def due(self, step):
+        return self.every > 0 and step % self.every == 0
+
+    def last_batch(self, i):
+        """Batch i is the loader's last: its state is written once the epoch's own work (checkpoint, validation) is done,
+        as the start of the next epoch."""
+        return self.batches is not None and i >= self.batches - 1
+
+    def save(self, epoch, i, lr, model_num, seen, step):
+        save_training_state(self.path, *self.objs, {"epoch": epoch, "i": i, "lr": lr, "model_num": model_num, "seen": seen,
+                                                    "step": step})
+
+
+def _start(progress, lr):
+    """(first epoch, batches of it already done, lr, model_num, seen, step) of a fresh (progress None) or resumed loop."""
+    if progress is None:
+        return 0, 0, lr, 0, 0, 0
+    return (int(progress["epoch"]), int(progress["i"]) + 1, float(progress["lr"]), int(progress["model_num"]),
+            int(progress["seen"]), int(progress["step"]))
+
+
 def _to_dev(t, dev):
     return t if t.device == dev else t.to(dev, non_blocking=True)
 
@@ -62,8 +185,9 @@ def _decay_lr(optimizer, lr, fast_div):
 
 
 def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_loader, val_loader, batch_size,
-                  n_epochs, lr, logger, train_writer):
-    """Depth->depth auto-encoder training; loss = BerHu + 3*imgrad_loss (trainer.py:411-468)."""
+                  n_epochs, lr, logger, train_writer, progress=None):
+    """Depth->depth auto-encoder training; loss = BerHu + 3*imgrad_loss (trainer.py:411-468).
+    progress: what load_training_state() returned -- the loop goes on after that step."""
     if _is_main():
         print("Training for %d epochs..." % n_epochs)
     dev = _device_of(model)
@@ -71,11 +195,13 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
     epoch_size = getattr(args, "epoch_size", 0) or len(dataset_loader)
     kitti = args.dataset == "KITTI"
     loss = output_loss = gradient_loss = None
-    model_num = 0
-    t0, seen = time.time(), 0
-    for epoch in range(n_epochs):
+    epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
+    saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
+    t0 = time.time()
+    for epoch in range(epoch0, n_epochs):
         model.train()
-        for i, (gt_data, _, gt_data_2) in enumerate(dataset_loader):
+        due = False
+        for i, (gt_data, _, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
             depths = _to_dev(gt_data, dev)
             sparse = _to_dev(gt_data_2, dev) if kitti else None       # None <=> NYU: unmasked BerHu
             with tracing.span("gdn.forward"):
@@ -90,6 +216,8 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
             with tracing.span("gdn.adam"):
                 optimizer.step()
             seen += depths.shape[0] * D.world_size()
+            gstep += 1
+            due = saver.due(gstep)
             if i >= epoch_size - 1:
                 break
             if epoch > 5 and (i + 1) % 1900 == 0:
@@ -101,15 +229,22 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
             if (i + 1) % 3000 == 0:
                 _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
                 model_num += 1
+                due = due or saver.on_checkpoint
+            if due and not saver.last_batch(i):
+                saver.save(epoch, i, lr, model_num, seen, gstep)
+                due = False
         if loss is not None:
             if _is_main():
                 print('\n', 'epoch: ', epoch + 1, '  loss: ', loss.item())
             _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
             model_num += 1
+            due = due or saver.on_checkpoint
         if logger is not None and val_loader is not None:
             errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
             if _is_main():
                 print(' * Avg ' + ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
+        if due:                  # after everything this epoch does: the resumed run starts the next one
+            saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
     return loss
 
 
@@ -161,8 +296,9 @@ def guide_latent_loss(G, depths, outputs, faithful=False, latent_grad=False):
 
 
 def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer, dataset_loader, val_loader,
-                  batch_size, n_epochs, lr, logger, train_writer):
+                  batch_size, n_epochs, lr, logger, train_writer, progress=None):
     """Colour->depth training with the frozen guide G (trainer.py:670-768).
+    progress: what load_training_state() returned -- the loop goes on after that step (the guide is not part of the state).
 
     loss = BerHu + latent (value only: G's features of the estimate are taken
     under no_grad, exactly as shipped, F3) + smoothness.  mode 'RtoD_single'
@@ -176,11 +312,13 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     single = args.mode == 'RtoD_single' or DtoD_model is None
     loss = output_loss = None
     latent = torch.zeros((), device=dev)
-    model_num = 0
-    t0, seen = time.time(), 0
-    for epoch in range(n_epochs):
+    epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
+    saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
+    t0 = time.time()
+    for epoch in range(epoch0, n_epochs):
         model.train()
-        for i, (gt_data, rgb_data, gt_data_2) in enumerate(dataset_loader):
+        due = False
+        for i, (gt_data, rgb_data, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
             inputs, depths = _to_dev(rgb_data, dev), _to_dev(gt_data, dev)
             sparse = _to_dev(gt_data_2, dev) if kitti else None
             with tracing.span("gdn.forward"):
@@ -203,6 +341,8 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
             with tracing.span("gdn.adam"):
                 optimizer.step()
             seen += depths.shape[0] * D.world_size()
+            gstep += 1
+            due = saver.due(gstep)
             if i >= epoch_size - 1:
                 break
             if epoch > 2 and (i + 1) % 2200 == 0:
@@ -214,14 +354,22 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
             if (i + 1) % 700 == 0:
                 _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
                 model_num += 1
+                due = due or saver.on_checkpoint
+            if due and not saver.last_batch(i):
+                saver.save(epoch, i, lr, model_num, seen, gstep)
+                due = False
         if logger is not None and val_loader is not None:
             errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
             if _is_main():
                 print(' * Avg ' + ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
+        if due:
+            saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
     if loss is not None and model_num == 0:
         # no cadence save happened (the reference's per-epoch save is commented out, trainer.py:877-887): a run shorter than
         # 700 steps per epoch -- a fine-tune, a trial -- leaves the weights it ends with instead of nothing
         _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
+        if saver.on_checkpoint:
+            saver.save(n_epochs, -1, lr, model_num, seen, gstep)
     return loss, output_loss, latent
 
 

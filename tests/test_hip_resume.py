@@ -1,0 +1,362 @@
+"""Exact resume on the GPU: a run that is stopped after step 3, rebuilt from its training state in newly made objects and
+continued must be BIT-IDENTICAL to the run that never stopped -- weights, BatchNorm buffers, Adam's flat moments and step
+state, the loss terms and the loader's augmentation draws.  The feature adds no arithmetic, so every comparison of the
+bitwise tests is torch.equal / byte equality.
+
+Smallest training size of the suite: 32 x 64, batch 2, a 4-sample SyntheticRawKitti set through GpuAugmentLoader: two batches
+per epoch, so six steps cross two epoch boundaries and the stop after step 3 falls in the middle of the second epoch."""
+import io
+import os
+import pathlib
+import subprocess
+import sys
+
+import pytest
+import torch
+
+from test_hip_kernels import close
+
+pytestmark = pytest.mark.gpu
+
+REPO = pathlib.Path(__file__).resolve().parent.parent
+H, W, B, N = 32, 64, 2, 4
+LR, BETAS, WD = 2e-4, (0.9, 0.999), 5e-4
+
+
+class Run:
+    """Model (+ frozen guide), optimizer and loader of one training run, built like GDN_main builds them."""
+
+    def __init__(self, gpu, mode, seed, dtype="fp32", capturable=False):
+        import gdn_amd.AE_model_unet as M
+        from gdn_amd.datasets import GpuAugmentLoader, SyntheticRawKitti
+        from gdn_amd.optim import Adam
+        self.mode, self.gpu = mode, gpu
+        torch.manual_seed(seed)
+        if mode == "DtoD":
+            net = M.AutoEncoder_DtoD(input_dim=1, height=H, width=W)
+        elif mode == "RtoD_single":
+            net = M.AutoEncoder(height=H, width=W)                       # the legacy colour-to-depth network
+        else:
+            net = M.AutoEncoder_2(input_dim=3, height=H, width=W)
+        self.net = net.to(gpu).train().compute_dtype(dtype)
+        self.guide = None
+        if mode == "RtoD":                                               # frozen, the same in every run, not part of the state
+            torch.manual_seed(1234)
+            self.guide = M.AutoEncoder_DtoD(input_dim=1, height=H, width=W).to(gpu).eval().requires_grad_(False)
+        self.opt = Adam(self.net.parameters(), LR, list(BETAS), eps=1e-08, weight_decay=WD, capturable=capturable)
+        self.loader = GpuAugmentLoader(SyntheticRawKitti(N, H, W, seed=1), B, gpu, train=True, seed=5, drop_last=True)
+
+    def step(self, gt, rgb, sparse):
+        """One iteration of the training loops' body (trainer.train_AE_DtoD / train_AE_RtoD); returns the three loss terms."""
+        from gdn_amd import trainer as T
+        from gdn_amd import utils as U
+        if self.mode == "DtoD":
+            out = self.net(gt, istrain=False)
+            terms = U.dtod_loss(out, gt, sparse)
+        else:
+            out = self.net(rgb, istrain=False)
+            lat = torch.zeros((), device=self.gpu) if self.guide is None else T.guide_latent_loss(self.guide, gt, out)
+            terms = U.rtod_pixel_loss(out, gt, rgb, sparse, plus=lat)
+        self.opt.zero_grad()
+        terms[0].backward()
+        self.opt.step()
+        return tuple(t.detach() for t in terms)
+
+    def train(self, steps, progress=None, before=None, after=None):
+        """`steps` iterations over the loader's epochs, going on after `progress`; returns ([(loss terms, draws)], progress).
+        before(k) / after(k): hooks around global step k (1-based)."""
+        epoch, first = (progress["epoch"], progress["i"] + 1) if progress else (0, 0)
+        k = progress["step"] if progress else 0
+        rec, todo = [], steps
+        while True:
+            for i, batch in enumerate(self.loader, first):
+                k += 1
+                if before is not None:
+                    before(k)
+                terms = self.step(*batch)
+                rec.append(([t.clone() for t in terms], list(self.loader.last_params)))
+                if after is not None:
+                    after(k)
+                todo -= 1
+                if todo == 0:
+                    return rec, {"epoch": epoch, "i": i, "lr": LR, "model_num": epoch, "seen": k * B, "step": k}
+            epoch, first = epoch + 1, 0
+
+    def flat(self):
+        (st,) = self.opt._flat.values()
+        return st
+
+
+def _same_records(got, want, what):
+    assert len(got) == len(want)
+    for k, ((ta, pa), (tb, pb)) in enumerate(zip(got, want)):
+        assert pa == pb, "%s: augmentation draws of record %d differ: %s / %s" % (what, k, pa, pb)
+        for j, (a, b) in enumerate(zip(ta, tb)):
+            assert torch.equal(a, b), "%s: loss term %d of record %d: %r / %r" % (what, j, k, float(a), float(b))
+
+
+def _same_state(a, b, what):
+    sa, sb = a.net.state_dict(), b.net.state_dict()
+    assert list(sa) == list(sb)
+    for key in sa:                                   # running statistics and num_batches_tracked included
+        assert torch.equal(sa[key], sb[key]), "%s: %s differs" % (what, key)
+    fa, fb = a.flat(), b.flat()
+    assert torch.equal(fa["m"], fb["m"]) and torch.equal(fa["v"], fb["v"]), what + ": Adam's flat moments differ"
+    assert fa["step"] == fb["step"] and fa["pstep"] is None and fb["pstep"] is None, (what, fa["step"], fb["step"])
+
+
+def _through_bytes(state):
+    buf = io.BytesIO()
+    torch.save(state, buf)
+    buf.seek(0)
+    return torch.load(buf, map_location="cpu", weights_only=True)
+
+
+def _stop_and_resume(gpu, mode, dtype="fp32", serialise=False, stale_shadows=False):
+    from gdn_amd import trainer as T
+    straight = Run(gpu, mode, 7, dtype)
+    want, _ = straight.train(6)
+    first = Run(gpu, mode, 7, dtype)
+    got, progress = first.train(3)
+    assert progress["epoch"] == 1 and progress["i"] == 0          # mid-epoch
+    state = T.training_state(first.net, first.opt, first.loader, progress)
+    assert not any(k.startswith("module.") for k in state["model"]) and len(state["optimizer"]["state"]) == len(list(first.net.parameters()))
+    if serialise:
+        state = _through_bytes(state)
+    second = Run(gpu, mode, 8, dtype)                              # other weights: a load that restores nothing cannot pass
+    if stale_shadows:
+        with torch.no_grad():
+            # (the loader's streams move; the load puts them back) -- bf16 shadows of seed 8's weights exist from here on
+            second.net(next(iter(second.loader))[0 if mode == "DtoD" else 1], istrain=False)
+            for p in second.net.parameters():
+                p.fill_(float("nan"))
+    restored = T.load_training_state(state, second.net, second.opt, second.loader)
+    assert restored == progress
+    rest, end = second.train(3, restored)
+    assert end["epoch"] == 2 and end["i"] == 1 and end["step"] == 6
+    _same_records(got + rest, want, mode)
+    _same_state(straight, second, mode)
+    return straight, first, second
+
+
+def test_resume_dtod_is_bit_identical(gpu):
+    """1: DtoD, fp32, eager; the state goes through torch.save / torch.load(weights_only=True) in memory."""
+    _stop_and_resume(gpu, "DtoD", serialise=True)
+
+
+@pytest.mark.parametrize("mode", ["RtoD_single", "RtoD"])
+def test_resume_rtod_is_bit_identical(gpu, mode):
+    """2: RtoD_single on the legacy AutoEncoder; RtoD (AutoEncoder_2) with a frozen guide that is not part of the state."""
+    _stop_and_resume(gpu, mode)
+
+
+def test_resume_bf16_rebuilds_the_weight_shadows(gpu):
+    """3: compute_dtype('bf16').  The fresh model has run a forward (its bf16 shadows hold ITS weights) and its weights are
+    poisoned before the load: the first forward afterwards must see shadows rebuilt from the restored master weights."""
+    _stop_and_resume(gpu, "DtoD", dtype="bf16", stale_shadows=True)
+
+
+def test_resume_capturable_adam_and_graphed_step(gpu):
+    """4: Adam(capturable=True).  Eager 6 = 3 + 3; the device step state ({beta1^t, beta2^t, t, ...}: repeated products
+    made on the device) is saved and restored byte for byte; and a GraphedTrainStep(warmup=1) built after a restore makes
+    steps 4 (its warm-up) and 5 (its first replay) of the uninterrupted run."""
+    from gdn_amd import trainer as T
+    from gdn_amd.graph import GraphedTrainStep
+    snaps = {}
+    straight = Run(gpu, "DtoD", 7, capturable=True)
+
+    def snap(k):
+        snaps[k] = ({key: v.clone() for key, v in straight.net.state_dict().items()}, straight.flat()["state"].clone())
+
+    want, _ = straight.train(6, after=snap)
+    first = Run(gpu, "DtoD", 7, capturable=True)
+    got, progress = first.train(3)
+    state = T.training_state(first.net, first.opt, first.loader, progress)
+    (rec,) = state["optimizer"]["gdn"]["stores"]
+    assert rec["state"].dtype == torch.uint8 and bytes(rec["state"].tolist()) == bytes(snaps[3][1].cpu().tolist())
+    assert float(state["optimizer"]["state"][0]["step"]) == 3.0
+    second = Run(gpu, "DtoD", 8, capturable=True)
+    rest, _ = second.train(3, T.load_training_state(state, second.net, second.opt, second.loader))
+    _same_records(got + rest, want, "capturable")
+    _same_state(straight, second, "capturable")
+    assert torch.equal(second.flat()["state"], straight.flat()["state"])
+    # --- restore again, then capture ---
+    third = Run(gpu, "DtoD", 9, capturable=True)
+    T.load_training_state(state, third.net, third.opt, third.loader)
+    b4 = next(iter(third.loader))                      # the second batch of epoch 2: step 4
+    run = GraphedTrainStep(third.step, b4, third.opt, warmup=1)
+    assert third.loader.last_params == want[3][1]
+    for key, v in snaps[4][0].items():
+        assert torch.equal(third.net.state_dict()[key], v), "after the warm-up step: " + key
+    assert torch.equal(third.flat()["state"], snaps[4][1])
+    b5 = next(iter(third.loader))                      # epoch 3 begins: step 5
+    terms = run(*b5)
+    assert third.loader.last_params == want[4][1]
+    for a, b in zip(terms, want[4][0]):
+        assert torch.equal(a, b), (float(a), float(b))
+    for key, v in snaps[5][0].items():
+        assert torch.equal(third.net.state_dict()[key], v), "after the first replay: " + key
+    assert torch.equal(third.flat()["state"], snaps[5][1])
+
+
+def test_resume_with_partial_coverage(gpu):
+    """5: one sub-module is frozen for step 2, so the arena's store keeps per-parameter step counts from then on; they are
+    saved after step 3 and the resumed run equals the uninterrupted one after step 6."""
+    from gdn_amd import trainer as T
+
+    def freeze(run):
+        return lambda k: run.net.res512_3.requires_grad_(k != 2)
+
+    straight = Run(gpu, "DtoD", 7)
+    want, _ = straight.train(6, before=freeze(straight))
+    counts = sorted(set(straight.flat()["pstep"].values()))
+    assert counts == [5, 6]
+    first = Run(gpu, "DtoD", 7)
+    got, progress = first.train(3, before=freeze(first))
+    state = T.training_state(first.net, first.opt, first.loader, progress)
+    assert sorted({int(s["step"]) for s in state["optimizer"]["state"].values()}) == [2, 3]
+    second = Run(gpu, "DtoD", 8)
+    rest, _ = second.train(3, T.load_training_state(state, second.net, second.opt, second.loader), before=freeze(second))
+    _same_records(got + rest, want, "partial coverage")
+    sa, sb = straight.net.state_dict(), second.net.state_dict()
+    for key in sa:
+        assert torch.equal(sa[key], sb[key]), key
+    fa, fb = straight.flat(), second.flat()
+    assert torch.equal(fa["m"], fb["m"]) and torch.equal(fa["v"], fb["v"])
+    names = {id(p): n for n, p in straight.net.named_parameters()}
+    names2 = {n: id(p) for n, p in second.net.named_parameters()}
+    assert {n: fa["pstep"][i] for i, n in names.items()} == {n: fb["pstep"][i] for n, i in names2.items()}
+
+
+def _three_steps_recording(gpu):
+    """A DtoD run after three steps, with the float64 first moment of one convolution weight accumulated IN LOGICAL ORDER from
+    the gradients the optimizer saw: (run, name, weight, m64, G = max|g + wd p|)."""
+    run = Run(gpu, "DtoD", 7)
+    name, w = next((n, p) for n, p in run.net.named_parameters() if p.dim() == 4 and p.shape[0] != p.shape[1])
+    m64 = torch.zeros(w.shape, dtype=torch.float64)
+    seen = {"G": 0.0}
+
+    def before(k):
+        seen["p"] = w.detach().cpu().double().contiguous()
+
+    real_step = run.opt.step
+
+    def recording_step():
+        g = w.grad.detach().cpu().double().contiguous() + WD * seen["p"]
+        seen["G"] = max(seen["G"], float(g.abs().max()))
+        m64.mul_(BETAS[0]).add_(g, alpha=1 - BETAS[0])
+        return real_step()
+
+    run.opt.step = recording_step
+    run.train(3, before=before)
+    run.opt.step = real_step
+    return run, name, w, m64, seen["G"]
+
+
+def test_exported_moment_has_the_logical_layout(gpu):
+    """6, layout: the exported exp_avg of a convolution weight has the parameter's logical shape, is contiguous and matches
+    a moment accumulated in float64 in logical order from the recorded gradients.  Bound: three updates
+    m = b1 m + (1 - b1)(g + wd p) in fp32 are at most 4 roundings each of relative 2^-24 on terms no larger than
+    G = max|g + wd p|, so |m - m64| <= 12 * 6e-8 * G < 1e-6 * G; a layout mix-up is off by O(|m|)."""
+    run, name, w, m64, G = _three_steps_recording(gpu)
+    sd = run.opt.state_dict()
+    index = [n for n, _ in run.net.named_parameters()].index(name)
+    exp_avg = sd["state"][index]["exp_avg"]
+    assert exp_avg.shape == w.shape and exp_avg.is_contiguous()
+    assert float(sd["state"][index]["step"]) == 3.0 and sd["param_groups"][0]["params"] == list(range(len(sd["state"])))
+    err = float((exp_avg.cpu().double() - m64).abs().max())
+    print("exp_avg of %s %s: max |m - m64| = %.3e, bound %.3e, max|m64| = %.3e" % (name, tuple(w.shape), err, 1e-6 * G, float(m64.abs().max())))
+    assert err <= 1e-6 * G
+
+
+def test_optimizer_state_interop_with_torch_adam(gpu):
+    """6, exchange: after three steps opt.state_dict() loads into torch.optim.Adam over a CPU copy of the parameters; one
+    further step on each side, same gradients, is compared at test_adam_matches_oracle's bar, per parameter tensor
+    (|got - ref| <= 1e-7 * max|ref| + 1e-6 * |ref|); then a torch state loads into a new optim.Adam and a step is compared
+    the same way.
+
+    The kernels take the betas as float32, and 1 - float32(0.999) is 1.29e-5 below 0.001: moments handed to an optimizer that
+    goes on with beta2 = 0.999 exactly move the next update by 4.8e-6 of itself -- 9.9e-10 at lr = 2e-4, outside this bar
+    on every BatchNorm bias (parameters a few updates large; measured).  So state_dict() states the betas the moments were
+    accumulated with, the float32-rounded ones, torch's load_state_dict() takes them over, and both sides continue the same
+    Adam run."""
+    from gdn_amd import utils as U
+    from gdn_amd.optim import Adam
+    run = Run(gpu, "DtoD", 7)
+    run.train(3)
+    sd = run.opt.state_dict()
+    assert sd["param_groups"][0]["betas"] == (float(torch.tensor(0.9)), float(torch.tensor(0.999)))
+
+    def cpu(x):
+        return {k: cpu(v) for k, v in x.items()} if isinstance(x, dict) else (x.detach().cpu() if torch.is_tensor(x) else x)
+
+    ref = {n: p.detach().cpu().clone().contiguous().requires_grad_(True) for n, p in run.net.named_parameters()}
+    ropt = torch.optim.Adam(list(ref.values()), LR, BETAS, eps=1e-8, weight_decay=WD)
+    ropt.load_state_dict(cpu(sd))                      # (torch ignores the 'gdn' key)
+    it = iter(run.loader)
+    misses = []
+
+    def both_step(opt, what):
+        gt, rgb, sparse = next(it)
+        loss = U.dtod_loss(run.net(gt, istrain=False), gt, sparse)[0]
+        opt.zero_grad()
+        loss.backward()
+        for n, p in run.net.named_parameters():
+            ref[n].grad = p.grad.detach().cpu().clone().contiguous()
+        opt.step()
+        ropt.step()
+        for n, p in run.net.named_parameters():
+            try:
+                close(p, ref[n], rtol=1e-6, atol_scale=1e-7, what="%s: %s" % (what, n))
+            except AssertionError as e:
+                misses.append(str(e).splitlines()[0])
+
+    both_step(run.opt, "optim.Adam state in torch.optim.Adam")
+    back = Adam(run.net.parameters(), 1e-3)            # (lr and betas come from the checkpoint)
+    back.load_state_dict(ropt.state_dict())
+    assert back.param_groups[0]["lr"] == LR
+    with torch.no_grad():
+        for n, p in run.net.named_parameters():
+            p.copy_(ref[n])                             # the same starting point
+    both_step(back, "torch.optim.Adam state in optim.Adam")
+    (st,) = back._flat.values()
+    assert st["step"] == 5 and st["pstep"] is None
+    print("\n".join(["%d parameter tensors miss the bar:" % len(misses)] + misses))
+    assert not misses, "%d parameter tensors miss the bar, first: %s" % (len(misses), misses[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _cli(cwd, argv, limit=300):
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.pathsep.join([str(REPO / "gdn-pytorch_amd"), str(REPO)] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+    cwd.mkdir(parents=True, exist_ok=True)
+    cmd = ["timeout", "-k", "10", str(limit), sys.executable, "-m", "gdn_amd.GDN_main", *argv]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(cwd), timeout=limit + 60)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    return r.stdout
+
+
+def test_cli_resume_ends_like_the_uninterrupted_run(gpu, tmp_path):
+    """7: three epochs of two steps from the command line; a second run stopped after two epochs leaves the state written at
+    step 3 (--save_state_every 3); --resume of that file in a third directory ends with the same .pkl files, loss digits in
+    the names included, and equal tensors.  One fresh child process per run; two state files reach the disk."""
+    base = ["synthetic", "--synthetic", "--augment", "--mode", "DtoD", "--height", str(H), "--width", str(W), "--batch_size", "2",
+            "--epoch_size", "2", "--gpu_num", "0", "--save_state_every", "3"]
+    _cli(tmp_path / "a", base + ["--epochs", "3"])
+    _cli(tmp_path / "stopped", base + ["--epochs", "2"])
+    states = sorted((tmp_path / "stopped").rglob("train_state.pt"))
+    assert len(states) == 1 and len(sorted((tmp_path / "a").rglob("train_state.pt"))) == 1
+    assert not list(tmp_path.rglob("train_state.pt.tmp*"))
+    head = torch.load(states[0], map_location="cpu", weights_only=True)
+    assert (head["step"], head["epoch"], head["i"], head["model_num"]) == (3, 1, 0, 1)
+    del head
+    out = _cli(tmp_path / "b", base[:-2] + ["--epochs", "3", "--resume", str(states[0])])
+    assert "=> resumed AutoEncoder_DtoD" in out and not list((tmp_path / "b").rglob("train_state.pt"))
+    a = {p.name: p for p in (tmp_path / "a").rglob("*.pkl")}
+    b = {p.name: p for p in (tmp_path / "b").rglob("*.pkl")}
+    assert len(a) == 3 and sorted(b) == sorted(a)[1:], (sorted(a), sorted(b))      # epochs 2 and 3, same names
+    for name in b:
+        ta, tb = torch.load(a[name], map_location="cpu"), torch.load(b[name], map_location="cpu")
+        assert list(ta) == list(tb)
+        for key in ta:
+            assert torch.equal(ta[key], tb[key]), (name, key)
