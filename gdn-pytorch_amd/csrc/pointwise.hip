@@ -567,17 +567,19 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // Capturable Adam: the step counter and the running powers beta^t live in device memory, so a captured training step
 // advances them on every replay.  state = { double beta1^t, double beta2^t, int32 t, float bc1, float bc2s }.
 struct AdamDevState { double p1, p2; int step; float bc1, bc2s; };
-__global__ void adam_prep_kernel(AdamDevState* st, const float* __restrict__ hyper) {
+__device__ __forceinline__ void adam_advance(AdamDevState* st, const float* __restrict__ hyper) {
     st->step += 1;
     st->p1 *= (double)hyper[1];
     st->p2 *= (double)hyper[2];
     st->bc1 = (float)(1.0 - st->p1);
     st->bc2s = (float)sqrt(1.0 - st->p2);
 }
-__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                       const float* __restrict__ hyper, const AdamDevState* st) {
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
+__global__ void adam_prep_kernel(AdamDevState* st, const float* __restrict__ hyper) { adam_advance(st, hyper); }
+// the update of both capturable kernels: `gscale` is hyper[5] (adam_dev_kernel) or hyper[5] * coef (adam_dev_guarded_kernel)
+__device__ __forceinline__ void adam_dev_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
+                                                const AdamDevState* st, float gscale) {
+    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
     const float step = lr / st->bc1, bc2s = st->bc2s;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float pi = p[i];
@@ -587,6 +589,91 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
         m[i] = mi; v[i] = vi;
         p[i] = pi - step * mi / (sqrtf(vi) / bc2s + eps);
     }
+}
+__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       const float* __restrict__ hyper, const AdamDevState* st) {
+    adam_dev_update(p, g, m, v, n, hyper, st, hyper[5]);
+}
+
+// ---- gradient guard: global gradient norm, clipping coefficient and the decision to skip a non-finite step, all in device
+// memory (capturable; no host read).  The record (include/gdn_hip.h) is written with ordinary stores by single threads.
+struct AdamGuard { double sumsq; float norm, coef; int skip, steps, clipped, skipped; };
+static_assert(sizeof(AdamGuard) == 32, "guard record layout is part of the C ABI");
+
+// blocks of the partial-sum launch: a function of n alone, so the order of every addition is too
+constexpr int GRADNORM_MAX_BLOCKS = 1024;
+inline int gradnorm_blocks(int64_t n) { return stream_blocks(cdiv64(n, 16), 256, GRADNORM_MAX_BLOCKS); }
+
+__device__ __forceinline__ double sq4_d(f32x4 a) {
+    const double x = (double)a.x, y = (double)a.y, z = (double)a.z, w = (double)a.w;       // 1e30f squared fits a double
+    return (x * x + y * y) + (z * z + w * w);
+}
+// stage 1: partial[b] = sum of squares of block b's share.  Up to 3 head elements bring the body to a 16-byte boundary
+// (ar.grad[o:o+n] slices and loose parameters start anywhere); the body is read as float4, 4 loads in flight per lane;
+// head and tail (< 4 elements each) go to lanes of block 0.  Per-lane partials -> xor-butterfly over the 64 lanes -> the
+// block's 4 waves through LDS -> one double per block: no atomics, no ticket, the same additions in the same order every run.
+__global__ __launch_bounds__(256) void adam_gradnorm_partial_kernel(const float* __restrict__ g, int64_t n,
+                                                                   double* __restrict__ partial) {
+    __shared__ double sh[4];
+    int64_t head = (int64_t)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
+    if (head > n) head = n;
+    const int64_t nvec = (n - head) >> 2, tail0 = head + nvec * 4;
+    const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
+    const int64_t T = (int64_t)gridDim.x * 256;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int64_t i = blockIdx.x * 256ll + threadIdx.x;
+    for (; i + 3 * T < nvec; i += 4 * T) {
+        const f32x4 x0 = gv[i], x1 = gv[i + T], x2 = gv[i + 2 * T], x3 = gv[i + 3 * T];
+        a0 += sq4_d(x0); a1 += sq4_d(x1); a2 += sq4_d(x2); a3 += sq4_d(x3);
+    }
+    for (; i < nvec; i += T) a0 += sq4_d(gv[i]);
+    if (blockIdx.x == 0) {
+        const int64_t t = threadIdx.x;
+        if (t < head) { const double x = (double)g[t]; a1 += x * x; }
+        if (t >= 64 && tail0 + (t - 64) < n) { const double x = (double)g[tail0 + (t - 64)]; a2 += x * x; }
+    }
+    const double s = block_sum_d256((a0 + a1) + (a2 + a3), sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+// stage 2 (one block): lane t adds partial[t], partial[t + 256], ... in index order, then the same block reduction
+__global__ __launch_bounds__(256) void adam_gradnorm_final_kernel(const double* __restrict__ partial, int nb, AdamGuard* guard,
+                                                                 int accumulate) {
+    __shared__ double sh[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) a += partial[i];
+    const double s = block_sum_d256(a, sh);
+    if (threadIdx.x == 0) guard->sumsq = accumulate ? guard->sumsq + s : s;
+}
+// the decision: norm of the gradient as Adam sees it (after grad_scale), torch.nn.utils.clip_grad_norm_'s coefficient, skip
+__global__ void adam_guard_finalize_kernel(AdamGuard* guard, const float* __restrict__ hyper, double max_norm, int skip_nonfinite) {
+    const double norm = sqrt(guard->sumsq) * fabs((double)hyper[5]);
+    const bool finite = isfinite(norm);
+    double coef = 1.0;
+    int skip = 0;
+    if (finite) {
+        if (max_norm > 0.0) coef = fmin(1.0, max_norm / (norm + 1e-6));
+    } else if (skip_nonfinite) {
+        skip = 1;
+        coef = 0.0;
+    }
+    const float coef32 = (float)coef;
+    guard->norm = (float)norm;
+    guard->coef = coef32;
+    guard->skip = skip;
+    guard->steps += 1;
+    if (coef32 < 1.f && !skip) guard->clipped += 1;
+    guard->skipped += skip;
+}
+__global__ void adam_prep_guarded_kernel(AdamDevState* st, const float* __restrict__ hyper, const AdamGuard* guard) {
+    if (guard->skip == 0) adam_advance(st, hyper);       // a skipped step takes no place in the bias corrections
+}
+__global__ __launch_bounds__(256) void adam_dev_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                               const float* __restrict__ hyper, const AdamDevState* st,
+                                                               const AdamGuard* guard) {
+    if (guard->skip != 0) return;                        // p, m, v are neither read nor written
+    adam_dev_update(p, g, m, v, n, hyper, st, hyper[5] * guard->coef);
 }
 
 }  // namespace
@@ -890,6 +977,38 @@ extern "C" int gdn_adam_step_dev(float* p, const float* g, float* m, float* v, i
     hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, ST(stream), (AdamDevState*)state, hyper);
     hipLaunchKernelGGL(adam_dev_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n, hyper,
                        (const AdamDevState*)state);
+    return gdn_launch_status();
+}
+
+extern "C" size_t gdn_grad_sumsq_workspace_bytes(int64_t n) {
+    return n > 0 ? (size_t)gradnorm_blocks(n) * sizeof(double) : 0;
+}
+extern "C" int gdn_grad_sumsq(const float* g, int64_t n, void* guard, int32_t accumulate, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!g || n <= 0 || !guard || ((uintptr_t)g & 3) || ((uintptr_t)guard & 7) || ((uintptr_t)workspace & 7)) return GDN_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < gdn_grad_sumsq_workspace_bytes(n)) return GDN_ERR_WORKSPACE;
+    const int nb = gradnorm_blocks(n);
+    hipLaunchKernelGGL(adam_gradnorm_partial_kernel, dim3(nb), dim3(256), 0, ST(stream), g, n, (double*)workspace);
+    hipLaunchKernelGGL(adam_gradnorm_final_kernel, dim3(1), dim3(256), 0, ST(stream), (const double*)workspace, nb,
+                       (AdamGuard*)guard, accumulate);
+    return gdn_launch_status();
+}
+extern "C" int gdn_grad_guard_finalize(void* guard, const float* hyper, double max_norm, int32_t skip_nonfinite, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!guard || !hyper || ((uintptr_t)guard & 7) || max_norm != max_norm) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(adam_guard_finalize_kernel, dim3(1), dim3(1), 0, ST(stream), (AdamGuard*)guard, hyper, max_norm,
+                       skip_nonfinite ? 1 : 0);
+    return gdn_launch_status();
+}
+extern "C" int gdn_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                                         void* state, const void* guard, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !g || !m || !v || n <= 0 || !hyper || !state || !guard) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(adam_prep_guarded_kernel, dim3(1), dim3(1), 0, ST(stream), (AdamDevState*)state, hyper,
+                       (const AdamGuard*)guard);
+    hipLaunchKernelGGL(adam_dev_guarded_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n,
+                       hyper, (const AdamDevState*)state, (const AdamGuard*)guard);
     return gdn_launch_status();
 }
 

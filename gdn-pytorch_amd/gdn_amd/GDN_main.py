@@ -28,6 +28,10 @@ legacy AutoEncoder for RtoD_test, as ever), so a checkpoint either mode trains c
 GDN_RtoD_pretrained.pkl: ``--mode RtoD --rtod_arch legacy --init_from GDN_RtoD_pretrained.pkl``).
 ``--save_state`` / ``--save_state_every N`` write the rolling ``<save_dir>/train_state.pt`` (weights, optimizer, loader and
 schedule state); ``--resume PATH`` with the otherwise unchanged command line continues that run bit for bit.
+``--clip_grad_norm X`` clips the global gradient norm and ``--skip_nonfinite`` drops a step whose gradient holds a NaN or an
+Inf, both decided on the device inside the fused Adam (no sync, no torch kernel); the progress prints report the norm, the
+coefficient and the counts.  The guard protects weights, moments and the step count -- a forward that was itself
+non-finite has already written its BatchNorm running statistics.
 """
 import os
 import sys
@@ -46,7 +50,13 @@ TEST_MODES = ('DtoD_test', 'RtoD_test')
 
 
 def _make_optimizer(model, args):
-    return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4)
+    """The reference's Adam; --clip_grad_norm / --skip_nonfinite add the device-side gradient guard (optim.Adam)."""
+    guard = {}
+    if getattr(args, "clip_grad_norm", 0.0) > 0.0:
+        guard["max_grad_norm"] = float(args.clip_grad_norm)
+    if getattr(args, "skip_nonfinite", False):
+        guard["skip_nonfinite"] = True
+    return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
 
 
 def _rtod_network(args, H, W):

@@ -6,7 +6,7 @@ fails, the product path raises.
 import ctypes
 import os
 import pathlib
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _PKG = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get("GDN_HIP_LIB", _PKG.parent / "lib" / "libgdn_hip.so"))
@@ -131,6 +131,10 @@ _SIGS = {
     "gdn_spline_rotate3": (c_int32, [_P, _i32, _i32, _i32, _i32, _P, _P, _i32, _P, _P, _sz, _P]),
     "gdn_adam_step": (c_int32, [_P, _P, _P, _P, _i64, _f, _f, _f, _f, _f, _i32, _f, _P]),
     "gdn_adam_step_dev": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P]),
+    "gdn_grad_sumsq_workspace_bytes": (_sz, [_i64]),
+    "gdn_grad_sumsq": (c_int32, [_P, _i64, _P, _i32, _P, _sz, _P]),
+    "gdn_grad_guard_finalize": (c_int32, [_P, _P, c_double, _i32, _P]),
+    "gdn_adam_step_dev_guarded": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),

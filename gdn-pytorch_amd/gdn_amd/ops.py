@@ -1246,3 +1246,23 @@ def spline_rotate(src, angle=None, matrix=None, offset=None, clip=True):
 def adam_step_dev(p, g, m, v, hyper, state):
     """Capturable Adam: hyper float32[6] and state uint8[32] live on the device (see gdn_adam_step_dev)."""
     lib.gdn_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), stream())
+
+
+def grad_sumsq(g, guard, accumulate=False):
+    """guard.sumsq (+)= sum of squares of the float32 buffer `g` in double, in a fixed order (see gdn_grad_sumsq); guard is
+    the 32-byte device record of the gradient guard."""
+    n = g.numel()
+    nb = int(lib.gdn_grad_sumsq_workspace_bytes(n))
+    ws = workspace(nb, g.device, "gradnorm")
+    lib.gdn_grad_sumsq(_p(g), n, _p(guard), 1 if accumulate else 0, _p(ws), nb, stream())
+
+
+def grad_guard_finalize(guard, hyper, max_norm=0.0, skip_nonfinite=False):
+    """Norm, clipping coefficient, skip decision and counters of the guard record from its sumsq (gdn_grad_guard_finalize);
+    max_norm <= 0: no clipping."""
+    lib.gdn_grad_guard_finalize(_p(guard), _p(hyper), float(max_norm), 1 if skip_nonfinite else 0, stream())
+
+
+def adam_step_dev_guarded(p, g, m, v, hyper, state, guard):
+    """adam_step_dev under the guard record's coefficient and skip decision (gdn_adam_step_dev_guarded)."""
+    lib.gdn_adam_step_dev_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), _p(guard), stream())

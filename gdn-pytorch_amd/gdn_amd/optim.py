@@ -4,22 +4,50 @@ Same update rule as the reference's ``optim.Adam(model.parameters(), lr,
 [momentum, beta], eps=1e-08, weight_decay=5e-4)`` (GDN_main.py:157,173:
 coupled L2 weight decay on every parameter, BN affine included), executed as
 ONE kernel launch over the arena instead of 124-136 per-tensor launches.
+
+Gradient guard (``max_grad_norm`` / ``skip_nonfinite``): the global gradient norm, ``clip_grad_norm_``'s coefficient and the
+decision to skip a step whose gradient holds a NaN or an Inf are taken on the device, in one 32-byte record the update
+kernel reads -- no torch kernel, no host read, capturable.
 """
+import struct
+
 import torch
 
 from . import ops
 from ._lib import GdnError
 
 
+_GUARD_FMT = "<dffiiii"      # gdn_hip.h: { double sumsq; float norm, coef; int32 skip, steps, clipped, skipped; }
+
+
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+    """Fused Adam.  max_grad_norm (positive) clips the global gradient norm -- over every parameter of every group that
+    has a gradient, after grad_scale, torch.nn.utils.clip_grad_norm_'s formula; skip_nonfinite leaves parameters, moments
+    and the step count untouched by a step whose gradient holds a NaN or an Inf.  Clipping alone does not change what a
+    non-finite gradient does: without skip_nonfinite such a step is applied exactly as an unguarded one would apply it.
+    Either option makes the optimizer a CAPTURABLE one (capturable=True is implied): a skipped step must not advance the
+    step count and the host must not read the device to find out, so the count has to live on the device.  Both options
+    are launch arguments: a captured graph holds the values of its capture, changing them afterwards needs a new capture.
+    The guard protects parameters, moments and the step count; a forward that was itself non-finite has already written its
+    BatchNorm running statistics."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
+                 max_grad_norm=None, skip_nonfinite=False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping), got %r" % (max_grad_norm,))
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._flat = {}        # id(arena) -> {"m","v","step"}
         self.grad_scale = 1.0  # set to 1/world_size by the data-parallel wrapper
         # capturable: the step counter, beta^t and the hyper-parameters live in device memory (gdn_adam_step_dev), so
         # step() can be captured in a hipGraph and replayed; call refresh_hyper() after changing lr outside a capture
-        self.capturable = bool(capturable)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self.capturable = bool(capturable) or self.guarded
+        # guarded: step() gathers its launches in _work, then runs the norm pass, the decision and the updates; _guard is
+        # the device record (made by the first step), _guard_counts what load_state_dict() read for it before it existed
+        self._work, self._guard, self._guard_counts = None, None, None
         # load_state_dict() parks what it read here until the store it belongs to exists (the arena is built by the first
         # forward, the stores by the first step): id(param) -> {"step","m","v"} in LOGICAL layout, and the device step state
         # of the capturable path per store, keyed by the store's first parameter
@@ -80,10 +108,57 @@ class Adam(torch.optim.Optimizer):
         if self.capturable:
             self._ensure_dev(st, group, device, st["step"] - 1)      # (step() has counted this update already)
             st["full_dev"] = True         # the store's device counter has taken every update so far: a valid thing to copy
-            ops.adam_step_dev(pdata, grad, st["m"], st["v"], st["hyper"], st["state"])
+            self._launch_dev(pdata, grad, st["m"], st["v"], st["hyper"], st["state"])
         else:
             ops.adam_step(pdata, grad, st["m"], st["v"], group["lr"], b1, b2, group["eps"], group["weight_decay"],
                           st["step"], self.grad_scale)
+
+    def _launch_dev(self, pdata, grad, m, v, hyper, state):
+        """One capturable update: launched now, or -- guarded -- gathered until the norm of ALL gradients is known."""
+        if self._work is None:
+            ops.adam_step_dev(pdata, grad, m, v, hyper, state)
+        else:
+            self._work.append((pdata, grad, m, v, hyper, state))
+
+    def _guard_record(self, device):
+        if self._guard is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise GdnError("guarded Adam: the guard record would be created (and reset by every replay) inside a graph "
+                               "capture; run one eager step first")
+            steps, clipped, skipped = self._guard_counts or (0, 0, 0)
+            raw = struct.pack(_GUARD_FMT, 0.0, 0.0, 1.0, 0, steps, clipped, skipped)
+            self._guard = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+            self._guard_counts = None
+        elif self._guard.device != device:
+            raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (self._guard.device, device))
+        return self._guard
+
+    def _guarded_updates(self):
+        """The two passes of a guarded step over the gathered launches: sum of squares of every gradient into the record
+        and the decision; then every update under that decision."""
+        work, self._work = self._work, None
+        if not work:
+            return
+        guard = self._guard_record(work[0][0].device)
+        for k, w in enumerate(work):
+            if w[0].device != guard.device:
+                raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (guard.device, w[0].device))
+            ops.grad_sumsq(w[1], guard, accumulate=k > 0)
+        ops.grad_guard_finalize(guard, work[0][4], self.max_grad_norm or 0.0, self.skip_nonfinite)
+        for pdata, grad, m, v, hyper, state in work:
+            ops.adam_step_dev_guarded(pdata, grad, m, v, hyper, state, guard)
+
+    def guard_stats(self):
+        """{'norm', 'coef', 'steps', 'clipped', 'skipped'} of the guard: norm and coefficient of the last step, counts over
+        the run.  One small device-to-host copy, i.e. a sync: for print cadence, not for every step; not inside a capture."""
+        if not self.guarded:
+            raise GdnError("guard_stats(): this optimizer has no gradient guard (max_grad_norm / skip_nonfinite)")
+        self._refuse_capture("guard_stats()")
+        if self._guard is None:
+            steps, clipped, skipped = self._guard_counts or (0, 0, 0)
+            return {"norm": 0.0, "coef": 1.0, "steps": steps, "clipped": clipped, "skipped": skipped}
+        _, norm, coef, _, steps, clipped, skipped = struct.unpack(_GUARD_FMT, self._guard.cpu().numpy().tobytes())
+        return {"norm": norm, "coef": coef, "steps": steps, "clipped": clipped, "skipped": skipped}
 
     def _step_partial(self, ar, st, group):
         """Per-tensor updates ON SLICES OF THE FLAT MOMENTS for the parameters that have a gradient (torch.optim.Adam skips
@@ -122,7 +197,7 @@ class Adam(torch.optim.Optimizer):
                     else:
                         ds = self._dev_state(group, st["pstep"][id(p)] - 1, ar.device)
                     pdev[id(p)] = ds
-                ops.adam_step_dev(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], st["hyper"], ds)
+                self._launch_dev(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], st["hyper"], ds)
             else:
                 ops.adam_step(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], group["lr"], b1, b2, group["eps"],
                               group["weight_decay"], st["pstep"][id(p)], self.grad_scale)
@@ -140,6 +215,19 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if not self.guarded:
+            self._step_groups()
+            return loss
+        self._work = []
+        try:
+            self._step_groups()
+        except BaseException:
+            self._work = None
+            raise
+        self._guarded_updates()
+        return loss
+
+    def _step_groups(self):
         for group in self.param_groups:
             b1, b2 = group["betas"]
             arenas, loose = self._arena_groups(group)
@@ -190,7 +278,6 @@ class Adam(torch.optim.Optimizer):
                 self._apply(p.data, g, st, group, p.device)
                 if getattr(p, "_gdn_arena", None) is not None:
                     p._gdn_arena.touch()
-        return loss
 
     # ------------------------------------------------------------------------------------------------------------------
     # state exchange: torch.optim.Adam's format ({'state': {index: {'step','exp_avg','exp_avg_sq'}}, 'param_groups'}),
@@ -294,8 +381,12 @@ class Adam(torch.optim.Optimizer):
         for rec in self._pending_dev.values():
             recs.append(dict(rec, params=[index[i] for i in rec["params"]],
                              pdev={index[i]: t for i, t in rec["pdev"].items()}))
-        return {"state": dict(sorted(state.items())), "param_groups": groups,
-                "gdn": {"version": 1, "capturable": self.capturable, "grad_scale": float(self.grad_scale), "stores": recs}}
+        priv = {"version": 1, "capturable": self.capturable, "grad_scale": float(self.grad_scale), "stores": recs}
+        if self.guarded:
+            gs = self.guard_stats()
+            priv["guard"] = {"max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite,
+                             "steps": gs["steps"], "clipped": gs["clipped"], "skipped": gs["skipped"]}
+        return {"state": dict(sorted(state.items())), "param_groups": groups, "gdn": priv}
 
     def load_state_dict(self, state_dict):
         """Restore a state_dict() of this class or of torch.optim.Adam over the same parameters (count and shapes are
@@ -341,6 +432,13 @@ class Adam(torch.optim.Optimizer):
                 continue
             pending_dev[ids[0]] = dict(rec, params=ids, pdev={id(by_saved[i]): t for i, t in rec["pdev"].items()})
         self._pending, self._pending_dev = pending, pending_dev
+        if self.guarded and priv.get("guard") is not None:
+            # the run's counts go on; max_grad_norm / skip_nonfinite stay this optimizer's own (constructor arguments)
+            self._guard_counts = tuple(int(priv["guard"][k]) for k in ("steps", "clipped", "skipped"))
+            if self._guard is not None:
+                raw = struct.pack(_GUARD_FMT, 0.0, 0.0, 1.0, 0, *self._guard_counts)
+                self._guard.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+                self._guard_counts = None
         # stores that exist: rewrite them now; parameters without a saved state start over
         for kind, st, ar, ps in self._stores():
             if kind == "arena":

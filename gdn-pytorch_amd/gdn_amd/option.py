@@ -1,10 +1,17 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
---init_from, --save_state, --save_state_every, --resume).
+--init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
 import argparse
+
+
+def _non_negative_float(text):
+    v = float(text)
+    if not v >= 0.0:
+        raise argparse.ArgumentTypeError("%r is not a non-negative number" % (text,))
+    return v
 
 
 def build_parser():
@@ -78,6 +85,12 @@ def build_parser():
     p.add_argument('--resume', type=str, default=None, metavar='PATH',
                    help='DtoD / RtoD / RtoD_single: continue the run that wrote this train_state.pt, bit for bit as if it had '
                         'never stopped (same command line otherwise); a missing file is an error, and so is --init_from with it')
+    p.add_argument('--clip_grad_norm', type=_non_negative_float, default=0.0, metavar='X',
+                   help='training: clip the global gradient norm (all parameters, after the data-parallel mean) to X before '
+                        'the Adam update, on the device (torch.nn.utils.clip_grad_norm_\'s formula); 0 = off')
+    p.add_argument('--skip_nonfinite', action='store_true',
+                   help='training: a step whose gradient holds a NaN or an Inf leaves weights, Adam moments and the step '
+                        'count untouched (decided on the device, no sync); the progress prints count such steps')
     return p
 
 

@@ -184,6 +184,24 @@ def _decay_lr(optimizer, lr, fast_div):
     return lr
 
 
+def _guard_stats(optimizer):
+    """guard_stats() of an optimizer with a gradient guard (a device read: only where the loops print anyway), else None."""
+    return optimizer.guard_stats() if getattr(optimizer, "guarded", False) and _is_main() else None
+
+
+def _print_guard_progress(optimizer):
+    gs = _guard_stats(optimizer)
+    if gs is not None:
+        print("grad_norm: %.4f  clip_coef: %.4f  (clipped %d, skipped %d of %d steps)" %
+              (gs["norm"], gs["coef"], gs["clipped"], gs["skipped"], gs["steps"]))
+
+
+def _print_guard_epoch(optimizer):
+    gs = _guard_stats(optimizer)
+    if gs is not None:
+        print("grad guard: clipped %d, skipped %d of %d steps" % (gs["clipped"], gs["skipped"], gs["steps"]))
+
+
 def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_loader, val_loader, batch_size,
                   n_epochs, lr, logger, train_writer, progress=None):
     """Depth->depth auto-encoder training; loss = BerHu + 3*imgrad_loss (trainer.py:411-468).
@@ -226,6 +244,7 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
                 print("epoch: %d,  %d/%d" % (epoch + 1, i + 1, epoch_size))
                 print("total_loss: %5f, output_loss: %5f, gradient_loss: %5f  (%.1f img/s)" %
                       (loss.item(), output_loss.item(), gradient_loss.item(), seen / (time.time() - t0)))
+                _print_guard_progress(optimizer)
             if (i + 1) % 3000 == 0:
                 _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
                 model_num += 1
@@ -236,6 +255,7 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
         if loss is not None:
             if _is_main():
                 print('\n', 'epoch: ', epoch + 1, '  loss: ', loss.item())
+            _print_guard_epoch(optimizer)
             _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
             model_num += 1
             due = due or saver.on_checkpoint
@@ -351,6 +371,7 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
                 print("epoch: %d,  %d/%d" % (epoch + 1, i + 1, epoch_size))
                 print("total_loss: %5f, output_loss: %5f, smoothness_loss: %5f, latent_loss: %5f  (%.1f img/s)" %
                       (loss.item(), output_loss.item(), smooth.item(), latent.item(), seen / (time.time() - t0)))
+                _print_guard_progress(optimizer)
             if (i + 1) % 700 == 0:
                 _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
                 model_num += 1
@@ -358,6 +379,7 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
             if due and not saver.last_batch(i):
                 saver.save(epoch, i, lr, model_num, seen, gstep)
                 due = False
+        _print_guard_epoch(optimizer)
         if logger is not None and val_loader is not None:
             errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
             if _is_main():

@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 /* The GDN_HINT_* bits (below) this library acts on.  A binding that sets a bit that CHANGES WHAT IS COMPUTED (GDN_HINT_FLIP_TAPS)
@@ -701,6 +701,31 @@ int gdn_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
  * initialised to {1.0, 1.0, 0, 0, 0} and advanced by the call itself. */
 int gdn_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
                       const float* hyper, void* state, void* stream);
+
+/* Gradient guard of the capturable update: the global gradient norm, torch.nn.utils.clip_grad_norm_'s coefficient and the
+ * decision to skip a step whose gradient holds a NaN or an Inf, all taken on the device (no host read, capturable).
+ * guard = 32 bytes of device memory, 8-byte aligned, zero-initialised by the caller:
+ *   { double sumsq; float norm; float coef; int32 skip; int32 steps; int32 clipped; int32 skipped; }
+ *
+ * gdn_grad_sumsq: guard->sumsq = (accumulate ? guard->sumsq : 0) + sum g[i]^2 over n floats (any 4-byte aligned base, n >= 1).
+ *   Each element is squared and summed in double (1e30f does not overflow); a NaN or an Inf anywhere makes sumsq non-finite,
+ *   which IS the detection.  Two launches: per-block partial sums into `workspace` (gdn_grad_sumsq_workspace_bytes(n); the
+ *   grid is a function of n alone), then one block that adds them in a fixed order -- no floating-point atomics: the same
+ *   buffer at the same address gives the same bits every time.
+ * gdn_grad_guard_finalize (one launch, after the last gdn_grad_sumsq of a step; hyper as for gdn_adam_step_dev), in double:
+ *   norm = sqrt(sumsq) * |hyper[5]|, the norm of the gradient as the update sees it;
+ *   norm finite:      skip = 0, coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1;
+ *   norm not finite:  skip_nonfinite ? (skip = 1, coef = 0) : (skip = 0, coef = 1 -- clipping alone changes nothing there);
+ *   norm and coef are stored rounded once to float; steps += 1; clipped += (coef < 1 as stored, and not skipped);
+ *   skipped += skip.
+ * gdn_adam_step_dev_guarded: gdn_adam_step_dev with grad_scale * coef in the place of grad_scale (bit-identical to it for
+ *   coef == 1); with skip != 0 neither the step state nor p, m, v are touched. */
+size_t gdn_grad_sumsq_workspace_bytes(int64_t n);
+int gdn_grad_sumsq(const float* g, int64_t n, void* guard, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int gdn_grad_guard_finalize(void* guard, const float* hyper, double max_norm, int32_t skip_nonfinite, void* stream);
+int gdn_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n,
+                              const float* hyper, void* state, const void* guard, void* stream);
 
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
