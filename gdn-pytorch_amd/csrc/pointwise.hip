@@ -676,6 +676,68 @@ __global__ __launch_bounds__(256) void adam_dev_guarded_kernel(float* __restrict
     adam_dev_update(p, g, m, v, n, hyper, st, hyper[5] * guard->coef);
 }
 
+// ---- weight EMA and the in-place exchange of two float ranges (include/gdn_hip.h).  Pure streaming: the body moves 16 bytes per
+// lane, up to 3 head elements bring it to a 16-byte boundary and fewer than 4 tail elements follow it (lanes of block 0, as in
+// adam_gradnorm_partial_kernel); VEC = false is the scalar form for operands whose bases differ modulo 16.  No atomics, no LDS.
+// The head/body/tail split of `n` floats starting at `base`.
+struct StreamSplit { int64_t head, nvec, tail0; };
+__device__ __forceinline__ StreamSplit stream_split(const void* base, int64_t n) {
+    StreamSplit s;
+    s.head = (int64_t)((4u - (unsigned)(((uintptr_t)base >> 2) & 3u)) & 3u);
+    if (s.head > n) s.head = n;
+    s.nvec = (n - s.head) >> 2;
+    s.tail0 = s.head + s.nvec * 4;
+    return s;
+}
+__device__ __forceinline__ float ema1(float w, float p, float e) { return fmaf(w, p - e, e); }
+// e += w_t (p - e) with w_t = 1 - min(decay, (1 + t) / (10 + t)), t = the step count the Adam update of this store has just
+// advanced; every thread computes w_t itself, in double, rounded once.  A skipped step (guard->skip) reads and writes nothing.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n,
+                                                         double decay, const AdamDevState* st, const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;
+    const double t = (double)st->step;
+    const float w = (float)(1.0 - fmin(decay, (1.0 + t) / (10.0 + t)));
+    const int64_t T = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
+    if (!VEC) {
+        for (int64_t i = tid; i < n; i += T) e[i] = ema1(w, p[i], e[i]);
+        return;
+    }
+    const StreamSplit s = stream_split(e, n);
+    f32x4* __restrict__ ev = reinterpret_cast<f32x4*>(e + s.head);
+    const f32x4* __restrict__ pv = reinterpret_cast<const f32x4*>(p + s.head);
+    for (int64_t i = tid; i < s.nvec; i += T) {
+        const f32x4 x = pv[i];
+        f32x4 a = ev[i];
+        a.x = ema1(w, x.x, a.x); a.y = ema1(w, x.y, a.y); a.z = ema1(w, x.z, a.z); a.w = ema1(w, x.w, a.w);
+        ev[i] = a;
+    }
+    if (blockIdx.x == 0) {
+        const int64_t l = threadIdx.x;
+        if (l < s.head) e[l] = ema1(w, p[l], e[l]);
+        if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); e[i] = ema1(w, p[i], e[i]); }
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t T = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
+    if (!VEC) {
+        for (int64_t i = tid; i < n; i += T) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
+        return;
+    }
+    const StreamSplit s = stream_split(a, n);
+    f32x4* __restrict__ av = reinterpret_cast<f32x4*>(a + s.head);
+    f32x4* __restrict__ bv = reinterpret_cast<f32x4*>(b + s.head);
+    for (int64_t i = tid; i < s.nvec; i += T) { const f32x4 x = av[i]; av[i] = bv[i]; bv[i] = x; }
+    if (blockIdx.x == 0) {
+        const int64_t l = threadIdx.x;
+        if (l < s.head) { const float x = a[l]; a[l] = b[l]; b[l] = x; }
+        if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); const float x = a[i]; a[i] = b[i]; b[i] = x; }
+    }
+}
+// one lane per 16 bytes (VEC) or per float, capped like the Adam update's grid; the rest is grid-strided
+inline int stream_rw_blocks(int64_t n, bool vec) { return stream_blocks(vec ? cdiv64(n, 4) : n, 256, 4096); }
+
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
@@ -1009,6 +1071,28 @@ extern "C" int gdn_adam_step_dev_guarded(float* p, const float* g, float* m, flo
                        (const AdamGuard*)guard);
     hipLaunchKernelGGL(adam_dev_guarded_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n,
                        hyper, (const AdamDevState*)state, (const AdamGuard*)guard);
+    return gdn_launch_status();
+}
+
+extern "C" int gdn_ema_update(float* ema, const float* p, int64_t n, double decay, const void* state, const void* guard,
+                              void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!ema || !p || n <= 0 || !state || !(decay > 0.0 && decay < 1.0)) return GDN_ERR_BAD_ARG;
+    if (((uintptr_t)ema & 3) || ((uintptr_t)p & 3) || ((uintptr_t)state & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
+    const bool vec = (((uintptr_t)ema ^ (uintptr_t)p) & 15) == 0;
+    const auto kernel = vec ? ema_update_kernel<true> : ema_update_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), ema, p, n, decay,
+                       (const AdamDevState*)state, (const AdamGuard*)guard);
+    return gdn_launch_status();
+}
+extern "C" int gdn_swap_f32(float* a, float* b, int64_t n, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!a || !b || n <= 0 || ((uintptr_t)a & 3) || ((uintptr_t)b & 3)) return GDN_ERR_BAD_ARG;
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+    if (ua < ub + bytes && ub < ua + bytes) return GDN_ERR_BAD_ARG;       // overlapping ranges (a == b included)
+    const bool vec = (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0;
+    const auto kernel = vec ? swap_f32_kernel<true> : swap_f32_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), a, b, n);
     return gdn_launch_status();
 }
 

@@ -32,6 +32,9 @@ schedule state); ``--resume PATH`` with the otherwise unchanged command line con
 Inf, both decided on the device inside the fused Adam (no sync, no torch kernel); the progress prints report the norm, the
 coefficient and the counts.  The guard protects weights, moments and the step count -- a forward that was itself
 non-finite has already written its BatchNorm running statistics.
+``--ema_decay D`` keeps an exponential moving average of the weights inside the fused Adam: the per-epoch
+validation runs on the averaged weights and every ``X.pkl`` is followed by ``X_ema.pkl`` with them, in the same format.
+BatchNorm running statistics are buffers: the averaged model uses the live ones.
 """
 import os
 import sys
@@ -50,12 +53,15 @@ TEST_MODES = ('DtoD_test', 'RtoD_test')
 
 
 def _make_optimizer(model, args):
-    """The reference's Adam; --clip_grad_norm / --skip_nonfinite add the device-side gradient guard (optim.Adam)."""
+    """The reference's Adam; --clip_grad_norm / --skip_nonfinite add the device-side gradient guard, --ema_decay the
+    weight average (optim.Adam)."""
     guard = {}
     if getattr(args, "clip_grad_norm", 0.0) > 0.0:
         guard["max_grad_norm"] = float(args.clip_grad_norm)
     if getattr(args, "skip_nonfinite", False):
         guard["skip_nonfinite"] = True
+    if getattr(args, "ema_decay", 0.0) > 0.0:
+        guard["ema_decay"] = float(args.ema_decay)
     return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
 
 
@@ -90,6 +96,12 @@ def _check_resume(args):
         raise RuntimeError("--resume continues a training run; --mode %s trains nothing" % args.mode)
     if not os.path.isfile(path):
         raise FileNotFoundError("--resume %r: no such file" % (path,))
+
+
+def _check_ema(args):
+    """--ema_decay averages the weights of a training run; checked before anything touches the GPU."""
+    if getattr(args, "ema_decay", 0.0) > 0.0 and args.mode in TEST_MODES:
+        raise RuntimeError("--ema_decay averages the weights of a training run; --mode %s trains nothing" % args.mode)
 
 
 def _resume(args, model, opt, train_loader, rank):
@@ -154,6 +166,7 @@ def run(args, train_loader=None, val_loader=None):
     if train_loader is None:
         _check_dataset(args)
     _check_resume(args)
+    _check_ema(args)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num

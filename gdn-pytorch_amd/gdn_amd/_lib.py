@@ -135,6 +135,8 @@ _SIGS = {
     "gdn_grad_sumsq": (c_int32, [_P, _i64, _P, _i32, _P, _sz, _P]),
     "gdn_grad_guard_finalize": (c_int32, [_P, _P, c_double, _i32, _P]),
     "gdn_adam_step_dev_guarded": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P, _P]),
+    "gdn_ema_update": (c_int32, [_P, _P, _i64, c_double, _P, _P, _P]),
+    "gdn_swap_f32": (c_int32, [_P, _P, _i64, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),

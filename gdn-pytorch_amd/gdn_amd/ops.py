@@ -1266,3 +1266,15 @@ def grad_guard_finalize(guard, hyper, max_norm=0.0, skip_nonfinite=False):
 def adam_step_dev_guarded(p, g, m, v, hyper, state, guard):
     """adam_step_dev under the guard record's coefficient and skip decision (gdn_adam_step_dev_guarded)."""
     lib.gdn_adam_step_dev_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), _p(guard), stream())
+
+
+def ema_update(ema, p, decay, state, guard=None):
+    """ema += w_t (p - ema) with the warm-up weight of the step count in `state`, the device step state the Adam update of
+    the same store has just advanced; `guard` is the record a guarded update read (a skipped step leaves ema alone), None
+    after an unguarded one (gdn_ema_update)."""
+    lib.gdn_ema_update(_p(ema), _p(p), p.numel(), float(decay), _p(state), _p(guard), stream())
+
+
+def swap_(a, b):
+    """Exchange the contents of two non-overlapping dense float32 buffers in place (gdn_swap_f32)."""
+    lib.gdn_swap_f32(_p(a), _p(b), a.numel(), stream())

@@ -8,7 +8,12 @@ ONE kernel launch over the arena instead of 124-136 per-tensor launches.
 Gradient guard (``max_grad_norm`` / ``skip_nonfinite``): the global gradient norm, ``clip_grad_norm_``'s coefficient and the
 decision to skip a step whose gradient holds a NaN or an Inf are taken on the device, in one 32-byte record the update
 kernel reads -- no torch kernel, no host read, capturable.
+
+Weight average (``ema_decay``): an exponential moving average of the weights beside the moments, updated by one more launch
+after each update under the same skip decision, and exchanged with the weights in place for validation and for the
+checkpoint that is deployed.
 """
+import contextlib
 import struct
 
 import torch
@@ -20,6 +25,10 @@ from ._lib import GdnError
 _GUARD_FMT = "<dffiiii"      # gdn_hip.h: { double sumsq; float norm, coef; int32 skip, steps, clipped, skipped; }
 
 
+def _rank0():
+    return not (torch.distributed.is_available() and torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
+
+
 class Adam(torch.optim.Optimizer):
     """Fused Adam.  max_grad_norm (positive) clips the global gradient norm -- over every parameter of every group that
     has a gradient, after grad_scale, torch.nn.utils.clip_grad_norm_'s formula; skip_nonfinite leaves parameters, moments
@@ -29,12 +38,20 @@ class Adam(torch.optim.Optimizer):
     step count and the host must not read the device to find out, so the count has to live on the device.  Both options
     are launch arguments: a captured graph holds the values of its capture, changing them afterwards needs a new capture.
     The guard protects parameters, moments and the step count; a forward that was itself non-finite has already written its
-    BatchNorm running statistics."""
+    BatchNorm running statistics.
+
+    ema_decay (0 < d < 1) keeps an exponential moving average of the weights: avg += w_t (p - avg) after every APPLIED update
+    t = 1, 2, ... of a parameter, w_t = 1 - min(d, (1 + t) / (10 + t)) (the warm-up of timm's ModelEmaV2 / torch's
+    swa_utils), avg = p before the first update.  A step the guard skips leaves the average alone, a parameter without a
+    gradient keeps its own.  Like the guard it implies capturable=True (t is the device's step count).  swap_averaged() /
+    averaged_weights() exchange weights and averages in place; buffers (BatchNorm running statistics) are not averaged."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be positive (None: no clipping), got %r" % (max_grad_norm,))
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must lie in (0, 1) (None: no weight average), got %r" % (ema_decay,))
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._flat = {}        # id(arena) -> {"m","v","step"}
@@ -44,7 +61,8 @@ class Adam(torch.optim.Optimizer):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
-        self.capturable = bool(capturable) or self.guarded
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None
         # guarded: step() gathers its launches in _work, then runs the norm pass, the decision and the updates; _guard is
         # the device record (made by the first step), _guard_counts what load_state_dict() read for it before it existed
         self._work, self._guard, self._guard_counts = None, None, None
@@ -52,6 +70,10 @@ class Adam(torch.optim.Optimizer):
         # forward, the stores by the first step): id(param) -> {"step","m","v"} in LOGICAL layout, and the device step state
         # of the capturable path per store, keyed by the store's first parameter
         self._pending, self._pending_dev = {}, {}
+        # weight average: one flat buffer "ema" per state store beside m and v, made by the first step; _pending_ema is what
+        # load_state_dict() read for it (id(param) -> average in LOGICAL layout) until then; _swapped while the weights
+        # and the averages have changed places
+        self._pending_ema, self._swapped, self._ema_told = {}, False, False
 
     def refresh_hyper(self):
         """Push (lr, betas, eps, weight_decay, grad_scale) to the device buffers of the capturable path if they changed."""
@@ -108,17 +130,20 @@ class Adam(torch.optim.Optimizer):
         if self.capturable:
             self._ensure_dev(st, group, device, st["step"] - 1)      # (step() has counted this update already)
             st["full_dev"] = True         # the store's device counter has taken every update so far: a valid thing to copy
-            self._launch_dev(pdata, grad, st["m"], st["v"], st["hyper"], st["state"])
+            self._launch_dev(pdata, grad, st["m"], st["v"], st["hyper"], st["state"], st.get("ema"))
         else:
             ops.adam_step(pdata, grad, st["m"], st["v"], group["lr"], b1, b2, group["eps"], group["weight_decay"],
                           st["step"], self.grad_scale)
 
-    def _launch_dev(self, pdata, grad, m, v, hyper, state):
-        """One capturable update: launched now, or -- guarded -- gathered until the norm of ALL gradients is known."""
+    def _launch_dev(self, pdata, grad, m, v, hyper, state, ema=None):
+        """One capturable update: launched now, or -- guarded -- gathered until the norm of ALL gradients is known.  `ema`:
+        the slice of the weight average that belongs to `pdata`, updated right after it from the same step state."""
         if self._work is None:
             ops.adam_step_dev(pdata, grad, m, v, hyper, state)
+            if ema is not None:
+                ops.ema_update(ema, pdata, self.ema_decay, state)
         else:
-            self._work.append((pdata, grad, m, v, hyper, state))
+            self._work.append((pdata, grad, m, v, hyper, state, ema))
 
     def _guard_record(self, device):
         if self._guard is None:
@@ -145,8 +170,10 @@ class Adam(torch.optim.Optimizer):
                 raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (guard.device, w[0].device))
             ops.grad_sumsq(w[1], guard, accumulate=k > 0)
         ops.grad_guard_finalize(guard, work[0][4], self.max_grad_norm or 0.0, self.skip_nonfinite)
-        for pdata, grad, m, v, hyper, state in work:
+        for pdata, grad, m, v, hyper, state, ema in work:
             ops.adam_step_dev_guarded(pdata, grad, m, v, hyper, state, guard)
+            if ema is not None:
+                ops.ema_update(ema, pdata, self.ema_decay, state, guard)      # the same skip decision
 
     def guard_stats(self):
         """{'norm', 'coef', 'steps', 'clipped', 'skipped'} of the guard: norm and coefficient of the last step, counts over
@@ -159,6 +186,84 @@ class Adam(torch.optim.Optimizer):
             return {"norm": 0.0, "coef": 1.0, "steps": steps, "clipped": clipped, "skipped": skipped}
         _, norm, coef, _, steps, clipped, skipped = struct.unpack(_GUARD_FMT, self._guard.cpu().numpy().tobytes())
         return {"norm": norm, "coef": coef, "steps": steps, "clipped": clipped, "skipped": skipped}
+
+    # ---- weight average ----------------------------------------------------------------------------------------------
+    def _ensure_ema(self, st, weights, ar, p=None):
+        """The average of one store, made by its first step as a copy of the weights BEFORE that step's update (avg_0 = p_0,
+        same physical layout), then overwritten with what load_state_dict() read for it."""
+        if self.ema_decay is None or "ema" in st:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise GdnError("Adam(ema_decay): the weight average would be created inside a graph capture; run one eager step "
+                           "with the same gradient coverage first")
+        st["ema"] = weights.detach().clone(memory_format=torch.preserve_format)
+        if ar is None:
+            avg = self._pending_ema.pop(id(p), None)
+            if avg is not None:
+                st["ema"].copy_(avg)
+            return
+        for q, o, n, tr in ar.items:
+            avg = self._pending_ema.pop(id(q), None)
+            if avg is not None:
+                ar._view(st["ema"], o, q.shape, tr).copy_(avg)
+
+    def _ema_views(self):
+        """id(param) -> its average as a view in the parameter's logical shape, for every parameter a store averages."""
+        out = {}
+        for kind, st, ar, ps in self._stores():
+            if "ema" not in st:
+                continue
+            if kind == "arena":
+                for p, o, n, tr in ar.items:
+                    out[id(p)] = ar._view(st["ema"], o, p.shape, tr)
+            else:
+                out[id(ps[0])] = st["ema"]
+        return out
+
+    def averaged(self, p):
+        """The average of parameter `p`, in its logical shape: a view of the store's buffer once a step has made it; before
+        that what a checkpoint brought for it, else the parameter's own value (avg_0 = p_0).  While swap_averaged() is in
+        effect the buffer holds the raw weights instead."""
+        if self.ema_decay is None:
+            raise GdnError("averaged(): this optimizer keeps no weight average (ema_decay)")
+        v = self._ema_views().get(id(p))
+        if v is not None:
+            return v
+        avg = self._pending_ema.get(id(p))
+        return avg if avg is not None else p.detach()
+
+    def swap_averaged(self):
+        """Exchange weights and averages of every store in place (one launch per store), so the model itself runs on the
+        averaged weights -- and back with a second call.  Parameters no step has touched yet have no store: their average is
+        their value.  Between the two calls step(), state_dict() and load_state_dict() raise.  Not inside a graph capture."""
+        if self.ema_decay is None:
+            raise GdnError("swap_averaged(): this optimizer keeps no weight average (ema_decay)")
+        self._refuse_capture("swap_averaged()")
+        if any(pid in self._pending for pid in self._pending_ema):
+            # (a parameter that never took a step has no moments waiting either: its average is its value)
+            raise GdnError("swap_averaged(): averages read from a checkpoint are put in place by the first step after "
+                           "load_state_dict(); take one step first")
+        for kind, st, ar, ps in self._stores():
+            if "ema" not in st:
+                continue
+            ops.swap_(ar.data if kind == "arena" else ps[0].data, st["ema"])
+            arena = ar if kind == "arena" else getattr(ps[0], "_gdn_arena", None)
+            if arena is not None:
+                arena.touch()     # the weights changed behind torch's back: bf16 shadow, eval-BatchNorm coefficients
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """with optimizer.averaged_weights(): the model runs on the averaged weights; the raw ones are back afterwards."""
+        self.swap_averaged()
+        try:
+            yield self
+        finally:
+            self.swap_averaged()
+
+    def _refuse_swapped(self, what):
+        if self._swapped:
+            raise GdnError("optimizer %s while weights and averages are exchanged: call swap_averaged() again first" % what)
 
     def _step_partial(self, ar, st, group):
         """Per-tensor updates ON SLICES OF THE FLAT MOMENTS for the parameters that have a gradient (torch.optim.Adam skips
@@ -197,7 +302,8 @@ class Adam(torch.optim.Optimizer):
                     else:
                         ds = self._dev_state(group, st["pstep"][id(p)] - 1, ar.device)
                     pdev[id(p)] = ds
-                self._launch_dev(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], st["hyper"], ds)
+                self._launch_dev(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], st["hyper"], ds,
+                                 st["ema"][o:o + n] if "ema" in st else None)
             else:
                 ops.adam_step(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], group["lr"], b1, b2, group["eps"],
                               group["weight_decay"], st["pstep"][id(p)], self.grad_scale)
@@ -215,6 +321,8 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._swapped:
+            raise GdnError("optimizer.step() while weights and averages are exchanged: call swap_averaged() again first")
         if not self.guarded:
             self._step_groups()
             return loss
@@ -250,6 +358,7 @@ class Adam(torch.optim.Optimizer):
                           "pstep": None}
                     self._flat[id(ar)] = st
                     self._fill_arena(ar, st)          # a checkpoint loaded before this store existed
+                self._ensure_ema(st, ar.data, ar)
                 if st["pstep"] is None and all(p.grad is not None for p in ps):
                     st["step"] += 1
                     self._apply(ar.data, ar.grad, st, group, ar.device)
@@ -271,6 +380,7 @@ class Adam(torch.optim.Optimizer):
                     st["m"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["v"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     self._fill_loose(p, st)
+                self._ensure_ema(st, p.data, None, p)
                 st["step"] += 1
                 g = p.grad
                 if g.stride() != p.stride():
@@ -339,6 +449,7 @@ class Adam(torch.optim.Optimizer):
         """torch.optim.Adam's state_dict with the real moments (logical shape, contiguous; 'step' a float32 scalar tensor like
         torch's) and a 'gdn' key: host step counts, grad_scale and -- capturable path -- the device step state's bytes."""
         self._refuse_capture("state_dict()")
+        self._refuse_swapped("state_dict()")
         index, k = {}, 0
         for g in self.param_groups:
             for p in g["params"]:
@@ -386,6 +497,19 @@ class Adam(torch.optim.Optimizer):
             gs = self.guard_stats()
             priv["guard"] = {"max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite,
                              "steps": gs["steps"], "clipped": gs["clipped"], "skipped": gs["skipped"]}
+        if self.ema_decay is not None:
+            # every parameter, so the averaged model can be put together from this key alone
+            views = self._ema_views()
+            avg = {}
+            for g in self.param_groups:
+                for p in g["params"]:
+                    a = views.get(id(p))
+                    if a is None:
+                        a = self._pending_ema.get(id(p))
+                    if a is None:
+                        a = p         # no update yet: avg_0 = p_0
+                    avg[index[id(p)]] = a.detach().clone(memory_format=torch.contiguous_format)
+            priv["ema"] = {"decay": self.ema_decay, "avg": avg}
         return {"state": dict(sorted(state.items())), "param_groups": groups, "gdn": priv}
 
     def load_state_dict(self, state_dict):
@@ -396,6 +520,7 @@ class Adam(torch.optim.Optimizer):
         'step'.  Hyper-parameters of the groups are taken from the checkpoint (betas only if they differ in float32).  Not inside a graph capture; a graph captured
         before the load still holds the old device step state -- capture after loading."""
         self._refuse_capture("load_state_dict()")
+        self._refuse_swapped("load_state_dict()")
         groups = state_dict["param_groups"]
         mine = [len(g["params"]) for g in self.param_groups]
         theirs = [len(g["params"]) for g in groups]
@@ -439,16 +564,45 @@ class Adam(torch.optim.Optimizer):
                 raw = struct.pack(_GUARD_FMT, 0.0, 0.0, 1.0, 0, *self._guard_counts)
                 self._guard.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
                 self._guard_counts = None
+        # the averages (ema_decay stays the constructor's): parked like the moments; an optimizer without ema_decay ignores them
+        self._pending_ema = {}
+        if self.ema_decay is not None:
+            saved = (priv.get("ema") or {}).get("avg")
+            if saved is None:
+                if not self._ema_told and _rank0():
+                    print("optimizer state holds no weight average: the average starts from the loaded weights")
+                self._ema_told = True
+            else:
+                for key, a in saved.items():
+                    p = by_saved.get(key)
+                    if p is None:
+                        raise GdnError("weight average %r belongs to no parameter of the checkpoint's param_groups" % (key,))
+                    if tuple(a.shape) != tuple(p.shape):
+                        raise GdnError("weight average of parameter %r has shape %s, the parameter has %s" %
+                                       (key, tuple(a.shape), tuple(p.shape)))
+                    self._pending_ema[id(p)] = a.detach()
         # stores that exist: rewrite them now; parameters without a saved state start over
         for kind, st, ar, ps in self._stores():
             if kind == "arena":
                 self._fill_arena(ar, st, reset=True)
             else:
                 self._fill_loose(ps[0], st, reset=True)
+            if "ema" in st:
+                self._fill_ema(kind, st, ar, ps)
         for p in params:
             ar = getattr(p, "_gdn_arena", None)
             if ar is not None:
                 ar.touch()
+
+    def _fill_ema(self, kind, st, ar, ps):
+        """Rewrite the average of a store that exists: what load_state_dict() read, through each parameter's own view; the
+        weights as they are now where it read nothing."""
+        st["ema"].copy_(ar.data if kind == "arena" else ps[0].data)
+        items = ar.items if kind == "arena" else [(ps[0], 0, 0, None)]
+        for p, o, n, tr in items:
+            avg = self._pending_ema.pop(id(p), None)
+            if avg is not None:
+                (ar._view(st["ema"], o, p.shape, tr) if kind == "arena" else st["ema"]).copy_(avg)
 
     def _take_dev(self, st, rec, device):
         """Host counts and -- capturable -- the device step state of a store, from its 'gdn' record.  False: no usable record

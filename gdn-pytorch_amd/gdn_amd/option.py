@@ -1,6 +1,6 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
---init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite).
+--init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -11,6 +11,13 @@ def _non_negative_float(text):
     v = float(text)
     if not v >= 0.0:
         raise argparse.ArgumentTypeError("%r is not a non-negative number" % (text,))
+    return v
+
+
+def _ema_decay(text):
+    v = float(text)
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError("%r is not a decay in [0, 1)" % (text,))
     return v
 
 
@@ -79,7 +86,8 @@ def build_parser():
     p.add_argument('--save_state', action='store_true',
                    help='training: whenever a weight checkpoint is written, also write the rolling <save_dir>/train_state.pt '
                         '(weights, Adam moments and step state, loader position and RNG streams, epoch / iteration / learning '
-                        'rate: about three times the weights) that --resume continues from')
+                        'rate: about three times the weights, and one more copy of them with --ema_decay) that --resume continues '
+                        'from')
     p.add_argument('--save_state_every', type=int, default=0, metavar='N',
                    help='training: also write train_state.pt every N iterations (counted over the whole run)')
     p.add_argument('--resume', type=str, default=None, metavar='PATH',
@@ -91,6 +99,12 @@ def build_parser():
     p.add_argument('--skip_nonfinite', action='store_true',
                    help='training: a step whose gradient holds a NaN or an Inf leaves weights, Adam moments and the step '
                         'count untouched (decided on the device, no sync); the progress prints count such steps')
+    p.add_argument('--ema_decay', type=_ema_decay, default=0.0, metavar='D',
+                   help='training: keep an exponential moving average of the weights inside the fused Adam (decay D, warmed up '
+                        'as min(D, (1 + t) / (10 + t)) over the applied steps t; a skipped step leaves it alone); the per-epoch '
+                        'validation runs on the averaged weights and every X.pkl is followed by X_ema.pkl with them.  BatchNorm '
+                        'running statistics are buffers, not parameters: the averaged model uses the live ones (as torch\'s '
+                        'AveragedModel(use_buffers=False) does), no update_bn pass is made; 0 = off')
     return p
 
 

@@ -26,13 +26,36 @@ def _is_main():
     return D.rank() == 0
 
 
-def _save_checkpoint(model, path):
-    """state_dict with the DataParallel ``module.`` prefix the reference's files carry (F9)."""
+def _averaging(optimizer):
+    return getattr(optimizer, "ema_decay", None) is not None
+
+
+def _save_checkpoint(model, path, optimizer=None):
+    """state_dict with the DataParallel ``module.`` prefix the reference's files carry (F9).  With an optimizer that averages
+    the weights (--ema_decay) X.pkl is followed by X_ema.pkl: the same file with the averaged weights, written by rank 0 inside
+    a swap of its own (buffers -- BatchNorm running statistics -- are the live ones in both)."""
     if not _is_main():
         return
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     sd = {"module." + k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
     torch.save(sd, path)
+    if _averaging(optimizer):
+        with optimizer.averaged_weights():
+            sd = {"module." + k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
+        root, ext = os.path.splitext(path)
+        torch.save(sd, root + "_ema" + ext)
+
+
+def _validate_epoch(args, val_loader, model, optimizer, epoch, logger):
+    """The per-epoch validation of both training loops; on the averaged weights where the optimizer keeps them."""
+    if _averaging(optimizer):
+        with optimizer.averaged_weights():
+            errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
+    else:
+        errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
+    if _is_main():
+        print(('(averaged weights)' if _averaging(optimizer) else '') + ' * Avg ' +
+              ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
 
 
 def load_checkpoint(model, path, map_location="cpu"):
@@ -246,7 +269,7 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
                       (loss.item(), output_loss.item(), gradient_loss.item(), seen / (time.time() - t0)))
                 _print_guard_progress(optimizer)
             if (i + 1) % 3000 == 0:
-                _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
+                _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
                 model_num += 1
                 due = due or saver.on_checkpoint
             if due and not saver.last_batch(i):
@@ -256,13 +279,11 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
             if _is_main():
                 print('\n', 'epoch: ', epoch + 1, '  loss: ', loss.item())
             _print_guard_epoch(optimizer)
-            _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
+            _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
             model_num += 1
             due = due or saver.on_checkpoint
         if logger is not None and val_loader is not None:
-            errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
-            if _is_main():
-                print(' * Avg ' + ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
+            _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
         if due:                  # after everything this epoch does: the resumed run starts the next one
             saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
     return loss
@@ -373,7 +394,7 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
                       (loss.item(), output_loss.item(), smooth.item(), latent.item(), seen / (time.time() - t0)))
                 _print_guard_progress(optimizer)
             if (i + 1) % 700 == 0:
-                _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
+                _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
                 model_num += 1
                 due = due or saver.on_checkpoint
             if due and not saver.last_batch(i):
@@ -381,15 +402,13 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
                 due = False
         _print_guard_epoch(optimizer)
         if logger is not None and val_loader is not None:
-            errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
-            if _is_main():
-                print(' * Avg ' + ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
+            _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
         if due:
             saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
     if loss is not None and model_num == 0:
         # no cadence save happened (the reference's per-epoch save is commented out, trainer.py:877-887): a run shorter than
         # 700 steps per epoch -- a fine-tune, a trial -- leaves the weights it ends with instead of nothing
-        _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()))
+        _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
         if saver.on_checkpoint:
             saver.save(n_epochs, -1, lr, model_num, seen, gstep)
     return loss, output_loss, latent

@@ -727,6 +727,22 @@ int gdn_grad_guard_finalize(void* guard, const float* hyper, double max_norm, in
 int gdn_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n,
                               const float* hyper, void* state, const void* guard, void* stream);
 
+/* Exponential moving average of the weights, kept beside the moments (no reference counterpart).
+ * gdn_ema_update runs directly after the Adam update of the same store, on the same stream: `state` is the step state that
+ *   update has just advanced (gdn_adam_step_dev / gdn_adam_step_dev_guarded), `guard` the record the guarded update read, or
+ *   NULL after the unguarded one.  guard != NULL and guard->skip != 0: ema is neither read nor written.  Otherwise, with
+ *   t = state->step (1 after the first applied update):
+ *     w_t = (float)(1.0 - min(decay, (1.0 + t) / (10.0 + t)))     in double, rounded once -- every thread computes it itself
+ *     ema[i] = fmaf(w_t, p[i] - ema[i], ema[i])                    in float32
+ *   so the warm-up averages over the steps taken so far until (1 + t) / (10 + t) reaches `decay`.  The state is only read.
+ *   One launch; 0 < decay < 1, n >= 1, ema and p 4-byte aligned (GDN_ERR_BAD_ARG otherwise).
+ * gdn_swap_f32 exchanges two non-overlapping ranges of n floats in place (one launch); a NULL pointer, n <= 0 or overlapping
+ *   ranges return GDN_ERR_BAD_ARG before any launch.
+ * Both move 16 bytes per lane where the two bases agree modulo 16 (scalar head and tail around the aligned body) and one float
+ * per lane where they do not. */
+int gdn_ema_update(float* ema, const float* p, int64_t n, double decay, const void* state, const void* guard, void* stream);
+int gdn_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
