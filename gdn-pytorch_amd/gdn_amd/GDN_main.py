@@ -35,6 +35,8 @@ non-finite has already written its BatchNorm running statistics.
 ``--ema_decay D`` keeps an exponential moving average of the weights inside the fused Adam: the per-epoch
 validation runs on the averaged weights and every ``X.pkl`` is followed by ``X_ema.pkl`` with them, in the same format.
 BatchNorm running statistics are buffers: the averaged model uses the live ones.
+``--graph`` replays the training step as a hipGraph after ``--graph_warmup`` eager steps: one graph per step
+on one GPU, two around the eager gradient all-reduce under data parallelism; the run is bit for bit the run without the flag.
 """
 import os
 import sys
@@ -62,6 +64,8 @@ def _make_optimizer(model, args):
         guard["skip_nonfinite"] = True
     if getattr(args, "ema_decay", 0.0) > 0.0:
         guard["ema_decay"] = float(args.ema_decay)
+    if getattr(args, "graph", False):
+        guard["capturable"] = True            # the step counter lives on the device (the guard and the average imply it)
     return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
 
 
@@ -102,6 +106,18 @@ def _check_ema(args):
     """--ema_decay averages the weights of a training run; checked before anything touches the GPU."""
     if getattr(args, "ema_decay", 0.0) > 0.0 and args.mode in TEST_MODES:
         raise RuntimeError("--ema_decay averages the weights of a training run; --mode %s trains nothing" % args.mode)
+
+
+def _check_graph(args):
+    """--graph replays the step of a training run; checked before anything touches the GPU.  The global BerHu threshold is
+    an all-reduce(MAX) inside the loss: with more than one rank it would sit inside the captured forward."""
+    if not getattr(args, "graph", False):
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--graph replays the step of a training run; --mode %s trains nothing" % args.mode)
+    if getattr(args, "global_berhu", False) and D.env_rank()[2] > 1:
+        raise RuntimeError("--graph with --global_berhu on %d ranks: the threshold's all-reduce(MAX) sits inside the loss and "
+                           "no collective may be captured (drop one of the two flags)" % D.env_rank()[2])
 
 
 def _resume(args, model, opt, train_loader, rank):
@@ -167,6 +183,7 @@ def run(args, train_loader=None, val_loader=None):
         _check_dataset(args)
     _check_resume(args)
     _check_ema(args)
+    _check_graph(args)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num

@@ -217,6 +217,27 @@ class GpuAugmentLoader:
         # resume (state_dict / load_state_dict): the order stream's state before the current epoch's shuffle, the batch last
         # handed out in it (-1: none yet) and, after a load, the batch the next __iter__ starts with
         self._order_start, self._pos, self._resume = None, -1, None
+        self._bound = None
+
+    def bind_outputs(self, gt=None, rgb=None, sparse=None):
+        """Write every full-size batch into these three tensors -- a captured training step's static inputs -- and yield
+        exactly them, so nothing has to be copied before a replay.  An entry left None keeps its fresh tensor per batch;
+        all None unbinds.  The tensors are checked against the batch when it is written (ops.kitti_augment(out=)); a batch
+        of another size than the bound tensors' (a last partial one) is yielded in fresh tensors."""
+        bound = (gt, rgb, sparse)
+        for t in bound:
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dim() == 4 and t.dtype == torch.float32):
+                raise GdnError("bind_outputs: float32 [B,C,H,W] tensors or None, got %r" % (type(t).__name__,))
+        sizes = {t.shape[0] for t in bound if t is not None}
+        if len(sizes) > 1:
+            raise GdnError("bind_outputs: the tensors hold batches of different sizes %s" % sorted(sizes))
+        self._bound = None if not sizes else bound
+
+    def _outs(self, B):
+        """The bound tensors for a batch of B samples, or None (nothing bound, or another batch size)."""
+        if self._bound is None or next(t for t in self._bound if t is not None).shape[0] != B:
+            return None
+        return self._bound
 
     def _begin_epoch(self):
         """(sample order of the epoch that starts now, its first batch): batch 0 of a fresh shuffle, or -- once, after
@@ -304,13 +325,20 @@ class GpuAugmentLoader:
                 params = torch.tensor(host, dtype=torch.int32)
                 if self.dev.type == "cuda":
                     params = params.pin_memory().to(self.dev, non_blocking=True)
-            yield tuple(ops.kitti_augment(self._to_device([s[j] for s in samples]), params, self.train) for j in range(3))
+            outs = self._outs(len(samples))
+            if outs is None:
+                yield tuple(ops.kitti_augment(self._to_device([s[j] for s in samples]), params, self.train) for j in range(3))
+            else:
+                yield tuple(ops.kitti_augment(self._to_device([s[j] for s in samples]), params, self.train, out=outs[j])
+                            for j in range(3))
 
 
 class GpuCropLoader(GpuAugmentLoader):
     """Batches of (gt, rgb, gt) as normalised NCHW float32 tensors on `device`, in dataset order, with the NYU validation
     transform (CenterCrop to height x width at the centre of the colour image, ArrayToTensor, Normalize) executed by
     gdn_crop_normalize.  A sample whose third image is its first (NYUdataset) shares one output tensor."""
+
+    bind_outputs = None      # this transform allocates its outputs: a captured step copies its batch
 
     def __init__(self, dataset, batch_size, device, height, width, workers=0):
         super().__init__(dataset, batch_size, device, train=False, shuffle=False, workers=workers)
@@ -372,6 +400,8 @@ class GpuNYUAugmentLoader(GpuAugmentLoader):
     (GDN_main.py:94-129, datasets_list.py:399-430) executed by gdn_nyu_augment: the host decodes the files and makes the
     draws of draw_params_nyu per sample, in batch order; `last_params` keeps the last batch's draws.  Ordering, sharding
     (rank / world / order_seed) and drop_last are GpuAugmentLoader's.  height x width <= 251 x 340."""
+
+    bind_outputs = None      # this transform allocates its outputs: a captured step copies its batch
 
     def __init__(self, dataset, batch_size, device, height, width, mode="DtoD", seed=None, workers=0, drop_last=False,
                  rank=0, world=1, order_seed=None):
@@ -594,7 +624,13 @@ class GpuResidentLoader(GpuAugmentLoader):
                 self.last_params = host
                 rows[:, 1:] = host
             sel = self._ring.upload(ops.check_sel(rows, self.pools.n, H, W, self.train))
-            yield ops.kitti_augment_resident(self.pools.tensors, sel, self.train)
+            outs = self._outs(len(idxs))
+            if outs is None:
+                yield ops.kitti_augment_resident(self.pools.tensors, sel, self.train)
+            else:
+                outs = tuple(torch.empty((len(idxs), p.shape[3], H, W), dtype=torch.float32, device=self.dev) if o is None
+                             else o for o, p in zip(outs, self.pools.tensors))
+                yield ops.kitti_augment_resident(self.pools.tensors, sel, self.train, out=outs)
 
 
 class GpuNYUResidentLoader(GpuNYUAugmentLoader):

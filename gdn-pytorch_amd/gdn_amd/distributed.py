@@ -263,8 +263,9 @@ class GradReducer:
 
 
 def attach_reducer(model):
-    """Enable overlapped gradient reduction for `model` (no-op for world size 1)."""
-    if not active() or os.environ.get("GDN_OVERLAP_ALLREDUCE", "1") == "0":
+    """Enable overlapped gradient reduction for `model` (no-op for world size 1, and for a model whose step is replayed as
+    graphs: graph.GraphedDataParallelStep marks it, its whole arena is reduced after backward)."""
+    if not active() or os.environ.get("GDN_OVERLAP_ALLREDUCE", "1") == "0" or getattr(model, "_gdn_whole_arena_sync", False):
         return None
     ar = getattr(model, "_gdn_param_arena", None)
     if ar is None:

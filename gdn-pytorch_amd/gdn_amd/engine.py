@@ -221,7 +221,11 @@ def begin_backward(module, arena, ctx, trainable=True):
     # (backward without zero_grad: finish_grads adds it AFTER the tape) or a caller-owned .grad would be added behind
     # those reductions' backs -- such a backward leaves its local gradients in the arena and sync_gradients reduces the
     # whole arena afterwards (an already REDUCED carry is kept aside until then: ParamArena.carry_reduced)
-    if mine and trainable and not pending and not arena._bound_before:
+    # a model whose step is captured (graph.GraphedDataParallelStep) never overlaps: a collective issued from inside a
+    # capture, or by a tape that a replay does not run, is no collective at all -- its arena is reduced whole afterwards
+    if mine and trainable and not pending and not arena._bound_before and \
+            not getattr(module, "_gdn_whole_arena_sync", False) and \
+            not (arena.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
         red.begin()
         ctx.reducer = red
     return pending

@@ -1029,15 +1029,28 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=
                       float(grad_scale), stream())
 
 
-def kitti_augment(src, params, train=True):
+def _check_out(what, out, shape, device):
+    """A caller-owned output: a dense float32 tensor of exactly the shape and device the kernel writes."""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or \
+            out.device != device or not out.is_contiguous():
+        raise GdnError("%s: out must be a dense float32 %s tensor on %s, got %s" %
+                       (what, tuple(shape), device, "%s %s on %s" % (out.dtype, tuple(out.shape), out.device)
+                        if isinstance(out, torch.Tensor) else type(out).__name__))
+    return out
+
+
+def kitti_augment(src, params, train=True, out=None):
     """src [B,H,W,C] uint8/float32 as decoded; params int32 [B,5] on the device (or None when not train).
-    Returns the normalised NCHW float32 batch."""
+    Returns the normalised NCHW float32 batch: a new tensor, or `out` (dense float32 [B,C,H,W] on src's device, checked)."""
     if not src.is_cuda or src.dtype not in (torch.uint8, torch.float32) or src.dim() != 4 or not src.is_contiguous():
         raise GdnError("kitti_augment: src must be a dense [B,H,W,C] uint8/float32 tensor on the GPU")
     B, H, W, C = src.shape
     if train and (params is None or params.dtype != torch.int32 or tuple(params.shape) != (B, 5) or not params.is_cuda):
         raise GdnError("kitti_augment: params must be a device int32 [B,5] tensor")
-    dst = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+    if out is None:
+        dst = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+    else:
+        dst = _check_out("kitti_augment", out, (B, C, H, W), src.device)
     nb = int(lib.gdn_kitti_augment_workspace_bytes(B))
     ws = workspace(nb, src.device, "augment")
     lib.gdn_kitti_augment(_p(src), 1 if src.dtype == torch.float32 else 0, B, H, W, C, _p(params), 1 if train else 0,
@@ -1065,11 +1078,12 @@ def check_sel(rows, n, H, W, train=True):
     return rows
 
 
-def kitti_augment_resident(pools, sel, train=True):
+def kitti_augment_resident(pools, sel, train=True, out=None):
     """Assemble a batch from device-resident pools in one launch: pools = (gt, rgb, sparse), dense uint8 [N,H,W,C] device
     tensors of one N, H, W; sel = int32 [B,6] {sample index, flip, scaled_h, scaled_w, off_y, off_x} -- a device tensor
     whose rows the caller has passed through check_sel, or a host array / CPU tensor, checked and copied here.
-    Returns the three normalised NCHW float32 tensors (bit-identical to kitti_augment on the gathered samples)."""
+    Returns the three normalised NCHW float32 tensors (bit-identical to kitti_augment on the gathered samples): new ones, or
+    the three of `out` (dense float32 [B,C,H,W] each on the pools' device, checked)."""
     if len(pools) != 3 or any(not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 4 or
                               not p.is_contiguous() or not 1 <= p.shape[3] <= 4 for p in pools):
         raise GdnError("kitti_augment_resident: pools must be three dense [N,H,W,C<=4] uint8 tensors on the GPU")
@@ -1085,7 +1099,14 @@ def kitti_augment_resident(pools, sel, train=True):
             sel.device != dev:
         raise GdnError("kitti_augment_resident: sel must be a dense int32 [B,6] tensor on the pools' device")
     B = sel.shape[0]
-    outs = tuple(torch.empty((B, p.shape[3], H, W), dtype=torch.float32, device=dev) for p in pools)
+    if out is None:
+        outs = tuple(torch.empty((B, p.shape[3], H, W), dtype=torch.float32, device=dev) for p in pools)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise GdnError("kitti_augment_resident: out must be three tensors (gt, rgb, sparse)")
+        outs = tuple(_check_out("kitti_augment_resident", o, (B, p.shape[3], H, W), dev) for o, p in zip(out, pools))
+        if len({o.data_ptr() for o in outs}) != 3:
+            raise GdnError("kitti_augment_resident: the three out tensors must be distinct")
     lib.gdn_kitti_augment_resident(_p(pools[0]), pools[0].shape[3], _p(pools[1]), pools[1].shape[3], _p(pools[2]),
                                    pools[2].shape[3], H, W, _p(sel), B, 1 if train else 0, _p(outs[0]), _p(outs[1]),
                                    _p(outs[2]), stream())

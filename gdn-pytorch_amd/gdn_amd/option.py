@@ -1,6 +1,7 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
---init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay).
+--init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
+--graph_warmup).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -18,6 +19,13 @@ def _ema_decay(text):
     v = float(text)
     if not 0.0 <= v < 1.0:
         raise argparse.ArgumentTypeError("%r is not a decay in [0, 1)" % (text,))
+    return v
+
+
+def _positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("%r is not a positive integer" % (text,))
     return v
 
 
@@ -105,6 +113,13 @@ def build_parser():
                         'validation runs on the averaged weights and every X.pkl is followed by X_ema.pkl with them.  BatchNorm '
                         'running statistics are buffers, not parameters: the averaged model uses the live ones (as torch\'s '
                         'AveragedModel(use_buffers=False) does), no update_bn pass is made; 0 = off')
+    p.add_argument('--graph', action='store_true',
+                   help='training: capture the step (forward, losses, backward, fused Adam) as a hipGraph after the first '
+                        '--graph_warmup eager steps and replay it from then on: one graph launch per step on one GPU, two '
+                        'around the eager gradient all-reduce with data parallelism (which then no longer overlaps backward). '
+                        'The run is bit for bit the run without the flag; a batch of another shape runs eagerly')
+    p.add_argument('--graph_warmup', type=_positive_int, default=3, metavar='N',
+                   help='with --graph: eager steps (on their own batches) of a run or a resumed run before the capture')
     return p
 
 

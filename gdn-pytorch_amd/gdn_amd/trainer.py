@@ -225,6 +225,89 @@ def _print_guard_epoch(optimizer):
         print("grad guard: clipped %d, skipped %d of %d steps" % (gs["clipped"], gs["skipped"], gs["steps"]))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# --graph: the step of a training loop replayed as a hipGraph
+last_graph_report = None       # what the last --graph loop of this process printed: {'replayed', 'warmup', 'eager_steps'}
+
+
+def _shapes(inputs):
+    return [(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else None for t in inputs]
+
+
+class _GraphedLoopStep:
+    """The step of one --graph training loop.  The first `graph_warmup` steps of the run (or of the resumed run) are the
+    loop's ordinary eager steps on their own batches.  The next batch is captured around (prewarmed: the capture executes
+    nothing) and replayed, and so is every later batch of its shapes -- provided an eager step has already run at these
+    shapes and no larger batch has been seen: a last partial batch is never what gets captured once a full one has run.
+    Every other batch (a partial one, or one that waits for such a capture) runs eagerly and is counted in `eager_steps`.
+    One graph at world 1, two around the eager all-reduce otherwise.  bind(loader, static_inputs) hands the static inputs
+    to a loader that can write into them."""
+
+    def __init__(self, args, model, optimizer, loader, step_fn, fwd_bwd_fn, bind):
+        self.model, self.optimizer, self.loader = model, optimizer, loader
+        self.step_fn, self.fwd_bwd_fn, self.bind = step_fn, fwd_bwd_fn, bind
+        self.warmup = max(1, int(getattr(args, "graph_warmup", 3) or 3))
+        self.graphed, self.shapes, self.seen, self.largest = None, None, [], 0
+        self.warm = self.replayed = self.eager_steps = 0
+        self.bound = False
+
+    def _capture(self, inputs, shapes):
+        from .graph import GraphedDataParallelStep, GraphedTrainStep
+        if D.world_size() > 1:
+            self.graphed = GraphedDataParallelStep(self.fwd_bwd_fn, self.model, self.optimizer, inputs, prewarmed=True)
+        else:
+            self.graphed = GraphedTrainStep(self.step_fn, inputs, self.optimizer, prewarmed=True)
+        self.shapes = shapes
+        if callable(getattr(self.loader, "bind_outputs", None)):
+            self.bind(self.loader, self.graphed.static_inputs)      # from the next batch on nothing is copied
+            self.bound = True
+
+    def __call__(self, *inputs):
+        shapes = _shapes(inputs)
+        if self.graphed is None:
+            n = inputs[0].shape[0]
+            if self.warm >= self.warmup and shapes in self.seen and n >= self.largest:
+                self._capture(inputs, shapes)
+            else:
+                if self.warm < self.warmup:
+                    self.warm += 1
+                else:
+                    self.eager_steps += 1
+                if shapes not in self.seen:
+                    self.seen.append(shapes)
+                self.largest = max(self.largest, n)
+                return self.step_fn(*inputs)
+        if shapes != self.shapes:
+            self.eager_steps += 1
+            return self.step_fn(*inputs)
+        with tracing.span("gdn.graph_step"):
+            out = self.graphed(*inputs)
+        self.replayed += 1
+        return out
+
+    def close(self):
+        """End of the loop: the loader gets its own outputs back, rank 0 reports once."""
+        global last_graph_report
+        if self.bound:
+            self.loader.bind_outputs(None, None, None)
+            self.bound = False
+        last_graph_report = {"replayed": self.replayed, "warmup": self.warm, "eager_steps": self.eager_steps}
+        if _is_main():
+            print("graph: %d steps replayed as %s, %d eager (%d warm-up, %d on batches of another shape)" %
+                  (self.replayed, "2 graphs around the all-reduce" if D.world_size() > 1 else "1 graph",
+                   self.warm + self.eager_steps, self.warm, self.eager_steps))
+
+
+def _loop_step(args, model, optimizer, loader, step_fn, fwd_bwd_fn, bind):
+    """(what the loop calls per batch, what it calls when it ends): the eager step itself without --graph."""
+    if not getattr(args, "graph", False):
+        return step_fn, lambda: None
+    if not getattr(optimizer, "capturable", False):
+        raise U.GdnError("--graph needs optim.Adam(..., capturable=True): the step count must live on the device")
+    run = _GraphedLoopStep(args, model, optimizer, loader, step_fn, fwd_bwd_fn, bind)
+    return run, run.close
+
+
 def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_loader, val_loader, batch_size,
                   n_epochs, lr, logger, train_writer, progress=None):
     """Depth->depth auto-encoder training; loss = BerHu + 3*imgrad_loss (trainer.py:411-468).
@@ -238,6 +321,27 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
     loss = output_loss = gradient_loss = None
     epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
     saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
+
+    def fwd_bwd(depths, sparse):
+        with tracing.span("gdn.forward"):
+            outputs = model(depths, istrain=False)
+        with tracing.span("gdn.losses"):
+            terms = U.dtod_loss(outputs, depths, sparse)
+        optimizer.zero_grad()
+        with tracing.span("gdn.backward"):
+            U.backward(terms[0])        # == loss.backward(), seed gradient cached
+        return terms
+
+    def step(depths, sparse):
+        terms = fwd_bwd(depths, sparse)
+        with tracing.span("gdn.allreduce"):
+            D.sync_gradients(model, optimizer)
+        with tracing.span("gdn.adam"):
+            optimizer.step()
+        return terms
+
+    run_step, end_steps = _loop_step(args, model, optimizer, dataset_loader, step, fwd_bwd,
+                                     lambda loader, static: loader.bind_outputs(static[0], None, static[1]))
     t0 = time.time()
     for epoch in range(epoch0, n_epochs):
         model.train()
@@ -245,17 +349,7 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
         for i, (gt_data, _, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
             depths = _to_dev(gt_data, dev)
             sparse = _to_dev(gt_data_2, dev) if kitti else None       # None <=> NYU: unmasked BerHu
-            with tracing.span("gdn.forward"):
-                outputs = model(depths, istrain=False)
-            with tracing.span("gdn.losses"):
-                loss, output_loss, gradient_loss = U.dtod_loss(outputs, depths, sparse)
-            optimizer.zero_grad()
-            with tracing.span("gdn.backward"):
-                U.backward(loss)            # == loss.backward(), seed gradient cached
-            with tracing.span("gdn.allreduce"):
-                D.sync_gradients(model, optimizer)
-            with tracing.span("gdn.adam"):
-                optimizer.step()
+            loss, output_loss, gradient_loss = run_step(depths, sparse)
             seen += depths.shape[0] * D.world_size()
             gstep += 1
             due = saver.due(gstep)
@@ -286,6 +380,7 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
             _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
         if due:                  # after everything this epoch does: the resumed run starts the next one
             saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
+    end_steps()
     return loss
 
 
@@ -355,6 +450,37 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     latent = torch.zeros((), device=dev)
     epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
     saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
+    latent0 = latent
+
+    def fwd_bwd(inputs, depths, sparse):
+        latent = latent0
+        with tracing.span("gdn.forward"):
+            outputs = model(inputs, istrain=False)
+        tracing.push("gdn.losses")
+        if not single:
+            latent = guide_latent_loss(DtoD_model, depths, outputs, faithful=getattr(args, "faithful_guide", False),
+                                       latent_grad=getattr(args, "latent_grad", False))
+        if latent.requires_grad:            # --latent_grad: a differentiable term joins through autograd
+            pix, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse)
+            loss = pix + latent
+        else:                               # value-only latent loss (F3): summed by the loss kernel itself
+            loss, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse, plus=latent)
+        tracing.pop()
+        optimizer.zero_grad()
+        with tracing.span("gdn.backward"):
+            U.backward(loss)            # == loss.backward(), seed gradient cached
+        return loss, output_loss, smooth, latent
+
+    def step(inputs, depths, sparse):
+        terms = fwd_bwd(inputs, depths, sparse)
+        with tracing.span("gdn.allreduce"):
+            D.sync_gradients(model, optimizer)
+        with tracing.span("gdn.adam"):
+            optimizer.step()
+        return terms
+
+    run_step, end_steps = _loop_step(args, model, optimizer, dataset_loader, step, fwd_bwd,
+                                     lambda loader, static: loader.bind_outputs(static[1], static[0], static[2]))
     t0 = time.time()
     for epoch in range(epoch0, n_epochs):
         model.train()
@@ -362,25 +488,7 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
         for i, (gt_data, rgb_data, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
             inputs, depths = _to_dev(rgb_data, dev), _to_dev(gt_data, dev)
             sparse = _to_dev(gt_data_2, dev) if kitti else None
-            with tracing.span("gdn.forward"):
-                outputs = model(inputs, istrain=False)
-            tracing.push("gdn.losses")
-            if not single:
-                latent = guide_latent_loss(DtoD_model, depths, outputs, faithful=getattr(args, "faithful_guide", False),
-                                           latent_grad=getattr(args, "latent_grad", False))
-            if latent.requires_grad:            # --latent_grad: a differentiable term joins through autograd
-                pix, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse)
-                loss = pix + latent
-            else:                               # value-only latent loss (F3): summed by the loss kernel itself
-                loss, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse, plus=latent)
-            tracing.pop()
-            optimizer.zero_grad()
-            with tracing.span("gdn.backward"):
-                U.backward(loss)            # == loss.backward(), seed gradient cached
-            with tracing.span("gdn.allreduce"):
-                D.sync_gradients(model, optimizer)
-            with tracing.span("gdn.adam"):
-                optimizer.step()
+            loss, output_loss, smooth, latent = run_step(inputs, depths, sparse)
             seen += depths.shape[0] * D.world_size()
             gstep += 1
             due = saver.due(gstep)
@@ -411,6 +519,7 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
         _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
         if saver.on_checkpoint:
             saver.save(n_epochs, -1, lr, model_num, seen, gstep)
+    end_steps()
     return loss, output_loss, latent
 
 
