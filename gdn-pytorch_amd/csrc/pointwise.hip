@@ -547,13 +547,12 @@ __global__ void fill_kernel(float* __restrict__ p, float v, int64_t n) {
 }
 
 // ------------------------------------------------------------------------ Adam
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                   float b1, float b2, float eps, float wd, float bc1, float bc2s,
-                                                   float gscale) {
-    // torch.optim.Adam: g += wd*p; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
-    // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
-    const float step = lr / bc1;
+// torch.optim.Adam: g += wd*p; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
+// p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+// The update loop of all three Adam kernels: `step` = lr / bc1, `gscale` the gradient's scale (grad_scale, times the guard's coef).
+__device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, int64_t n, float step, float b1, float b2, float eps,
+                                            float wd, float bc2s, float gscale) {
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float pi = p[i];
         const float gi = g[i] * gscale + wd * pi;
@@ -562,6 +561,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         m[i] = mi; v[i] = vi;
         p[i] = pi - step * mi / (sqrtf(vi) / bc2s + eps);
     }
+}
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                                                   float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                                                   float gscale) {
+    adam_update(p, g, m, v, n, lr / bc1, b1, b2, eps, wd, bc2s, gscale);
 }
 
 // Capturable Adam: the step counter and the running powers beta^t live in device memory, so a captured training step
@@ -579,16 +584,7 @@ __global__ void adam_prep_kernel(AdamDevState* st, const float* __restrict__ hyp
 __device__ __forceinline__ void adam_dev_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                 float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                                                 const AdamDevState* st, float gscale) {
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
-    const float step = lr / st->bc1, bc2s = st->bc2s;
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float pi = p[i];
-        const float gi = g[i] * gscale + wd * pi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = pi - step * mi / (sqrtf(vi) / bc2s + eps);
-    }
+    adam_update(p, g, m, v, n, hyper[0] / st->bc1, hyper[1], hyper[2], hyper[3], hyper[4], st->bc2s, gscale);
 }
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
@@ -609,6 +605,16 @@ __device__ __forceinline__ double sq4_d(f32x4 a) {
     const double x = (double)a.x, y = (double)a.y, z = (double)a.z, w = (double)a.w;       // 1e30f squared fits a double
     return (x * x + y * y) + (z * z + w * w);
 }
+// The head/body/tail split of `n` floats starting at `base`.
+struct StreamSplit { int64_t head, nvec, tail0; };
+__device__ __forceinline__ StreamSplit stream_split(const void* base, int64_t n) {
+    StreamSplit s;
+    s.head = (int64_t)((4u - (unsigned)(((uintptr_t)base >> 2) & 3u)) & 3u);
+    if (s.head > n) s.head = n;
+    s.nvec = (n - s.head) >> 2;
+    s.tail0 = s.head + s.nvec * 4;
+    return s;
+}
 // stage 1: partial[b] = sum of squares of block b's share.  Up to 3 head elements bring the body to a 16-byte boundary
 // (ar.grad[o:o+n] slices and loose parameters start anywhere); the body is read as float4, 4 loads in flight per lane;
 // head and tail (< 4 elements each) go to lanes of block 0.  Per-lane partials -> xor-butterfly over the 64 lanes -> the
@@ -616,9 +622,8 @@ __device__ __forceinline__ double sq4_d(f32x4 a) {
 __global__ __launch_bounds__(256) void adam_gradnorm_partial_kernel(const float* __restrict__ g, int64_t n,
                                                                    double* __restrict__ partial) {
     __shared__ double sh[4];
-    int64_t head = (int64_t)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
-    if (head > n) head = n;
-    const int64_t nvec = (n - head) >> 2, tail0 = head + nvec * 4;
+    const StreamSplit sp = stream_split(g, n);
+    const int64_t head = sp.head, nvec = sp.nvec, tail0 = sp.tail0;
     const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
     const int64_t T = (int64_t)gridDim.x * 256;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -679,16 +684,6 @@ __global__ __launch_bounds__(256) void adam_dev_guarded_kernel(float* __restrict
 // ---- weight EMA and the in-place exchange of two float ranges (include/gdn_hip.h).  Pure streaming: the body moves 16 bytes per
 // lane, up to 3 head elements bring it to a 16-byte boundary and fewer than 4 tail elements follow it (lanes of block 0, as in
 // adam_gradnorm_partial_kernel); VEC = false is the scalar form for operands whose bases differ modulo 16.  No atomics, no LDS.
-// The head/body/tail split of `n` floats starting at `base`.
-struct StreamSplit { int64_t head, nvec, tail0; };
-__device__ __forceinline__ StreamSplit stream_split(const void* base, int64_t n) {
-    StreamSplit s;
-    s.head = (int64_t)((4u - (unsigned)(((uintptr_t)base >> 2) & 3u)) & 3u);
-    if (s.head > n) s.head = n;
-    s.nvec = (n - s.head) >> 2;
-    s.tail0 = s.head + s.nvec * 4;
-    return s;
-}
 __device__ __forceinline__ float ema1(float w, float p, float e) { return fmaf(w, p - e, e); }
 // e += w_t (p - e) with w_t = 1 - min(decay, (1 + t) / (10 + t)), t = the step count the Adam update of this store has just
 // advanced; every thread computes w_t itself, in double, rounded once.  A skipped step (guard->skip) reads and writes nothing.

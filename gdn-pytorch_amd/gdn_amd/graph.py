@@ -24,34 +24,6 @@ from . import engine as E
 from ._lib import GdnError
 
 
-def _host_counts(optimizer):
-    """The host-side update counts of every state store of `optimizer` (step() advances them; a capture runs step()'s host
-    code once without executing anything, a replay executes it without running the host code)."""
-    stores = list(optimizer._flat.values()) + [st for st in optimizer.state.values() if st]
-    return [(st, st["step"], None if st.get("pstep") is None else dict(st["pstep"])) for st in stores]
-
-
-def _take_back(before):
-    """Undo what a capture added to the host counts snapshot `before`; returns it as the per-replay increments."""
-    delta = []
-    for st, step, pstep in before:
-        dp = None
-        if pstep is not None and st.get("pstep") is not None:
-            dp = {k: st["pstep"][k] - v for k, v in pstep.items()}
-            st["pstep"].update(pstep)
-        delta.append((st, st["step"] - step, dp))
-        st["step"] = step
-    return delta
-
-
-def _count_replay(delta):
-    for st, dstep, dp in delta:
-        st["step"] += dstep
-        if dp is not None and st.get("pstep") is not None:
-            for k, d in dp.items():
-                st["pstep"][k] += d
-
-
 def _refill(static_inputs, inputs):
     """Copy `inputs` into the static buffers; an input that already IS its buffer (a bound loader wrote it there) costs
     nothing.  Returns the number of copies made."""
@@ -95,12 +67,12 @@ class GraphedTrainStep:
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self.warmup_steps = max(1, warmup)
-        before = _host_counts(optimizer) if prewarmed else None
+        before = optimizer.host_counts() if prewarmed else None
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             out = step_fn(*self.static_inputs)
         # (prewarmed: the run's host-side counts follow the replays, so a state_dict() equals the eager run's)
-        self._counts = _take_back(before) if prewarmed else []
+        self._counts = optimizer.take_back_counts(before) if prewarmed else []
         self.static_outputs = out
         self.replays = 0
         self.refills = 0
@@ -111,7 +83,7 @@ class GraphedTrainStep:
         self.optimizer.refresh_hyper()           # a learning-rate decay since the last replay reaches the device here
         self.graph.replay()
         self.replays += 1
-        _count_replay(self._counts)
+        self.optimizer.count_replay(self._counts)
         E.bump_graph_epoch()                     # BN running statistics changed behind torch's version counters
         return self.static_outputs
 
@@ -172,13 +144,13 @@ class GraphedDataParallelStep:
         if getattr(ar, "carry_reduced", None) is not None:
             raise GdnError("GraphedDataParallelStep: fwd_bwd_fn accumulates onto an all-reduced gradient (no zero_grad); "
                            "that cannot be replayed")
-        before = _host_counts(optimizer)
+        before = optimizer.host_counts()
         self.graph_b = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_b):
             optimizer.step()
-        counts = _take_back(before)
+        counts = optimizer.take_back_counts(before)
         if not prewarmed:                            # (as GraphedTrainStep always did: the capture counts as a step taken)
-            _count_replay(counts)
+            optimizer.count_replay(counts)
             counts = []
         self._counts = counts
         self.static_outputs = out
@@ -193,6 +165,6 @@ class GraphedDataParallelStep:
         D.sync_gradients(self.model, self.optimizer)     # eager: the whole arena, summed over the ranks
         self.graph_b.replay()
         self.replays += 1
-        _count_replay(self._counts)
+        self.optimizer.count_replay(self._counts)
         E.bump_graph_epoch()
         return self.static_outputs

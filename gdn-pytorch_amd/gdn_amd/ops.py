@@ -1265,7 +1265,9 @@ def spline_rotate(src, angle=None, matrix=None, offset=None, clip=True):
 
 
 def adam_step_dev(p, g, m, v, hyper, state):
-    """Capturable Adam: hyper float32[6] and state uint8[32] live on the device (see gdn_adam_step_dev)."""
+    """Capturable Adam: hyper float32[6] and the 28-byte step state {double beta1^t, beta2^t; int32 t; float bc1, bc2s} (a
+    uint8[28] tensor; the kernels never touch the C struct's 4 bytes of tail padding) live on the device (see
+    gdn_adam_step_dev)."""
     lib.gdn_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), stream())
 
 

@@ -22,11 +22,214 @@ from . import ops
 from ._lib import GdnError
 
 
-_GUARD_FMT = "<dffiiii"      # gdn_hip.h: { double sumsq; float norm, coef; int32 skip, steps, clipped, skipped; }
+# the two device records (gdn_hip.h), as the host packs and reads them
+_STEP_FMT = "<ddiff"         # { double beta1^t, beta2^t; int32 t; float bc1, bc2s; }: 28 bytes, which checkpoints carry verbatim
+_GUARD_FMT = "<dffiiii"      # { double sumsq; float norm, coef; int32 skip, steps, clipped, skipped; }: 32 bytes
+
+
+def _record(fmt, *fields):
+    return torch.frombuffer(bytearray(struct.pack(fmt, *fields)), dtype=torch.uint8)
+
+
+def _unpack(fmt, record):
+    return struct.unpack_from(fmt, record.cpu().numpy().tobytes())
+
+
+def _guard_bytes(steps, clipped, skipped):
+    """A guard record between two steps: no sum, coefficient 1, no skip, the run's counts."""
+    return _record(_GUARD_FMT, 0.0, 0.0, 1.0, 0, steps, clipped, skipped)
+
+
+def _step_state(group, t, device):
+    """The step state for `t` steps TAKEN so far (the kernel advances it before it uses it)."""
+    _no_capture("capturable Adam: a device step counter would be created (and reset by every replay) inside a graph "
+                "capture; run one eager step with the same gradient coverage first")
+    b1, b2 = group["betas"]
+    return _record(_STEP_FMT, float(b1) ** t, float(b2) ** t, t, 0.0, 0.0).to(device)
+
+
+def _f32(x):
+    """`x` as the kernels receive it: rounded to float32."""
+    return struct.unpack("<f", struct.pack("<f", float(x)))[0]
+
+
+def _no_capture(message):
+    """Refuse what a graph capture cannot hold.  (Asked of a process without a GPU, the stream query itself raises.)"""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise GdnError(message)
 
 
 def _rank0():
     return not (torch.distributed.is_available() and torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
+
+
+class _Parked:
+    """What load_state_dict() read, until the store it belongs to exists (the arena is built by the first forward, the
+    stores by the first step).  Tensors in each parameter's LOGICAL layout; _Store.fill() and Adam._guard_record() take
+    what is theirs out of it."""
+
+    def __init__(self, guard=None):
+        self.moments = {}        # id(param) -> {"step", "m", "v"}
+        self.averages = {}       # id(param) -> its weight average
+        self.records = {}        # id(a store's first param) -> the store's 'gdn' record, indices replaced by ids
+        self.guard = guard       # (steps, clipped, skipped) for a guard record that does not exist yet, or None
+
+    def averages_wait_for_a_step(self):
+        # (a parameter that never took a step has no moments waiting either: its average is its value)
+        return any(pid in self.moments for pid in self.averages)
+
+
+class _Store:
+    """The Adam state of one arena, or of one loose parameter -- the same thing with one item and no arena.
+
+    items    [(param, offset, numel, transposed or None)]: arena.items, or [(p, 0, p.numel(), None)]
+    m, v     the moments in the PHYSICAL layout: flat tensors of arena.numel floats, or zeros_like(p); `ema` the weight
+             average beside them (None without ema_decay); view() gives an item's logical-shape view of any of the three
+    step     the host's count of updates; `pstep` is None while every parameter has taken that many and becomes
+             {id(param): count} once an arena's coverage has been partial (always None for a loose parameter)
+    hyper, hyper_host, group, state, pdev, full_dev
+             the device side of the capturable path: float32[6] hyper-parameters and what the host last wrote there, their
+             param group, the store's step state, {id(param): step state} of the per-tensor path, and whether `state` has
+             taken every update so far (then it may be copied for a parameter: ADVICE r4)
+    The optimizer keeps its stores in Adam._stores, by id(arena) or id(param); torch.optim.Optimizer.state is not used."""
+
+    def __init__(self, items, arena=None):
+        self.items, self.arena = items, arena
+        if arena is not None:
+            self.device = arena.device
+            self.m, self.v = ops.zeros((arena.numel,), arena.device), ops.zeros((arena.numel,), arena.device)
+        else:
+            p = items[0][0]
+            self.device = p.device
+            self.m = torch.zeros_like(p, memory_format=torch.preserve_format)
+            self.v = torch.zeros_like(p, memory_format=torch.preserve_format)
+        self.ema, self.step, self.pstep = None, 0, None
+        self._drop_dev()
+
+    def _drop_dev(self):
+        self.hyper = self.hyper_host = self.group = self.state = None
+        self.pdev, self.full_dev = {}, False
+
+    @property
+    def kind(self):
+        return "loose" if self.arena is None else "arena"
+
+    @property
+    def weights(self):
+        """The live weights buffer the moments run beside."""
+        return self.items[0][0].data if self.arena is None else self.arena.data
+
+    def view(self, buf, item):
+        """`item`'s logical-shape view of the store buffer `buf` (tap-major underneath for convolution weights)."""
+        p, o, _, tr = item
+        return buf if self.arena is None else self.arena._view(buf, o, p.shape, tr)
+
+    def touch(self):
+        """The weights changed behind torch's back: bf16 shadow, eval-BatchNorm coefficients."""
+        arena = self.arena if self.arena is not None else getattr(self.items[0][0], "_gdn_arena", None)
+        if arena is not None:
+            arena.touch()
+
+    def count(self, p, memo=None):
+        """Updates parameter `p` has taken: the device's count where the capturable path keeps one (graph replays advance
+        it behind the host's back), the host's otherwise.  `memo` saves reading one step state twice."""
+        memo = {} if memo is None else memo
+
+        def dev(t):
+            if id(t) not in memo:
+                memo[id(t)] = _unpack(_STEP_FMT, t)[2]
+            return memo[id(t)]
+        if self.state is not None:
+            if self.pstep is None:
+                return dev(self.state)
+            if id(p) in self.pdev:
+                return dev(self.pdev[id(p)])
+            if self.full_dev:
+                return dev(self.state)        # no counter of its own yet: the arena's, frozen when coverage split
+        return self.step if self.pstep is None else self.pstep[id(p)]
+
+    def record(self, index):
+        """The store's entry of state_dict()['gdn']['stores']; `index`: id(param) -> its number in the param groups."""
+        ids = [id(p) for p, _, _, _ in self.items]
+        return {"kind": self.kind, "params": [index[i] for i in ids], "step": int(self.step),
+                "pstep": None if self.pstep is None else [int(self.pstep[i]) for i in ids],
+                "full_dev": bool(self.full_dev),
+                "state": None if self.state is None else self.state.detach().cpu().clone(),
+                "pdev": {index[i]: self.pdev[i].detach().cpu().clone() for i in ids if i in self.pdev}}
+
+    def take_record(self, rec, capturable):
+        """Host counts and -- capturable -- the device step state from a record() whose indices are ids.  False: no usable
+        record (a torch checkpoint, or device counts saved by a capturable optimizer and read by a host-side one), the
+        counts come from 'step'."""
+        self._drop_dev()
+        if rec is None or (rec.get("state") is not None and not capturable):
+            return False
+        self.step = int(rec["step"])
+        if self.arena is not None and rec["pstep"] is not None:
+            self.pstep = dict(zip(rec["params"], [int(c) for c in rec["pstep"]]))
+        else:
+            self.pstep = None
+        if rec.get("state") is not None:
+            self.state = rec["state"].to(device=self.device, copy=True)        # the device's own bytes, verbatim
+            self.full_dev = bool(rec["full_dev"])
+            if rec["pstep"] is not None:
+                self.pdev = {pid: t.to(device=self.device, copy=True) for pid, t in rec["pdev"].items()}
+        return True
+
+    def fill(self, parked, capturable, averaged, reset=False):
+        """Take what load_state_dict() parked for this store's parameters: each moment and average through the parameter's
+        own view of the buffer (tap-major for convolution weights), never under a logical shape.  A new store (the first
+        step made it) takes what is there; reset: a store that exists is rewritten, and starts over where nothing was read.
+        `averaged`: the store keeps a weight average -- made here as a copy of the weights BEFORE the first update
+        (avg_0 = p_0, same physical layout), then overwritten with what was read for it."""
+        ids = [id(p) for p, _, _, _ in self.items]
+        if reset or any(i in parked.moments for i in ids):
+            self.m.zero_()
+            self.v.zero_()
+            counts = {}
+            for item in self.items:
+                s = parked.moments.pop(id(item[0]), None)
+                counts[id(item[0])] = s["step"] if s else 0
+                if s:
+                    self.view(self.m, item).copy_(s["m"])
+                    self.view(self.v, item).copy_(s["v"])
+            rec = parked.records.pop(ids[0], None)
+            if rec is not None and (rec["kind"] != self.kind or rec["params"] != ids):
+                rec = None
+            if not self.take_record(rec, capturable):
+                level = set(counts.values())
+                self.step, self.pstep = (level.pop(), None) if len(level) == 1 else (max(level), counts)
+        if not averaged:
+            return
+        if self.ema is None:
+            _no_capture("Adam(ema_decay): the weight average would be created inside a graph capture; run one eager step "
+                        "with the same gradient coverage first")
+            self.ema = self.weights.detach().clone(memory_format=torch.preserve_format)
+        elif reset:
+            self.ema.copy_(self.weights)
+        for item in self.items:
+            avg = parked.averages.pop(id(item[0]), None)
+            if avg is not None:
+                self.view(self.ema, item).copy_(avg)
+
+    # host counts under graph capture and replay (DESIGN.md 3.4)
+    def counts(self):
+        return self.step, None if self.pstep is None else dict(self.pstep)
+
+    def take_back(self, step, pstep):
+        """Undo what a capture added since counts() gave (step, pstep); returns it as the per-replay increments."""
+        dp = None
+        if pstep is not None and self.pstep is not None:
+            dp = {k: self.pstep[k] - c for k, c in pstep.items()}
+            self.pstep.update(pstep)
+        dstep, self.step = self.step - step, step
+        return dstep, dp
+
+    def advance(self, dstep, dp):
+        self.step += dstep
+        if dp is not None and self.pstep is not None:
+            for k, d in dp.items():
+                self.pstep[k] += d
 
 
 class Adam(torch.optim.Optimizer):
@@ -54,7 +257,7 @@ class Adam(torch.optim.Optimizer):
             raise ValueError("ema_decay must lie in (0, 1) (None: no weight average), got %r" % (ema_decay,))
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
-        self._flat = {}        # id(arena) -> {"m","v","step"}
+        self._stores = {}      # id(arena) or id(loose param) -> _Store, made by the first step that updates it
         self.grad_scale = 1.0  # set to 1/world_size by the data-parallel wrapper
         # capturable: the step counter, beta^t and the hyper-parameters live in device memory (gdn_adam_step_dev), so
         # step() can be captured in a hipGraph and replayed; call refresh_hyper() after changing lr outside a capture
@@ -64,32 +267,29 @@ class Adam(torch.optim.Optimizer):
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None
         # guarded: step() gathers its launches in _work, then runs the norm pass, the decision and the updates; _guard is
-        # the device record (made by the first step), _guard_counts what load_state_dict() read for it before it existed
-        self._work, self._guard, self._guard_counts = None, None, None
-        # load_state_dict() parks what it read here until the store it belongs to exists (the arena is built by the first
-        # forward, the stores by the first step): id(param) -> {"step","m","v"} in LOGICAL layout, and the device step state
-        # of the capturable path per store, keyed by the store's first parameter
-        self._pending, self._pending_dev = {}, {}
-        # weight average: one flat buffer "ema" per state store beside m and v, made by the first step; _pending_ema is what
-        # load_state_dict() read for it (id(param) -> average in LOGICAL layout) until then; _swapped while the weights
-        # and the averages have changed places
-        self._pending_ema, self._swapped, self._ema_told = {}, False, False
+        # the device record (made by the first step)
+        self._work, self._guard = None, None
+        self._parked = _Parked()       # a loaded checkpoint, until the stores it belongs to exist
+        # _swapped while the weights and the averages have changed places
+        self._swapped, self._ema_told = False, False
+
+    def store_of(self, owner):
+        """The state store of an arena or of a loose parameter; None before the first step that updates it."""
+        return self._stores.get(id(owner))
 
     def refresh_hyper(self):
         """Push (lr, betas, eps, weight_decay, grad_scale) to the device buffers of the capturable path if they changed."""
-        for group in self.param_groups:
-            for st in list(self._flat.values()) + [self.state[p] for p in group["params"] if p in self.state]:
-                if "hyper" in st and st.get("group") is group:
-                    self._push_hyper(st, group)
+        for st in self._stores.values():
+            if st.hyper is not None:
+                self._push_hyper(st, st.group)
 
     def _push_hyper(self, st, group):
         vals = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                 float(group["weight_decay"]), float(self.grad_scale))
-        if st.get("hyper_host") != vals:
-            if torch.cuda.is_current_stream_capturing():
-                raise GdnError("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
-            st["hyper"].copy_(torch.tensor(vals, dtype=torch.float32))
-            st["hyper_host"] = vals
+        if st.hyper_host != vals:
+            _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
+            st.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+            st.hyper_host = vals
 
     def _arena_groups(self, group):
         """Split a param group into (arena, covers_whole_arena) and stragglers."""
@@ -102,58 +302,43 @@ class Adam(torch.optim.Optimizer):
                 loose.append(p)
         return arenas, loose
 
-    @staticmethod
-    def _dev_state(group, t, device):
-        """{double beta1^t, double beta2^t, int32 t, float bc1, float bc2s} for `t` steps TAKEN so far (the kernel advances it
-        before it uses it)."""
-        import struct
-        if torch.cuda.is_current_stream_capturing():
-            raise GdnError("capturable Adam: a device step counter would be created (and reset by every replay) inside a graph "
-                           "capture; run one eager step with the same gradient coverage first")
-        b1, b2 = group["betas"]
-        raw = struct.pack("<ddiff", float(b1) ** t, float(b2) ** t, t, 0.0, 0.0)
-        return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
-
-    def _ensure_dev(self, st, group, device, steps_taken):
-        """Device-side step state of the capturable path for one state store: hyper float32[6] and the step state of
-        _dev_state(); `steps_taken` = the host-side count of updates this store has had (a resume folds it in by advancing the
-        powers on the host first)."""
-        if "hyper" not in st:
-            st["hyper"] = torch.zeros(6, dtype=torch.float32, device=device)
-            if "state" not in st:          # (a loaded checkpoint brings the device's own bytes: _fill_arena / _fill_loose)
-                st["state"] = self._dev_state(group, steps_taken, device)
-            st["group"] = group
+    def _ensure_dev(self, st, group, steps_taken):
+        """Device side of the capturable path for one store: hyper float32[6] and the step state; `steps_taken` = the
+        host-side count of updates this store has had (a resume folds it in by advancing the powers on the host first)."""
+        if st.hyper is None:
+            st.hyper = torch.zeros(6, dtype=torch.float32, device=st.device)
+            if st.state is None:           # (a loaded checkpoint brings the device's own bytes: _Store.take_record)
+                st.state = _step_state(group, steps_taken, st.device)
+            st.group = group
         self._push_hyper(st, group)
 
-    def _apply(self, pdata, grad, st, group, device):
-        b1, b2 = group["betas"]
-        if self.capturable:
-            self._ensure_dev(st, group, device, st["step"] - 1)      # (step() has counted this update already)
-            st["full_dev"] = True         # the store's device counter has taken every update so far: a valid thing to copy
-            self._launch_dev(pdata, grad, st["m"], st["v"], st["hyper"], st["state"], st.get("ema"))
+    def _update(self, st, group, grad, item=None):
+        """One update of store `st` with `grad` (in the weights' physical layout): the whole store, or `item` of it with
+        that parameter's own step count.  Host path: launched now.  Capturable: launched now, followed by the update of
+        the same range of the weight average from the same step state, or -- guarded -- gathered until the norm of ALL
+        gradients is known."""
+        if item is None:
+            w, m, v, ema, count, state = st.weights, st.m, st.v, st.ema, st.step, st.state
         else:
-            ops.adam_step(pdata, grad, st["m"], st["v"], group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                          st["step"], self.grad_scale)
-
-    def _launch_dev(self, pdata, grad, m, v, hyper, state, ema=None):
-        """One capturable update: launched now, or -- guarded -- gathered until the norm of ALL gradients is known.  `ema`:
-        the slice of the weight average that belongs to `pdata`, updated right after it from the same step state."""
-        if self._work is None:
-            ops.adam_step_dev(pdata, grad, m, v, hyper, state)
+            p, o, n, _ = item
+            w, m, v, ema = st.weights[o:o + n], st.m[o:o + n], st.v[o:o + n], None if st.ema is None else st.ema[o:o + n]
+            count, state = st.pstep[id(p)], st.pdev.get(id(p))
+        if not self.capturable:
+            b1, b2 = group["betas"]
+            ops.adam_step(w, grad, m, v, group["lr"], b1, b2, group["eps"], group["weight_decay"], count, self.grad_scale)
+        elif self._work is not None:
+            self._work.append((w, grad, m, v, st.hyper, state, ema))
+        else:
+            ops.adam_step_dev(w, grad, m, v, st.hyper, state)
             if ema is not None:
-                ops.ema_update(ema, pdata, self.ema_decay, state)
-        else:
-            self._work.append((pdata, grad, m, v, hyper, state, ema))
+                ops.ema_update(ema, w, self.ema_decay, state)
 
     def _guard_record(self, device):
         if self._guard is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise GdnError("guarded Adam: the guard record would be created (and reset by every replay) inside a graph "
-                               "capture; run one eager step first")
-            steps, clipped, skipped = self._guard_counts or (0, 0, 0)
-            raw = struct.pack(_GUARD_FMT, 0.0, 0.0, 1.0, 0, steps, clipped, skipped)
-            self._guard = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
-            self._guard_counts = None
+            _no_capture("guarded Adam: the guard record would be created (and reset by every replay) inside a graph "
+                        "capture; run one eager step first")
+            self._guard = _guard_bytes(*(self._parked.guard or (0, 0, 0))).to(device)
+            self._parked.guard = None
         elif self._guard.device != device:
             raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (self._guard.device, device))
         return self._guard
@@ -180,45 +365,17 @@ class Adam(torch.optim.Optimizer):
         the run.  One small device-to-host copy, i.e. a sync: for print cadence, not for every step; not inside a capture."""
         if not self.guarded:
             raise GdnError("guard_stats(): this optimizer has no gradient guard (max_grad_norm / skip_nonfinite)")
-        self._refuse_capture("guard_stats()")
+        _no_capture("optimizer guard_stats() inside a graph capture")
         if self._guard is None:
-            steps, clipped, skipped = self._guard_counts or (0, 0, 0)
+            steps, clipped, skipped = self._parked.guard or (0, 0, 0)
             return {"norm": 0.0, "coef": 1.0, "steps": steps, "clipped": clipped, "skipped": skipped}
-        _, norm, coef, _, steps, clipped, skipped = struct.unpack(_GUARD_FMT, self._guard.cpu().numpy().tobytes())
+        _, norm, coef, _, steps, clipped, skipped = _unpack(_GUARD_FMT, self._guard)
         return {"norm": norm, "coef": coef, "steps": steps, "clipped": clipped, "skipped": skipped}
 
     # ---- weight average ----------------------------------------------------------------------------------------------
-    def _ensure_ema(self, st, weights, ar, p=None):
-        """The average of one store, made by its first step as a copy of the weights BEFORE that step's update (avg_0 = p_0,
-        same physical layout), then overwritten with what load_state_dict() read for it."""
-        if self.ema_decay is None or "ema" in st:
-            return
-        if torch.cuda.is_current_stream_capturing():
-            raise GdnError("Adam(ema_decay): the weight average would be created inside a graph capture; run one eager step "
-                           "with the same gradient coverage first")
-        st["ema"] = weights.detach().clone(memory_format=torch.preserve_format)
-        if ar is None:
-            avg = self._pending_ema.pop(id(p), None)
-            if avg is not None:
-                st["ema"].copy_(avg)
-            return
-        for q, o, n, tr in ar.items:
-            avg = self._pending_ema.pop(id(q), None)
-            if avg is not None:
-                ar._view(st["ema"], o, q.shape, tr).copy_(avg)
-
     def _ema_views(self):
         """id(param) -> its average as a view in the parameter's logical shape, for every parameter a store averages."""
-        out = {}
-        for kind, st, ar, ps in self._stores():
-            if "ema" not in st:
-                continue
-            if kind == "arena":
-                for p, o, n, tr in ar.items:
-                    out[id(p)] = ar._view(st["ema"], o, p.shape, tr)
-            else:
-                out[id(ps[0])] = st["ema"]
-        return out
+        return {id(item[0]): st.view(st.ema, item) for st in self._live_stores() if st.ema is not None for item in st.items}
 
     def averaged(self, p):
         """The average of parameter `p`, in its logical shape: a view of the store's buffer once a step has made it; before
@@ -226,10 +383,12 @@ class Adam(torch.optim.Optimizer):
         effect the buffer holds the raw weights instead."""
         if self.ema_decay is None:
             raise GdnError("averaged(): this optimizer keeps no weight average (ema_decay)")
-        v = self._ema_views().get(id(p))
-        if v is not None:
-            return v
-        avg = self._pending_ema.get(id(p))
+        return self._averaged(p, self._ema_views())
+
+    def _averaged(self, p, views):
+        avg = views.get(id(p))
+        if avg is None:
+            avg = self._parked.averages.get(id(p))
         return avg if avg is not None else p.detach()
 
     def swap_averaged(self):
@@ -238,18 +397,14 @@ class Adam(torch.optim.Optimizer):
         their value.  Between the two calls step(), state_dict() and load_state_dict() raise.  Not inside a graph capture."""
         if self.ema_decay is None:
             raise GdnError("swap_averaged(): this optimizer keeps no weight average (ema_decay)")
-        self._refuse_capture("swap_averaged()")
-        if any(pid in self._pending for pid in self._pending_ema):
-            # (a parameter that never took a step has no moments waiting either: its average is its value)
+        _no_capture("optimizer swap_averaged() inside a graph capture")
+        if self._parked.averages_wait_for_a_step():
             raise GdnError("swap_averaged(): averages read from a checkpoint are put in place by the first step after "
                            "load_state_dict(); take one step first")
-        for kind, st, ar, ps in self._stores():
-            if "ema" not in st:
-                continue
-            ops.swap_(ar.data if kind == "arena" else ps[0].data, st["ema"])
-            arena = ar if kind == "arena" else getattr(ps[0], "_gdn_arena", None)
-            if arena is not None:
-                arena.touch()     # the weights changed behind torch's back: bf16 shadow, eval-BatchNorm coefficients
+        for st in self._live_stores():
+            if st.ema is not None:
+                ops.swap_(st.weights, st.ema)
+                st.touch()
         self._swapped = not self._swapped
 
     @contextlib.contextmanager
@@ -265,24 +420,25 @@ class Adam(torch.optim.Optimizer):
         if self._swapped:
             raise GdnError("optimizer %s while weights and averages are exchanged: call swap_averaged() again first" % what)
 
-    def _step_partial(self, ar, st, group):
+    # ---- the step ----------------------------------------------------------------------------------------------------
+    def _step_partial(self, st, group):
         """Per-tensor updates ON SLICES OF THE FLAT MOMENTS for the parameters that have a gradient (torch.optim.Adam skips
         the others).  Host path: per-parameter step counts (`pstep`), back to the one-launch update once every parameter
         THAT TAKES GRADIENTS is level again.  Capturable path: the step counter is device memory, so each parameter gets a
         device state of its own -- a stream-ordered copy of the arena's when the one-launch path ran before -- and the
         arena stays on per-tensor launches from then on (replays advance those counters behind the host's back, so the
         host cannot tell when they are level)."""
-        if st["pstep"] is None:
-            st["pstep"] = {id(p): st["step"] for p, _, _, _ in ar.items}
-        b1, b2 = group["betas"]
+        ar = st.arena
+        if st.pstep is None:
+            st.pstep = {id(p): st.step for p, _, _, _ in st.items}
         if self.capturable:
             # ADVICE r4: the arena's device counter may be copied only if the one-launch path has driven it (then it also holds
             # the updates that graph replays made behind the host's back); when the very first step is already partial, there
             # is no such counter and every parameter starts from its host count
-            had_dev = bool(st.get("full_dev"))
-            self._ensure_dev(st, group, ar.device, st["step"])
-            pdev = st.setdefault("pdev", {})
-        for p, o, n, tr in ar.items:
+            had_dev = st.full_dev
+            self._ensure_dev(st, group, st.step)
+        for item in st.items:
+            p, o, n, _ = item
             if p.grad is None:
                 continue
             g = p.grad
@@ -290,30 +446,22 @@ class Adam(torch.optim.Optimizer):
             if g.data_ptr() != gslice.data_ptr():
                 # a caller-owned gradient: bring it into the parameter's physical (tap-major) order
                 gslice = torch.empty_like(p, memory_format=torch.preserve_format).copy_(g)
-            st["pstep"][id(p)] += 1
-            if self.capturable:
-                ds = pdev.get(id(p))
-                if ds is None:
-                    if had_dev:
-                        if torch.cuda.is_current_stream_capturing():
-                            raise GdnError("capturable Adam: a per-parameter step counter would be created inside a graph capture "
-                                           "(every replay would reset it); run one eager step with this gradient coverage first")
-                        ds = st["state"].clone()          # the arena's device counter so far (no host read)
-                    else:
-                        ds = self._dev_state(group, st["pstep"][id(p)] - 1, ar.device)
-                    pdev[id(p)] = ds
-                self._launch_dev(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], st["hyper"], ds,
-                                 st["ema"][o:o + n] if "ema" in st else None)
-            else:
-                ops.adam_step(ar.data[o:o + n], gslice, st["m"][o:o + n], st["v"][o:o + n], group["lr"], b1, b2, group["eps"],
-                              group["weight_decay"], st["pstep"][id(p)], self.grad_scale)
+            st.pstep[id(p)] += 1
+            if self.capturable and id(p) not in st.pdev:
+                if had_dev:
+                    _no_capture("capturable Adam: a per-parameter step counter would be created inside a graph capture "
+                                "(every replay would reset it); run one eager step with this gradient coverage first")
+                    st.pdev[id(p)] = st.state.clone()         # the arena's device counter so far (no host read)
+                else:
+                    st.pdev[id(p)] = _step_state(group, st.pstep[id(p)] - 1, st.device)
+            self._update(st, group, gslice, item)
         if self.capturable:
             return
-        counts = {st["pstep"][id(p)] for p, _, _, _ in ar.items if p.requires_grad}     # (a frozen parameter never levels)
+        counts = {st.pstep[id(p)] for p, _, _, _ in st.items if p.requires_grad}        # (a frozen parameter never levels)
         if len(counts) == 1:              # everyone who steps is level again: back to the one-launch update
             lvl = counts.pop()
-            if all(st["pstep"][id(p)] == lvl for p, _, _, _ in ar.items):
-                st["step"], st["pstep"] = lvl, None
+            if all(c == lvl for c in st.pstep.values()):
+                st.step, st.pstep = lvl, None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -337,7 +485,6 @@ class Adam(torch.optim.Optimizer):
 
     def _step_groups(self):
         for group in self.param_groups:
-            b1, b2 = group["betas"]
             arenas, loose = self._arena_groups(group)
             for ar, ps in arenas.values():
                 if getattr(ar, "carry_reduced", None) is not None:
@@ -347,149 +494,112 @@ class Adam(torch.optim.Optimizer):
                                    "sync_gradients() after the last backward of an accumulation")
                 if len(ps) != len(ar.items):
                     loose.extend(ps)      # partial coverage: fall back to per-tensor launches
-                    continue
-                if all(p.grad is None for p in ps):
-                    continue              # nothing ran backward for this model: skip it, like torch.optim.Adam
-                st = self._flat.get(id(ar))
-                if st is None:
-                    # ONE state store per arena: flat moments; `pstep` is None while every parameter has taken the same
-                    # number of steps (st["step"]) and becomes a per-parameter count once coverage has been partial
-                    st = {"m": ops.zeros((ar.numel,), ar.device), "v": ops.zeros((ar.numel,), ar.device), "step": 0,
-                          "pstep": None}
-                    self._flat[id(ar)] = st
-                    self._fill_arena(ar, st)          # a checkpoint loaded before this store existed
-                self._ensure_ema(st, ar.data, ar)
-                if st["pstep"] is None and all(p.grad is not None for p in ps):
-                    st["step"] += 1
-                    self._apply(ar.data, ar.grad, st, group, ar.device)
                 else:
-                    # part of the model got no gradient this step (frozen sub-modules, an unused branch): torch.optim.Adam
-                    # skips those parameters -- the one-launch update would apply weight decay and stale moments to them.
-                    # The others are updated per tensor ON SLICES OF THE SAME FLAT MOMENTS with their own step counts, so a
-                    # parameter never alternates between two sets of moments when coverage changes between steps.
-                    self._step_partial(ar, st, group)
-                ar.touch()        # the kernel wrote the parameters behind torch's back: bf16 shadows are stale
+                    self._step_store(group, ar.items, ar)
             for p in loose:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda:
-                    raise GdnError("fused Adam needs GPU parameters: the HIP path has no CPU fallback")
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["m"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["v"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    self._fill_loose(p, st)
-                self._ensure_ema(st, p.data, None, p)
-                st["step"] += 1
-                g = p.grad
-                if g.stride() != p.stride():
-                    g = torch.empty_like(p, memory_format=torch.preserve_format).copy_(g)
-                self._apply(p.data, g, st, group, p.device)
-                if getattr(p, "_gdn_arena", None) is not None:
-                    p._gdn_arena.touch()
+                self._step_store(group, [(p, 0, p.numel(), None)])
+
+    def _new_store(self, items, arena=None):
+        """ONE state store per arena, one per loose parameter, filled with what a checkpoint loaded before it existed
+        brought for it."""
+        st = _Store(items, arena)
+        st.fill(self._parked, self.capturable, self.ema_decay is not None)
+        return st
+
+    def _step_store(self, group, items, ar=None):
+        """This step's update of one arena (`items` are all of its parameters) or of one loose parameter."""
+        have = sum(p.grad is not None for p, _, _, _ in items)
+        if have == 0:
+            return                    # nothing ran backward for this model: skip it, like torch.optim.Adam
+        owner = ar if ar is not None else items[0][0]
+        if ar is None and not owner.is_cuda:
+            raise GdnError("fused Adam needs GPU parameters: the HIP path has no CPU fallback")
+        st = self._stores.get(id(owner))
+        if st is None:
+            st = self._stores[id(owner)] = self._new_store(items, ar)
+        if st.pstep is None and have == len(items):
+            st.step += 1
+            if ar is not None:
+                grad = ar.grad
+            else:
+                grad = owner.grad
+                if grad.stride() != owner.stride():
+                    grad = torch.empty_like(owner, memory_format=torch.preserve_format).copy_(grad)
+            if self.capturable:
+                self._ensure_dev(st, group, st.step - 1)      # (this update is counted already)
+                st.full_dev = True        # the store's device counter has taken every update so far: a valid thing to copy
+            self._update(st, group, grad)
+        else:
+            # part of the model got no gradient this step (frozen sub-modules, an unused branch): torch.optim.Adam
+            # skips those parameters -- the one-launch update would apply weight decay and stale moments to them.
+            # The others are updated per tensor ON SLICES OF THE SAME FLAT MOMENTS with their own step counts, so a
+            # parameter never alternates between two sets of moments when coverage changes between steps.
+            self._step_partial(st, group)
+        st.touch()            # the kernel wrote the parameters behind torch's back: bf16 shadows are stale
+
+    # ---- host counts under a graph (graph.py; DESIGN.md 3.4) --------------------------------------------------------------
+    def host_counts(self):
+        """The host-side update counts of every store (step() advances them; a capture runs step()'s host code once
+        without executing anything, a replay executes it without running the host code)."""
+        return [(st,) + st.counts() for st in self._stores.values()]
+
+    def take_back_counts(self, before):
+        """Undo what a capture added to the host counts since host_counts() gave `before`; returns it as the per-replay
+        increments for count_replay()."""
+        return [(st,) + st.take_back(step, pstep) for st, step, pstep in before]
+
+    def count_replay(self, increments):
+        for st, dstep, dp in increments:
+            st.advance(dstep, dp)
 
     # ------------------------------------------------------------------------------------------------------------------
     # state exchange: torch.optim.Adam's format ({'state': {index: {'step','exp_avg','exp_avg_sq'}}, 'param_groups'}),
     # moments in each parameter's LOGICAL shape, plus a private 'gdn' key for what that format has no place for
     # ------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _refuse_capture(what):
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise GdnError("optimizer %s inside a graph capture" % what)
-
-    @staticmethod
-    def _f32(x):
-        """`x` as the kernels receive it: rounded to float32."""
-        import struct
-        return struct.unpack("<f", struct.pack("<f", float(x)))[0]
-
-    @staticmethod
-    def _dev_count(state):
-        """The step count a device step state holds (the int32 after the two doubles of _dev_state)."""
-        import struct
-        return struct.unpack_from("<i", state.cpu().numpy().tobytes(), 16)[0]
-
-    def _stores(self):
-        """(kind, store, arena or None, [params]) for every state store, parameters in param_groups order within a store."""
+    def _live_stores(self):
+        """Every store that holds the state of this optimizer's parameters as they are grouped and laid out now, parameters
+        in param_groups order within a store."""
         out = []
         for group in self.param_groups:
             arenas, loose = self._arena_groups(group)
             for ar, ps in arenas.values():
-                st = self._flat.get(id(ar))
-                if st is not None and len(ps) == len(ar.items):
-                    out.append(("arena", st, ar, [p for p, _, _, _ in ar.items]))
+                if id(ar) in self._stores and len(ps) == len(ar.items):
+                    out.append(self._stores[id(ar)])
                 else:
                     loose.extend(ps)
-            for p in loose:
-                st = self.state.get(p)
-                if st:
-                    out.append(("loose", st, None, [p]))
+            out.extend(self._stores[id(p)] for p in loose if id(p) in self._stores)
         return out
-
-    def _count(self, st, p, memo):
-        """Updates parameter `p` of store `st` has taken: the device's count where the capturable path keeps one (graph
-        replays advance it behind the host's back), the host's otherwise."""
-        def dev(t):
-            if id(t) not in memo:
-                memo[id(t)] = self._dev_count(t)
-            return memo[id(t)]
-        pstep = st.get("pstep")
-        if "state" in st:
-            if pstep is None:
-                return dev(st["state"])
-            own = st.get("pdev", {}).get(id(p))
-            if own is not None:
-                return dev(own)
-            if st.get("full_dev"):
-                return dev(st["state"])       # no counter of its own yet: the arena's, frozen when coverage split
-        return st["step"] if pstep is None else pstep[id(p)]
 
     def state_dict(self):
         """torch.optim.Adam's state_dict with the real moments (logical shape, contiguous; 'step' a float32 scalar tensor like
         torch's) and a 'gdn' key: host step counts, grad_scale and -- capturable path -- the device step state's bytes."""
-        self._refuse_capture("state_dict()")
+        _no_capture("optimizer state_dict() inside a graph capture")
         self._refuse_swapped("state_dict()")
-        index, k = {}, 0
-        for g in self.param_groups:
-            for p in g["params"]:
-                index[id(p)] = k
-                k += 1
+        params = [p for g in self.param_groups for p in g["params"]]
+        index = {id(p): k for k, p in enumerate(params)}
         groups = []
         for g in self.param_groups:
             packed = {key: v for key, v in g.items() if key != "params"}
             # the betas the moments were accumulated with: the kernels take them as float32, and 1 - beta2 is where that shows
             # (1 - float32(0.999) is 1.29e-5 below 0.001); an optimizer that goes on from these moments with the rounded
             # values continues the same Adam run to rounding
-            packed["betas"] = tuple(self._f32(b) for b in g["betas"])
+            packed["betas"] = tuple(_f32(b) for b in g["betas"])
             packed["params"] = [index[id(p)] for p in g["params"]]
             groups.append(packed)
+
+        def entry(step, m, v):
+            return {"step": torch.tensor(float(step)), "exp_avg": m.detach().clone(memory_format=torch.contiguous_format),
+                    "exp_avg_sq": v.detach().clone(memory_format=torch.contiguous_format)}
         state, recs, memo = {}, [], {}
-        for kind, st, ar, ps in self._stores():
-            if kind == "arena":
-                views = {id(p): (ar._view(st["m"], o, p.shape, tr), ar._view(st["v"], o, p.shape, tr)) for p, o, n, tr in ar.items}
-            else:
-                views = {id(ps[0]): (st["m"], st["v"])}
-            for p in ps:
-                m, v = views[id(p)]
-                state[index[id(p)]] = {"step": torch.tensor(float(self._count(st, p, memo))),
-                                       "exp_avg": m.detach().clone(memory_format=torch.contiguous_format),
-                                       "exp_avg_sq": v.detach().clone(memory_format=torch.contiguous_format)}
-            pstep = st.get("pstep")
-            recs.append({"kind": kind, "params": [index[id(p)] for p in ps], "step": int(st["step"]),
-                         "pstep": None if pstep is None else [int(pstep[id(p)]) for p in ps],
-                         "full_dev": bool(st.get("full_dev")),
-                         "state": st["state"].detach().cpu().clone() if "state" in st else None,
-                         "pdev": {index[id(p)]: st["pdev"][id(p)].detach().cpu().clone() for p in ps
-                                  if id(p) in st.get("pdev", {})}})
+        for st in self._live_stores():
+            for item in st.items:
+                state[index[id(item[0])]] = entry(st.count(item[0], memo), st.view(st.m, item), st.view(st.v, item))
+            recs.append(st.record(index))
         # loaded, but no step since: hand back what was loaded
-        byid = {id(p): p for g in self.param_groups for p in g["params"]}
-        for pid, s in self._pending.items():
-            if pid in byid and index[pid] not in state:
-                state[index[pid]] = {"step": torch.tensor(float(s["step"])),
-                                     "exp_avg": s["m"].detach().clone(memory_format=torch.contiguous_format),
-                                     "exp_avg_sq": s["v"].detach().clone(memory_format=torch.contiguous_format)}
-        for rec in self._pending_dev.values():
+        for pid, s in self._parked.moments.items():
+            if pid in index and index[pid] not in state:
+                state[index[pid]] = entry(s["step"], s["m"], s["v"])
+        for rec in self._parked.records.values():
             recs.append(dict(rec, params=[index[i] for i in rec["params"]],
                              pdev={index[i]: t for i, t in rec["pdev"].items()}))
         priv = {"version": 1, "capturable": self.capturable, "grad_scale": float(self.grad_scale), "stores": recs}
@@ -498,18 +608,11 @@ class Adam(torch.optim.Optimizer):
             priv["guard"] = {"max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite,
                              "steps": gs["steps"], "clipped": gs["clipped"], "skipped": gs["skipped"]}
         if self.ema_decay is not None:
-            # every parameter, so the averaged model can be put together from this key alone
+            # every parameter, so the averaged model can be put together from this key alone (no update yet: avg_0 = p_0)
             views = self._ema_views()
-            avg = {}
-            for g in self.param_groups:
-                for p in g["params"]:
-                    a = views.get(id(p))
-                    if a is None:
-                        a = self._pending_ema.get(id(p))
-                    if a is None:
-                        a = p         # no update yet: avg_0 = p_0
-                    avg[index[id(p)]] = a.detach().clone(memory_format=torch.contiguous_format)
-            priv["ema"] = {"decay": self.ema_decay, "avg": avg}
+            priv["ema"] = {"decay": self.ema_decay,
+                           "avg": {index[id(p)]: self._averaged(p, views).detach().clone(memory_format=torch.contiguous_format)
+                                   for p in params}}
         return {"state": dict(sorted(state.items())), "param_groups": groups, "gdn": priv}
 
     def load_state_dict(self, state_dict):
@@ -519,7 +622,7 @@ class Adam(torch.optim.Optimizer):
         device step state is restored byte for byte; without it (a torch checkpoint) it is recomputed on the host from
         'step'.  Hyper-parameters of the groups are taken from the checkpoint (betas only if they differ in float32).  Not inside a graph capture; a graph captured
         before the load still holds the old device step state -- capture after loading."""
-        self._refuse_capture("load_state_dict()")
+        _no_capture("optimizer load_state_dict() inside a graph capture")
         self._refuse_swapped("load_state_dict()")
         groups = state_dict["param_groups"]
         mine = [len(g["params"]) for g in self.param_groups]
@@ -529,7 +632,7 @@ class Adam(torch.optim.Optimizer):
                            "groups %s" % (sum(theirs), theirs, sum(mine), mine))
         params = [p for g in self.param_groups for p in g["params"]]
         by_saved = dict(zip([i for g in groups for i in g["params"]], params))
-        pending = {}
+        parked = _Parked(self._parked.guard)
         for key, s in state_dict["state"].items():
             p = by_saved.get(key)
             if p is None:
@@ -538,34 +641,30 @@ class Adam(torch.optim.Optimizer):
                 if tuple(s[name].shape) != tuple(p.shape):
                     raise GdnError("optimizer state %r of parameter %r has shape %s, the parameter has %s" %
                                    (name, key, tuple(s[name].shape), tuple(p.shape)))
-            pending[id(p)] = {"step": int(round(float(s["step"]))), "m": s["exp_avg"].detach(), "v": s["exp_avg_sq"].detach()}
+            parked.moments[id(p)] = {"step": int(round(float(s["step"]))), "m": s["exp_avg"].detach(), "v": s["exp_avg_sq"].detach()}
         for g, saved in zip(self.param_groups, groups):
             for key, v in saved.items():
                 if key == "betas":
                     # betas that round to this optimizer's own in float32 are the same to the kernels: keep the own spelling (the
                     # capturable path computes its host-side powers from it, as the uninterrupted run does)
-                    if [self._f32(b) for b in v] != [self._f32(b) for b in g["betas"]]:
+                    if [_f32(b) for b in v] != [_f32(b) for b in g["betas"]]:
                         g["betas"] = tuple(v)
                 elif key != "params":
                     g[key] = v
         priv = state_dict.get("gdn") or {}
         self.grad_scale = float(priv.get("grad_scale", self.grad_scale))
-        pending_dev = {}
         for rec in priv.get("stores", []):
             ids = [id(by_saved[i]) for i in rec["params"] if i in by_saved]
             if len(ids) != len(rec["params"]) or not ids:
                 continue
-            pending_dev[ids[0]] = dict(rec, params=ids, pdev={id(by_saved[i]): t for i, t in rec["pdev"].items()})
-        self._pending, self._pending_dev = pending, pending_dev
+            parked.records[ids[0]] = dict(rec, params=ids, pdev={id(by_saved[i]): t for i, t in rec["pdev"].items()})
         if self.guarded and priv.get("guard") is not None:
             # the run's counts go on; max_grad_norm / skip_nonfinite stay this optimizer's own (constructor arguments)
-            self._guard_counts = tuple(int(priv["guard"][k]) for k in ("steps", "clipped", "skipped"))
+            parked.guard = tuple(int(priv["guard"][k]) for k in ("steps", "clipped", "skipped"))
             if self._guard is not None:
-                raw = struct.pack(_GUARD_FMT, 0.0, 0.0, 1.0, 0, *self._guard_counts)
-                self._guard.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-                self._guard_counts = None
+                self._guard.copy_(_guard_bytes(*parked.guard))
+                parked.guard = None
         # the averages (ema_decay stays the constructor's): parked like the moments; an optimizer without ema_decay ignores them
-        self._pending_ema = {}
         if self.ema_decay is not None:
             saved = (priv.get("ema") or {}).get("avg")
             if saved is None:
@@ -580,84 +679,12 @@ class Adam(torch.optim.Optimizer):
                     if tuple(a.shape) != tuple(p.shape):
                         raise GdnError("weight average of parameter %r has shape %s, the parameter has %s" %
                                        (key, tuple(a.shape), tuple(p.shape)))
-                    self._pending_ema[id(p)] = a.detach()
+                    parked.averages[id(p)] = a.detach()
+        self._parked = parked
         # stores that exist: rewrite them now; parameters without a saved state start over
-        for kind, st, ar, ps in self._stores():
-            if kind == "arena":
-                self._fill_arena(ar, st, reset=True)
-            else:
-                self._fill_loose(ps[0], st, reset=True)
-            if "ema" in st:
-                self._fill_ema(kind, st, ar, ps)
+        for st in self._live_stores():
+            st.fill(parked, self.capturable, self.ema_decay is not None, reset=True)
         for p in params:
             ar = getattr(p, "_gdn_arena", None)
             if ar is not None:
                 ar.touch()
-
-    def _fill_ema(self, kind, st, ar, ps):
-        """Rewrite the average of a store that exists: what load_state_dict() read, through each parameter's own view; the
-        weights as they are now where it read nothing."""
-        st["ema"].copy_(ar.data if kind == "arena" else ps[0].data)
-        items = ar.items if kind == "arena" else [(ps[0], 0, 0, None)]
-        for p, o, n, tr in items:
-            avg = self._pending_ema.pop(id(p), None)
-            if avg is not None:
-                (ar._view(st["ema"], o, p.shape, tr) if kind == "arena" else st["ema"]).copy_(avg)
-
-    def _take_dev(self, st, rec, device):
-        """Host counts and -- capturable -- the device step state of a store, from its 'gdn' record.  False: no usable record
-        (a torch checkpoint, or device counts saved by a capturable optimizer and read by a host-side one), the counts come
-        from 'step'."""
-        for key in ("hyper", "hyper_host", "state", "pdev", "full_dev", "group"):
-            st.pop(key, None)
-        if rec is None or (rec.get("state") is not None and not self.capturable):
-            return False
-        st["step"] = int(rec["step"])
-        st["pstep"] = None if rec["pstep"] is None else dict(zip(rec["params"], [int(c) for c in rec["pstep"]]))
-        if rec.get("state") is not None:
-            st["state"] = rec["state"].to(device=device, copy=True)        # the device's own bytes, verbatim
-            st["full_dev"] = bool(rec["full_dev"])
-            if rec["pstep"] is not None:
-                st["pdev"] = {pid: t.to(device=device, copy=True) for pid, t in rec["pdev"].items()}
-        return True
-
-    def _fill_arena(self, ar, st, reset=False):
-        """Write what load_state_dict() read for this arena's parameters into its flat store: each moment through the
-        parameter's own view of the flat buffer (tap-major for convolution weights), never under a logical shape."""
-        ids = [id(p) for p, _, _, _ in ar.items]
-        if not reset and not any(i in self._pending for i in ids):
-            return
-        st["m"].zero_()
-        st["v"].zero_()
-        counts = {}
-        for p, o, n, tr in ar.items:
-            s = self._pending.pop(id(p), None)
-            counts[id(p)] = s["step"] if s else 0
-            if s:
-                ar._view(st["m"], o, p.shape, tr).copy_(s["m"])
-                ar._view(st["v"], o, p.shape, tr).copy_(s["v"])
-        rec = self._pending_dev.pop(ids[0], None)
-        if rec is not None and (rec["kind"] != "arena" or rec["params"] != ids):
-            rec = None
-        if not self._take_dev(st, rec, ar.device):
-            level = set(counts.values())
-            if len(level) == 1:
-                st["step"], st["pstep"] = level.pop(), None
-            else:
-                st["step"], st["pstep"] = max(level), counts
-
-    def _fill_loose(self, p, st, reset=False):
-        s = self._pending.pop(id(p), None)
-        if s is None and not reset:
-            return
-        st["m"].zero_()
-        st["v"].zero_()
-        st["step"] = s["step"] if s else 0
-        if s:
-            st["m"].copy_(s["m"])
-            st["v"].copy_(s["v"])
-        rec = self._pending_dev.pop(id(p), None)
-        if rec is not None and (rec["kind"] != "loose" or rec["params"] != [id(p)]):
-            rec = None
-        self._take_dev(st, rec, p.device)
-        st.pop("pstep", None)

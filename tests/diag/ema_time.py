@@ -43,7 +43,7 @@ nbytes = 4 * ar.numel
 kw = dict(lr=2e-5, betas=[0.9, 0.999], eps=1e-8, weight_decay=5e-4)
 plain, ema = Adam(model.parameters(), capturable=True, **kw), Adam(model.parameters(), ema_decay=0.999, **kw)
 ema.step()                                        # (makes the average)
-st = ema._flat[id(ar)]
+st = ema.store_of(ar)
 
 
 def two_swaps():
@@ -52,7 +52,7 @@ def two_swaps():
 
 
 calls = [("capturable", plain.step), ("ema", ema.step),
-         ("gdn_ema_update alone", lambda: ops.ema_update(st["ema"], ar.data, 0.999, st["state"])),
+         ("gdn_ema_update alone", lambda: ops.ema_update(st.ema, ar.data, 0.999, st.state)),
          ("two exchanges", two_swaps)]
 
 

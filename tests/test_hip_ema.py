@@ -175,8 +175,8 @@ def _loose(gpu, n, **kw):
 
 
 def _snapshot(p, opt):
-    st = opt.state[p]
-    return [p.detach().clone(), st["m"].clone(), st["v"].clone(), st["state"].clone()]
+    st = opt.store_of(p)
+    return [p.detach().clone(), st.m.clone(), st.v.clone(), st.state.clone()]
 
 
 def _same(a, b, what):
@@ -206,7 +206,7 @@ def test_ema_leaves_adam_alone(gpu):
         e64 = R.update(e64, p1.detach().cpu().numpy(), DECAY, k)
         M = np.maximum(M, np.maximum(np.abs(_np64(p1)), np.abs(e64)))
         assert np.all(np.abs(_np64(ema.averaged(p1)) - e64) <= R.bound(k, M)), k
-    assert "ema" not in plain.state[p0] and not torch.equal(ema.averaged(p1), p1.detach())
+    assert plain.store_of(p0).ema is None and not torch.equal(ema.averaged(p1), p1.detach())
 
 
 def test_guarded_ema_takes_the_same_skip_decision(gpu):
@@ -230,7 +230,7 @@ def test_guarded_ema_takes_the_same_skip_decision(gpu):
         after = ema.averaged(p1)
         if k == 2:
             assert torch.equal(after, before), "the skipped step moved the average"
-            assert ema._dev_count(ema.state[p1]["state"]) == 2
+            assert ema.store_of(p1).count(p1) == 2
             continue
         t += 1
         p_now = p1.detach().cpu().numpy()
@@ -241,7 +241,7 @@ def test_guarded_ema_takes_the_same_skip_decision(gpu):
             assert t == 3
             other = R.update(_np64(before), p_now, DECAY, 4)
             assert np.any(np.abs(_np64(after) - other) > R.bound(1, M)), "the step after the skipped one used weight(d, 4)"
-    assert ema.guard_stats()["skipped"] == 1 and ema._dev_count(ema.state[p1]["state"]) == 5
+    assert ema.guard_stats()["skipped"] == 1 and ema.store_of(p1).count(p1) == 5
 
 
 def test_matches_torch_adam_and_averaged_model(gpu):
@@ -317,7 +317,7 @@ def test_arena_one_launch_and_partial_coverage(gpu, base_model, batches):
     p0 = [p.detach().clone() for p in model.parameters()]
     _model_step(model, opt, batches[0])
     ar = model._gdn_param_arena
-    assert opt._flat[id(ar)]["pstep"] is None and any(tr is not None for _, _, _, tr in ar.items)
+    assert opt.store_of(ar).pstep is None and any(tr is not None for _, _, _, tr in ar.items)
     for (name, p), start in zip(model.named_parameters(), p0):
         assert opt.averaged(p).shape == p.shape, name
         _within(opt.averaged(p), start, p, 1, 1, "%s after one step" % name)
@@ -327,7 +327,7 @@ def test_arena_one_launch_and_partial_coverage(gpu, base_model, batches):
     e1 = [opt.averaged(p).clone() for p in model.parameters()]
     p1 = [p.detach().clone() for p in model.parameters()]
     _model_step(model, opt, batches[1])
-    assert opt._flat[id(ar)]["pstep"] is not None          # (the per-parameter path ran)
+    assert opt.store_of(ar).pstep is not None          # (the per-parameter path ran)
     for (name, p), e, w in zip(model.named_parameters(), e1, p1):
         if id(p) in frozen:
             assert torch.equal(p, w) and torch.equal(opt.averaged(p), e), "frozen %s moved" % name

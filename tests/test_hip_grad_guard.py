@@ -169,8 +169,8 @@ def _loose(gpu, n, **kw):
 
 
 def _snapshot(p, opt):
-    st = opt.state[p]
-    return [p.detach().clone(), st["m"].clone(), st["v"].clone(), st["state"].clone()]
+    st = opt.store_of(p)
+    return [p.detach().clone(), st.m.clone(), st.v.clone(), st.state.clone()]
 
 
 def _same(a, b, what):
@@ -228,7 +228,7 @@ def test_skipped_step_touches_nothing(gpu):
             five.step()
     _same(_snapshot(p, opt), _snapshot(q, five), "after six steps, one skipped")
     assert opt.guard_stats()["steps"] == 6 and opt.guard_stats()["skipped"] == 1 and five.guard_stats()["skipped"] == 0
-    assert opt._dev_count(opt.state[p]["state"]) == 5 and bool(torch.isfinite(p).all())
+    assert opt.store_of(p).count(p) == 5 and bool(torch.isfinite(p).all())
     r, through = _loose(gpu, n, max_grad_norm=10.0)
     r.grad = poisoned.to(gpu)
     through.step()
@@ -319,7 +319,7 @@ def test_arena_norm_and_partial_coverage(gpu, base_model, batches):
     assert abs(gs2["norm"] - ref2) <= U23 * ref2 and gs2["steps"] == 2
     for k, v in model2.res512_3.named_parameters():
         assert torch.equal(v, frozen[k]), "frozen parameter %s moved" % k
-    assert opt2._flat[id(model2._gdn_param_arena)]["pstep"] is not None          # (the per-parameter path ran)
+    assert opt2.store_of(model2._gdn_param_arena).pstep is not None          # (the per-parameter path ran)
 
 
 def test_arena_padding_contributes_nothing(gpu):
@@ -337,7 +337,7 @@ def test_arena_padding_contributes_nothing(gpu):
     before = ar.data.clone()
     opt = Adam(blk.parameters(), 1e-3, [0.9, 0.999], eps=1e-8, weight_decay=5e-4, max_grad_norm=1.0)
     opt.step()
-    assert id(ar) in opt._flat and opt._flat[id(ar)]["pstep"] is None            # (the one-launch path ran)
+    assert opt.store_of(ar) is not None and opt.store_of(ar).pstep is None            # (the one-launch path ran)
     ref = _norm_of_grads(blk.parameters())
     gs = opt.guard_stats()
     assert abs(gs["norm"] - ref) <= U23 * ref and gs["clipped"] == 1

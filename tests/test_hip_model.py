@@ -784,8 +784,9 @@ def test_adam_keeps_one_state_when_coverage_changes(gpu):
             torch.testing.assert_close(p.detach(), ref[k].detach(), rtol=2e-5, atol=2e-7, msg=lambda m, k=k, s=step: "%s step %d: %s" % (k, s, m))
             with torch.no_grad():
                 ref[k].copy_(p.detach())                         # same starting point for the next step's comparison
-    st = next(iter(opt._flat.values()))
-    assert st["pstep"] is not None and len(set(st["pstep"].values())) == 2      # res512_3 is one step behind, for good
+    st = opt.store_of(model._gdn_param_arena)
+    assert all(opt.store_of(p) is None for p in model.parameters())                    # (the arena's store is the only one)
+    assert st.pstep is not None and len(set(st.pstep.values())) == 2      # res512_3 is one step behind, for good
 
 
 @pytest.mark.parametrize("first_partial", [True, False])

@@ -83,7 +83,8 @@ class Run:
             epoch, first = epoch + 1, 0
 
     def flat(self):
-        (st,) = self.opt._flat.values()
+        st = self.opt.store_of(self.net._gdn_param_arena)
+        assert st is not None and all(self.opt.store_of(p) is None for p in self.net.parameters())      # (the only store)
         return st
 
 
@@ -101,8 +102,8 @@ def _same_state(a, b, what):
     for key in sa:                                   # running statistics and num_batches_tracked included
         assert torch.equal(sa[key], sb[key]), "%s: %s differs" % (what, key)
     fa, fb = a.flat(), b.flat()
-    assert torch.equal(fa["m"], fb["m"]) and torch.equal(fa["v"], fb["v"]), what + ": Adam's flat moments differ"
-    assert fa["step"] == fb["step"] and fa["pstep"] is None and fb["pstep"] is None, (what, fa["step"], fb["step"])
+    assert torch.equal(fa.m, fb.m) and torch.equal(fa.v, fb.v), what + ": Adam's flat moments differ"
+    assert fa.step == fb.step and fa.pstep is None and fb.pstep is None, (what, fa.step, fb.step)
 
 
 def _through_bytes(state):
@@ -166,7 +167,7 @@ def test_resume_capturable_adam_and_graphed_step(gpu):
     straight = Run(gpu, "DtoD", 7, capturable=True)
 
     def snap(k):
-        snaps[k] = ({key: v.clone() for key, v in straight.net.state_dict().items()}, straight.flat()["state"].clone())
+        snaps[k] = ({key: v.clone() for key, v in straight.net.state_dict().items()}, straight.flat().state.clone())
 
     want, _ = straight.train(6, after=snap)
     first = Run(gpu, "DtoD", 7, capturable=True)
@@ -179,7 +180,7 @@ def test_resume_capturable_adam_and_graphed_step(gpu):
     rest, _ = second.train(3, T.load_training_state(state, second.net, second.opt, second.loader))
     _same_records(got + rest, want, "capturable")
     _same_state(straight, second, "capturable")
-    assert torch.equal(second.flat()["state"], straight.flat()["state"])
+    assert torch.equal(second.flat().state, straight.flat().state)
     # --- restore again, then capture ---
     third = Run(gpu, "DtoD", 9, capturable=True)
     T.load_training_state(state, third.net, third.opt, third.loader)
@@ -188,7 +189,7 @@ def test_resume_capturable_adam_and_graphed_step(gpu):
     assert third.loader.last_params == want[3][1]
     for key, v in snaps[4][0].items():
         assert torch.equal(third.net.state_dict()[key], v), "after the warm-up step: " + key
-    assert torch.equal(third.flat()["state"], snaps[4][1])
+    assert torch.equal(third.flat().state, snaps[4][1])
     b5 = next(iter(third.loader))                      # epoch 3 begins: step 5
     terms = run(*b5)
     assert third.loader.last_params == want[4][1]
@@ -196,7 +197,7 @@ def test_resume_capturable_adam_and_graphed_step(gpu):
         assert torch.equal(a, b), (float(a), float(b))
     for key, v in snaps[5][0].items():
         assert torch.equal(third.net.state_dict()[key], v), "after the first replay: " + key
-    assert torch.equal(third.flat()["state"], snaps[5][1])
+    assert torch.equal(third.flat().state, snaps[5][1])
 
 
 def test_resume_with_partial_coverage(gpu):
@@ -209,7 +210,7 @@ def test_resume_with_partial_coverage(gpu):
 
     straight = Run(gpu, "DtoD", 7)
     want, _ = straight.train(6, before=freeze(straight))
-    counts = sorted(set(straight.flat()["pstep"].values()))
+    counts = sorted(set(straight.flat().pstep.values()))
     assert counts == [5, 6]
     first = Run(gpu, "DtoD", 7)
     got, progress = first.train(3, before=freeze(first))
@@ -222,10 +223,10 @@ def test_resume_with_partial_coverage(gpu):
     for key in sa:
         assert torch.equal(sa[key], sb[key]), key
     fa, fb = straight.flat(), second.flat()
-    assert torch.equal(fa["m"], fb["m"]) and torch.equal(fa["v"], fb["v"])
+    assert torch.equal(fa.m, fb.m) and torch.equal(fa.v, fb.v)
     names = {id(p): n for n, p in straight.net.named_parameters()}
     names2 = {n: id(p) for n, p in second.net.named_parameters()}
-    assert {n: fa["pstep"][i] for i, n in names.items()} == {n: fb["pstep"][i] for n, i in names2.items()}
+    assert {n: fa.pstep[i] for i, n in names.items()} == {n: fb.pstep[i] for n, i in names2.items()}
 
 
 def _three_steps_recording(gpu):
@@ -319,8 +320,9 @@ def test_optimizer_state_interop_with_torch_adam(gpu):
         for n, p in run.net.named_parameters():
             p.copy_(ref[n])                             # the same starting point
     both_step(back, "torch.optim.Adam state in optim.Adam")
-    (st,) = back._flat.values()
-    assert st["step"] == 5 and st["pstep"] is None
+    st = back.store_of(run.net._gdn_param_arena)
+    assert all(back.store_of(p) is None for p in run.net.parameters())                 # (the arena's store is the only one)
+    assert st.step == 5 and st.pstep is None
     print("\n".join(["%d parameter tensors miss the bar:" % len(misses)] + misses))
     assert not misses, "%d parameter tensors miss the bar, first: %s" % (len(misses), misses[0])
 

@@ -140,29 +140,31 @@ def _torch_state(net, steps=2):
     return opt.state_dict()
 
 
-def test_optimizer_state_goes_through_the_tap_major_layout():
+def test_optimizer_state_goes_through_the_tap_major_layout(monkeypatch):
     """A torch state loaded into optim.Adam lands in the flat moments in the arena's PHYSICAL order (tap-major convolution
     weights: each parameter's own strides), and comes back out in logical shape, contiguous, equal."""
     from gdn_amd import engine as E
+    from gdn_amd import ops
     from gdn_amd.optim import Adam
+    monkeypatch.setattr(ops, "zeros", lambda shape, device: torch.zeros(shape, device=device))      # (gdn_fill needs a GPU)
     net = _small_net()
     sd = _torch_state(net)
     ar = E.ParamArena(net, torch.device("cpu"))
     net._gdn_param_arena = ar
     opt = Adam(net.parameters(), 1e-3, (0.9, 0.999), eps=1e-8, weight_decay=5e-4)
-    st = {"m": torch.zeros(ar.numel), "v": torch.zeros(ar.numel), "step": 0, "pstep": None}
-    opt._flat[id(ar)] = st
+    st = opt._stores[id(ar)] = opt._new_store(ar.items, ar)      # (as the first step would)
+    assert opt.store_of(ar) is st and st.step == 0 and st.m.shape == (ar.numel,) and not st.m.any()
     gen = ar.generation
     opt.load_state_dict(sd)
-    assert ar.generation > gen and st["step"] == 2 and st["pstep"] is None and not opt._pending
+    assert ar.generation > gen and st.step == 2 and st.pstep is None and not opt._parked.moments
     for k, (p, o, n, tr) in enumerate(ar.items):
         want = sd["state"][k]["exp_avg"]
         if tr is not None:
             fwd, _ = E._perm(tr)
-            assert torch.equal(st["m"][o:o + n], want.permute(*fwd).reshape(-1)), "parameter %d is not tap-major" % k
-            assert not torch.equal(st["m"][o:o + n], want.reshape(-1))
+            assert torch.equal(st.m[o:o + n], want.permute(*fwd).reshape(-1)), "parameter %d is not tap-major" % k
+            assert not torch.equal(st.m[o:o + n], want.reshape(-1))
         else:
-            assert torch.equal(st["m"][o:o + n], want.reshape(-1))
+            assert torch.equal(st.m[o:o + n], want.reshape(-1))
     out = opt.state_dict()
     assert list(out["state"]) == list(range(len(ar.items))) and out["param_groups"][0]["params"] == list(range(len(ar.items)))
     for k, p in enumerate(net.parameters()):
