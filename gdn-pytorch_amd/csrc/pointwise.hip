@@ -730,6 +730,30 @@ __global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, fl
         if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); const float x = a[i]; a[i] = b[i]; b[i] = x; }
     }
 }
+// acc[i] = acc[i] + g[i]: one IEEE float32 add per element (nothing to contract into an FMA, subnormals kept), the sum of a
+// gradient-accumulation group (include/gdn_hip.h).  `g` is only read.
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n) {
+    const int64_t T = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
+    if (!VEC) {
+        for (int64_t i = tid; i < n; i += T) acc[i] = acc[i] + g[i];
+        return;
+    }
+    const StreamSplit s = stream_split(acc, n);
+    f32x4* __restrict__ av = reinterpret_cast<f32x4*>(acc + s.head);
+    const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + s.head);
+    for (int64_t i = tid; i < s.nvec; i += T) {
+        const f32x4 x = gv[i];
+        f32x4 a = av[i];
+        a.x = a.x + x.x; a.y = a.y + x.y; a.z = a.z + x.z; a.w = a.w + x.w;
+        av[i] = a;
+    }
+    if (blockIdx.x == 0) {
+        const int64_t l = threadIdx.x;
+        if (l < s.head) acc[l] = acc[l] + g[l];
+        if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); acc[i] = acc[i] + g[i]; }
+    }
+}
 // one lane per 16 bytes (VEC) or per float, capped like the Adam update's grid; the rest is grid-strided
 inline int stream_rw_blocks(int64_t n, bool vec) { return stream_blocks(vec ? cdiv64(n, 4) : n, 256, 4096); }
 
@@ -1088,6 +1112,16 @@ extern "C" int gdn_swap_f32(float* a, float* b, int64_t n, void* stream) {
     const bool vec = (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0;
     const auto kernel = vec ? swap_f32_kernel<true> : swap_f32_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), a, b, n);
+    return gdn_launch_status();
+}
+extern "C" int gdn_grad_accumulate(float* acc, const float* g, int64_t n, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!acc || !g || n <= 0 || ((uintptr_t)acc & 3) || ((uintptr_t)g & 3)) return GDN_ERR_BAD_ARG;
+    const uintptr_t ua = (uintptr_t)acc, ug = (uintptr_t)g, bytes = (uintptr_t)n * sizeof(float);
+    if (ua < ug + bytes && ug < ua + bytes) return GDN_ERR_BAD_ARG;       // overlapping ranges (acc == g included)
+    const bool vec = (((uintptr_t)acc ^ (uintptr_t)g) & 15) == 0;
+    const auto kernel = vec ? grad_accumulate_kernel<true> : grad_accumulate_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), acc, g, n);
     return gdn_launch_status();
 }
 

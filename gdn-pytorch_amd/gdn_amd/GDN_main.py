@@ -37,6 +37,9 @@ validation runs on the averaged weights and every ``X.pkl`` is followed by ``X_e
 BatchNorm running statistics are buffers: the averaged model uses the live ones.
 ``--graph`` replays the training step as a hipGraph after ``--graph_warmup`` eager steps: one graph per step
 on one GPU, two around the eager gradient all-reduce under data parallelism; the run is bit for bit the run without the flag.
+``--accum_steps K`` applies the mean gradient of K loader batches in one Adam update: an effective batch of
+K x batch_size x ranks with one gradient all-reduce per update; guard, average and step count are per update.  Not with
+``--graph`` yet.
 """
 import os
 import sys
@@ -120,6 +123,18 @@ def _check_graph(args):
                            "no collective may be captured (drop one of the two flags)" % D.env_rank()[2])
 
 
+def _check_accum(args):
+    """--accum_steps groups the batches of a training run; checked before anything touches the GPU."""
+    accum = int(getattr(args, "accum_steps", 1) or 1)
+    if accum <= 1:
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--accum_steps accumulates the gradients of a training run; --mode %s trains nothing" % args.mode)
+    if getattr(args, "graph", False):
+        raise RuntimeError("--graph with --accum_steps %d is not supported yet: a group would need captured graphs of its "
+                           "first, middle and last micro-step, which is a follow-up (drop one of the two flags)" % accum)
+
+
 def _resume(args, model, opt, train_loader, rank):
     """--resume: weights, optimizer, loader and progress from the state file; None without the flag."""
     path = getattr(args, "resume", None)
@@ -184,6 +199,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_resume(args)
     _check_ema(args)
     _check_graph(args)
+    _check_accum(args)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num

@@ -137,6 +137,7 @@ _SIGS = {
     "gdn_adam_step_dev_guarded": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P, _P]),
     "gdn_ema_update": (c_int32, [_P, _P, _i64, c_double, _P, _P, _P]),
     "gdn_swap_f32": (c_int32, [_P, _P, _i64, _P]),
+    "gdn_grad_accumulate": (c_int32, [_P, _P, _i64, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),
@@ -145,7 +146,8 @@ _STATUS_FUNCS = {n for n, (r, _) in _SIGS.items() if r is c_int32} - {"gdn_versi
 
 EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --
-# a stale build would take the arguments apart differently.
+# a stale build would take the arguments apart differently.  (gdn_grad_accumulate joined revision 223 without a new number:
+# _load() binds every name above, so a library built before it fails at load with the missing symbol.)
 ABI_VERSION = 223
 
 

@@ -94,6 +94,11 @@ class ParamArena:
         # since the last fresh backward) rather than this rank's local gradients; `carry_reduced` -- an already reduced
         # gradient carried across a further backward (accumulation without zero_grad), kept OUT of the arena until the new
         # local contribution has been reduced too (sync_gradients adds it back), so nothing is summed over the ranks twice
+        # gradient accumulation: `_grad_alt` -- a second gradient arena, made by the first accumulating
+        # backward that qualifies (bind_grads) and kept; `_pinned` -- a graph capture has recorded this arena's gradient
+        # address, so the two buffers never exchange roles again
+        self._grad_alt = None
+        self._pinned = False
         self.reduced = False
         self.reduced_scale = 1.0       # 1: the reduced arena holds sums over the ranks; 1/world: means (sync_gradients without an optimizer)
         self.carry_reduced = None      # always kept as a SUM over the ranks
@@ -152,14 +157,42 @@ class ParamArena:
                 return self._view(self.grad, o, p.shape, tr)
         raise KeyError("parameter not in arena")
 
+    def _exchange_ok(self):
+        """An accumulating backward may make its sum in the second gradient arena: a GPU arena outside a stream capture
+        whose gradient address no captured graph holds, every parameter's .grad already its arena slice, and no all-reduced
+        gradient involved (that one takes the carry_reduced detour of finish_grads)."""
+        if self.device.type != "cuda" or self._pinned or self.reduced or self.carry_reduced is not None:
+            return False
+        base = self.grad.data_ptr()
+        return all(p.grad is not None and p.grad.data_ptr() == base + 4 * o for p, o, _, _ in self.items)
+
     def bind_grads(self):
         """Point every .grad at its arena slice for one backward.  Returns the params whose existing, caller-owned grad
         must be accumulated afterwards.  A .grad that already IS the arena slice (a second backward without zero_grad:
-        gradient accumulation) is carried over: the kernels overwrite their slices, finish_grads() adds the carry back."""
+        gradient accumulation) is carried over: the kernels overwrite their slices, finish_grads() adds the carry back.
+
+        Where every parameter is carried (_exchange_ok) nothing is copied: the two gradient arenas exchange roles -- the
+        old sum becomes the carry, the tape writes into the other buffer, which every .grad now views -- and finish_grads()
+        adds the carry with one launch of gdn_grad_accumulate.  Every other case clones the arena as it always did."""
         self._gv = {}
         self._written = set()
         self._bound_before = set()
         self._carry = None
+        self._carry_kept = False
+        capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            self._pinned = True
+        elif self.items and self._exchange_ok():
+            if self._grad_alt is None:
+                self._grad_alt = ops.zeros((self.numel,), self.device)       # (the padding between slices stays zero)
+            self._carry, self.grad, self._grad_alt = self.grad, self._grad_alt, self.grad
+            self._carry_kept = True
+            for p, o, n, tr in self.items:
+                gv = self._view(self.grad, o, p.shape, tr)
+                p.grad = gv
+                self._gv[id(p)] = gv
+                self._bound_before.add(id(p))
+            return []
         accumulate = []
         for p, o, n, tr in self.items:
             gv = self._view(self.grad, o, p.shape, tr)
@@ -201,6 +234,8 @@ class ParamArena:
                     self._carry.mul_(1.0 / self.reduced_scale)
                 self.carry_reduced = self._carry if self.carry_reduced is None else self.carry_reduced.add_(self._carry)
                 self.reduced = False
+            elif self._carry_kept:
+                ops.grad_accumulate(self.grad, self._carry)       # written + carry, what grad.add_(carry) gives
             else:
                 self.grad.add_(self._carry)
             self._carry = None

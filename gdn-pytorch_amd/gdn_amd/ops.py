@@ -1301,3 +1301,11 @@ def ema_update(ema, p, decay, state, guard=None):
 def swap_(a, b):
     """Exchange the contents of two non-overlapping dense float32 buffers in place (gdn_swap_f32)."""
     lib.gdn_swap_f32(_p(a), _p(b), a.numel(), stream())
+
+
+def grad_accumulate(acc, g):
+    """acc += g for two non-overlapping dense float32 buffers of one size, one float32 add per element
+    (gdn_grad_accumulate): the running sum of a gradient-accumulation group.  No host sync, no allocation."""
+    if acc.numel() != g.numel():
+        raise GdnError("grad_accumulate: %d and %d elements" % (acc.numel(), g.numel()))
+    lib.gdn_grad_accumulate(_p(acc), _p(g), acc.numel(), stream())

@@ -12,6 +12,9 @@ kernel reads -- no torch kernel, no host read, capturable.
 Weight average (``ema_decay``): an exponential moving average of the weights beside the moments, updated by one more launch
 after each update under the same skip decision, and exchanged with the weights in place for validation and for the
 checkpoint that is deployed.
+
+Gradient accumulation (``micro_batches``): the gradient buffer holds the SUM of that many micro-batch gradients and the
+update takes their mean through its gradient scale -- one norm, one decision, one update per group.
 """
 import contextlib
 import struct
@@ -247,7 +250,16 @@ class Adam(torch.optim.Optimizer):
     t = 1, 2, ... of a parameter, w_t = 1 - min(d, (1 + t) / (10 + t)) (the warm-up of timm's ModelEmaV2 / torch's
     swa_utils), avg = p before the first update.  A step the guard skips leaves the average alone, a parameter without a
     gradient keeps its own.  Like the guard it implies capturable=True (t is the device's step count).  swap_averaged() /
-    averaged_weights() exchange weights and averages in place; buffers (BatchNorm running statistics) are not averaged."""
+    averaged_weights() exchange weights and averages in place; buffers (BatchNorm running statistics) are not averaged.
+
+    micro_batches (an attribute, default 1; a host-side integer set between steps): the gradients hold the sum of that many
+    micro-batch gradients (backwards without zero_grad), and the update kernels and the guard's norm see
+    grad_scale / micro_batches -- computed in double, rounded to float32 once -- where they see grad_scale today.  A factor of
+    its own because distributed.sync_gradients() overwrites grad_scale on every call.  The guard and the average stay per
+    UPDATE: one norm over the mean gradient, one decision, one count, one average update per group.  A NaN or an Inf in any
+    micro-batch's gradient stays in the sum, so with skip_nonfinite the WHOLE group's update is skipped.  It describes the
+    step being taken, not the run: state_dict() does not carry it.  Like every hyper-parameter of the capturable path it is
+    pushed to the device when it changes, which is refused inside a graph capture."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
                  max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
@@ -259,6 +271,7 @@ class Adam(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._stores = {}      # id(arena) or id(loose param) -> _Store, made by the first step that updates it
         self.grad_scale = 1.0  # set to 1/world_size by the data-parallel wrapper
+        self.micro_batches = 1  # gradient accumulation: the gradients hold the sum of this many micro-batches (see the class)
         # capturable: the step counter, beta^t and the hyper-parameters live in device memory (gdn_adam_step_dev), so
         # step() can be captured in a hipGraph and replayed; call refresh_hyper() after changing lr outside a capture
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -277,15 +290,22 @@ class Adam(torch.optim.Optimizer):
         """The state store of an arena or of a loose parameter; None before the first step that updates it."""
         return self._stores.get(id(owner))
 
+    def _scale(self):
+        """The gradient scale the kernels see, in double: they round it to float32 once."""
+        k = int(self.micro_batches)
+        if k < 1:
+            raise ValueError("micro_batches must be a positive integer, got %r" % (self.micro_batches,))
+        return float(self.grad_scale) if k == 1 else float(self.grad_scale) / k
+
     def refresh_hyper(self):
-        """Push (lr, betas, eps, weight_decay, grad_scale) to the device buffers of the capturable path if they changed."""
+        """Push (lr, betas, eps, weight_decay, grad_scale / micro_batches) to the device buffers of the capturable path if they changed."""
         for st in self._stores.values():
             if st.hyper is not None:
                 self._push_hyper(st, st.group)
 
     def _push_hyper(self, st, group):
         vals = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
-                float(group["weight_decay"]), float(self.grad_scale))
+                float(group["weight_decay"]), self._scale())
         if st.hyper_host != vals:
             _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
             st.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
@@ -325,7 +345,7 @@ class Adam(torch.optim.Optimizer):
             count, state = st.pstep[id(p)], st.pdev.get(id(p))
         if not self.capturable:
             b1, b2 = group["betas"]
-            ops.adam_step(w, grad, m, v, group["lr"], b1, b2, group["eps"], group["weight_decay"], count, self.grad_scale)
+            ops.adam_step(w, grad, m, v, group["lr"], b1, b2, group["eps"], group["weight_decay"], count, self._scale())
         elif self._work is not None:
             self._work.append((w, grad, m, v, st.hyper, state, ema))
         else:

@@ -1,7 +1,7 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
---graph_warmup).
+--graph_warmup, --accum_steps).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -120,6 +120,12 @@ def build_parser():
                         'The run is bit for bit the run without the flag; a batch of another shape runs eagerly')
     p.add_argument('--graph_warmup', type=_positive_int, default=3, metavar='N',
                    help='with --graph: eager steps (on their own batches) of a run or a resumed run before the capture')
+    p.add_argument('--accum_steps', type=_positive_int, default=1, metavar='K',
+                   help='training: accumulate the gradients of K loader batches (by position within the epoch; the group an '
+                        'epoch ends with may be shorter) and apply their mean in one Adam update: the effective batch is '
+                        'K x batch_size x ranks at the given learning rate, with one gradient all-reduce per update.  '
+                        'BatchNorm statistics and the BerHu threshold stay per batch, as they are per replica under data '
+                        'parallelism; not with --graph yet; 1 = off')
     return p
 
 

@@ -9,6 +9,9 @@ under no_grad exactly like the reference (latent loss is value-only, F3), data
 parallelism is one process per GPU with an RCCL all-reduce of the gradient arena,
 and the reference's image/feature-map dumps (and the crashes listed in SURVEY 3.5)
 are not reproduced.
+
+Added here without a reference counterpart: exact resume (--resume / --save_state), the --graph replay of the step and
+gradient accumulation (--accum_steps K: K loader batches per Adam update).
 """
 import os
 import time
@@ -86,7 +89,8 @@ def training_state(model, optimizer, loader, progress):
     """A plain dict (tensors on the host) of the model's state_dict under bare keys, the optimizer's state_dict
     (optim.Adam: real moments and the device step state), the loader's state of every rank, the torch RNG state and
     `progress`: 'epoch', 'i' (the batch of that epoch the last completed step used; -1: the epoch is about to start),
-    'lr', 'model_num', 'seen', 'step' (iterations over the whole run).  The guide network of RtoD is frozen and not part
+    'lr', 'model_num', 'seen', 'step' (iterations over the whole run), and 'accum_steps' where the run accumulates
+    gradients (--accum_steps > 1; a run without it writes the file it always wrote).  The guide network of RtoD is frozen and not part
     of it.  Collective under data parallelism: every rank calls it, the loader states are gathered to rank 0, which gets
     the dict; the other ranks get None (weights and moments are identical on all ranks)."""
     i = int(progress.get("i", -1))
@@ -106,6 +110,8 @@ def training_state(model, optimizer, loader, progress):
     for k in PROGRESS_KEYS:
         v = progress.get(k, defaults[k])
         state[k] = float(v) if k == "lr" else int(v)
+    if int(progress.get("accum_steps", 1)) > 1:
+        state["accum_steps"] = int(progress["accum_steps"])
     return state
 
 
@@ -129,7 +135,10 @@ def load_training_state(state, model, optimizer, loader):
     torch.set_rng_state(state["torch_rng"])
     if state.get("cuda_rng") is not None and torch.cuda.is_available():
         torch.cuda.set_rng_state(state["cuda_rng"])
-    return {k: state[k] for k in PROGRESS_KEYS}
+    progress = {k: state[k] for k in PROGRESS_KEYS}
+    if "accum_steps" in state:
+        progress["accum_steps"] = int(state["accum_steps"])
+    return progress
 
 
 def save_training_state(path, model, optimizer, loader, progress, writer=torch.save):
@@ -162,6 +171,7 @@ class _StateSaver:
     """--save_state / --save_state_every of one training loop: the rolling <save_dir>/train_state.pt."""
 
     def __init__(self, args, save_dir, model, optimizer, loader):
+        self.accum = _accum_steps(args)
         self.on_checkpoint = bool(getattr(args, "save_state", False))
         self.every = max(0, int(getattr(args, "save_state_every", 0) or 0))
         self.path = save_dir + '/' + STATE_FILE
@@ -177,8 +187,68 @@ class _StateSaver:
         return self.batches is not None and i >= self.batches - 1
 
     def save(self, epoch, i, lr, model_num, seen, step):
-        save_training_state(self.path, *self.objs, {"epoch": epoch, "i": i, "lr": lr, "model_num": model_num, "seen": seen,
-                                                    "step": step})
+        progress = {"epoch": epoch, "i": i, "lr": lr, "model_num": model_num, "seen": seen, "step": step}
+        if self.accum > 1:
+            progress["accum_steps"] = self.accum
+        save_training_state(self.path, *self.objs, progress)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --accum_steps: K loader batches per Adam update
+def _accum_steps(args):
+    return max(1, int(getattr(args, "accum_steps", 1) or 1))
+
+
+def _check_accum(args, progress):
+    """--accum_steps of this run against the one of the training state it resumes: the groups of an epoch are formed by
+    batch position, so another K would cut them elsewhere.  Raises before any step."""
+    accum = _accum_steps(args)
+    if getattr(args, "graph", False) and accum > 1:
+        raise U.GdnError("--graph with --accum_steps %d: a group would need graphs of its first, middle and last micro-step; "
+                         "capturing those is a follow-up, not part of this version" % accum)
+    if progress is not None and int(progress.get("accum_steps", 1)) != accum:
+        raise U.GdnError("the training state was written with --accum_steps %d, this run has --accum_steps %d: the resumed "
+                         "run would group its batches differently" % (int(progress.get("accum_steps", 1)), accum))
+    return accum
+
+
+class _Groups:
+    """The micro-steps of one --accum_steps K > 1 training loop.  The loader batches of an epoch form groups by position
+    (i // K): zero_grad before a group's first backward, the following backwards accumulate into the gradient arena
+    (engine.ParamArena.bind_grads: no copy, one gdn_grad_accumulate launch each), and after the group's last backward ONE
+    sync_gradients and ONE optimizer step with micro_batches = the number of micro-batches the group has -- K, or fewer for
+    the group an epoch ends with.  Groups never cross an epoch boundary.  Under data parallelism no micro-batch starts the
+    overlapped reducer (the model is marked like a graphed one): the local sums accumulate and the whole arena is reduced
+    once per update."""
+
+    def __init__(self, accum, model, optimizer, epoch_size, saver):
+        self.accum, self.model, self.optimizer, self.epoch_size, self.saver = accum, model, optimizer, epoch_size, saver
+        self.micro = 0                      # micro-batches of the open group so far; 0: between two groups
+        if D.world_size() > 1:
+            model._gdn_whole_arena_sync = True
+
+    def begin_epoch(self):
+        self.micro = 0
+
+    def update(self):
+        """The update of the open group (the loop calls it itself only where a loader ended without notice)."""
+        if self.micro == 0:
+            return
+        self.optimizer.micro_batches, self.micro = self.micro, 0
+        with tracing.span("gdn.allreduce"):
+            D.sync_gradients(self.model, self.optimizer)
+        with tracing.span("gdn.adam"):
+            self.optimizer.step()
+
+    def __call__(self, i, fwd_bwd, *inputs):
+        terms = fwd_bwd(*inputs, first=self.micro == 0)
+        self.micro += 1
+        if self.micro >= self.accum or i >= self.epoch_size - 1 or self.saver.last_batch(i):
+            self.update()
+        return terms
+
+    def close(self):
+        self.optimizer.micro_batches = 1
 
 
 def _start(progress, lr):
@@ -321,13 +391,16 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
     loss = output_loss = gradient_loss = None
     epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
     saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
+    accum = _check_accum(args, progress)
+    groups = _Groups(accum, model, optimizer, epoch_size, saver) if accum > 1 else None
 
-    def fwd_bwd(depths, sparse):
+    def fwd_bwd(depths, sparse, first=True):
         with tracing.span("gdn.forward"):
             outputs = model(depths, istrain=False)
         with tracing.span("gdn.losses"):
             terms = U.dtod_loss(outputs, depths, sparse)
-        optimizer.zero_grad()
+        if first:                       # (--accum_steps: the later backwards of a group accumulate)
+            optimizer.zero_grad()
         with tracing.span("gdn.backward"):
             U.backward(terms[0])        # == loss.backward(), seed gradient cached
         return terms
@@ -345,14 +418,20 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
     t0 = time.time()
     for epoch in range(epoch0, n_epochs):
         model.train()
-        due = False
+        due = held = False
+        if groups is not None:
+            groups.begin_epoch()
         for i, (gt_data, _, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
             depths = _to_dev(gt_data, dev)
             sparse = _to_dev(gt_data_2, dev) if kitti else None       # None <=> NYU: unmasked BerHu
-            loss, output_loss, gradient_loss = run_step(depths, sparse)
+            if groups is None:
+                loss, output_loss, gradient_loss = run_step(depths, sparse)
+            else:
+                loss, output_loss, gradient_loss = groups(i, fwd_bwd, depths, sparse)
             seen += depths.shape[0] * D.world_size()
             gstep += 1
-            due = saver.due(gstep)
+            due = saver.due(gstep) or (held and due)     # (held: a state that fell due inside a group waits for its end)
+            held = groups is not None and groups.micro > 0
             if i >= epoch_size - 1:
                 break
             if epoch > 5 and (i + 1) % 1900 == 0:
@@ -366,9 +445,11 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
                 _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
                 model_num += 1
                 due = due or saver.on_checkpoint
-            if due and not saver.last_batch(i):
+            if due and not held and not saver.last_batch(i):
                 saver.save(epoch, i, lr, model_num, seen, gstep)
                 due = False
+        if groups is not None:
+            groups.update()
         if loss is not None:
             if _is_main():
                 print('\n', 'epoch: ', epoch + 1, '  loss: ', loss.item())
@@ -381,6 +462,8 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
         if due:                  # after everything this epoch does: the resumed run starts the next one
             saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
     end_steps()
+    if groups is not None:
+        groups.close()
     return loss
 
 
@@ -450,9 +533,11 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     latent = torch.zeros((), device=dev)
     epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
     saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
+    accum = _check_accum(args, progress)
+    groups = _Groups(accum, model, optimizer, epoch_size, saver) if accum > 1 else None
     latent0 = latent
 
-    def fwd_bwd(inputs, depths, sparse):
+    def fwd_bwd(inputs, depths, sparse, first=True):
         latent = latent0
         with tracing.span("gdn.forward"):
             outputs = model(inputs, istrain=False)
@@ -466,7 +551,8 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
         else:                               # value-only latent loss (F3): summed by the loss kernel itself
             loss, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse, plus=latent)
         tracing.pop()
-        optimizer.zero_grad()
+        if first:                       # (--accum_steps: the later backwards of a group accumulate)
+            optimizer.zero_grad()
         with tracing.span("gdn.backward"):
             U.backward(loss)            # == loss.backward(), seed gradient cached
         return loss, output_loss, smooth, latent
@@ -484,14 +570,20 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     t0 = time.time()
     for epoch in range(epoch0, n_epochs):
         model.train()
-        due = False
+        due = held = False
+        if groups is not None:
+            groups.begin_epoch()
         for i, (gt_data, rgb_data, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
             inputs, depths = _to_dev(rgb_data, dev), _to_dev(gt_data, dev)
             sparse = _to_dev(gt_data_2, dev) if kitti else None
-            loss, output_loss, smooth, latent = run_step(inputs, depths, sparse)
+            if groups is None:
+                loss, output_loss, smooth, latent = run_step(inputs, depths, sparse)
+            else:
+                loss, output_loss, smooth, latent = groups(i, fwd_bwd, inputs, depths, sparse)
             seen += depths.shape[0] * D.world_size()
             gstep += 1
-            due = saver.due(gstep)
+            due = saver.due(gstep) or (held and due)     # (held: a state that fell due inside a group waits for its end)
+            held = groups is not None and groups.micro > 0
             if i >= epoch_size - 1:
                 break
             if epoch > 2 and (i + 1) % 2200 == 0:
@@ -505,9 +597,11 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
                 _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
                 model_num += 1
                 due = due or saver.on_checkpoint
-            if due and not saver.last_batch(i):
+            if due and not held and not saver.last_batch(i):
                 saver.save(epoch, i, lr, model_num, seen, gstep)
                 due = False
+        if groups is not None:
+            groups.update()
         _print_guard_epoch(optimizer)
         if logger is not None and val_loader is not None:
             _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
@@ -520,6 +614,8 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
         if saver.on_checkpoint:
             saver.save(n_epochs, -1, lr, model_num, seen, gstep)
     end_steps()
+    if groups is not None:
+        groups.close()
     return loss, output_loss, latent
 
 

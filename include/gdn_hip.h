@@ -743,6 +743,16 @@ int gdn_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, int6
 int gdn_ema_update(float* ema, const float* p, int64_t n, double decay, const void* state, const void* guard, void* stream);
 int gdn_swap_f32(float* a, float* b, int64_t n, void* stream);
 
+/* Gradient accumulation (no reference counterpart): acc[i] = acc[i] + g[i] over n floats, one IEEE float32
+ * add per element (no FMA, subnormals kept, no atomics), `g` only read: the sum of a group of micro-batch gradients, whose
+ * mean the optimizer takes through its gradient scale.  One launch, 16 bytes per lane where the two bases agree modulo 16
+ * (scalar head and tail around the aligned body), one float per lane where they do not.  A NULL pointer, n <= 0, a base that
+ * is not 4-byte aligned or overlapping ranges return GDN_ERR_BAD_ARG before any launch.
+ * Added WITHOUT a new ABI revision: no existing signature or record changed, and the Python loader binds every name it
+ * declares when it opens the library, so a revision-223 library built before this symbol existed still fails loudly at load
+ * (a missing symbol), never silently at the first accumulating backward. */
+int gdn_grad_accumulate(float* acc, const float* g, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
