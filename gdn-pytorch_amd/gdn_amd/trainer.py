@@ -15,6 +15,7 @@ gradient accumulation (--accum_steps K: K loader batches per Adam update, DESIGN
 """
 import os
 import time
+import typing
 
 import torch
 
@@ -70,7 +71,7 @@ def load_checkpoint(model, path, map_location="cpu"):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# resume: everything a run needs to go on bit for bit as if it had never stopped (DESIGN.md 2.15)
+# resume: everything a run needs to go on bit for bit as if it had never stopped (DESIGN.md 3.1)
 STATE_FILE = "train_state.pt"
 PROGRESS_KEYS = ("epoch", "i", "lr", "model_num", "seen", "step")
 
@@ -168,7 +169,11 @@ def read_training_state(path):
 
 
 class _StateSaver:
-    """--save_state / --save_state_every of one training loop: the rolling <save_dir>/train_state.pt."""
+    """--save_state / --save_state_every of one training loop: the rolling <save_dir>/train_state.pt, and when it is
+    written.  The loop reports what happened -- stepped(), checkpointed(), begin_epoch() -- and asks write_now(i) after a
+    batch and `pending` at the epoch's end.  A state falls due every `every` steps and on every checkpoint (--save_state).
+    One that falls due inside an open micro-batch group waits for the group's end; one that falls due on the loader's last
+    batch waits for the epoch's own work (checkpoint, validation) and is written as the start of the next epoch."""
 
     def __init__(self, args, save_dir, model, optimizer, loader):
         self.accum = _accum_steps(args)
@@ -177,20 +182,31 @@ class _StateSaver:
         self.path = save_dir + '/' + STATE_FILE
         self.objs = (model, optimizer, loader)
         self.batches = len(loader) if hasattr(loader, "__len__") else None
-
-    def due(self, step):
-        return self.every > 0 and step % self.every == 0
+        self.pending = self.held = False
 
     def last_batch(self, i):
-        """Batch i is the loader's last: its state is written once the epoch's own work (checkpoint, validation) is done,
-        as the start of the next epoch."""
         return self.batches is not None and i >= self.batches - 1
+
+    def begin_epoch(self):
+        self.pending = self.held = False
+
+    def stepped(self, step, held):
+        """Step number `step` of the run is done; held: it left a micro-batch group open."""
+        self.pending = (self.every > 0 and step % self.every == 0) or (self.held and self.pending)
+        self.held = held
+
+    def checkpointed(self):
+        self.pending = self.pending or self.on_checkpoint
+
+    def write_now(self, i):
+        return self.pending and not self.held and not self.last_batch(i)
 
     def save(self, epoch, i, lr, model_num, seen, step):
         progress = {"epoch": epoch, "i": i, "lr": lr, "model_num": model_num, "seen": seen, "step": step}
         if self.accum > 1:
             progress["accum_steps"] = self.accum
         save_training_state(self.path, *self.objs, progress)
+        self.pending = False
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -210,45 +226,6 @@ def _check_accum(args, progress):
         raise U.GdnError("the training state was written with --accum_steps %d, this run has --accum_steps %d: the resumed "
                          "run would group its batches differently" % (int(progress.get("accum_steps", 1)), accum))
     return accum
-
-
-class _Groups:
-    """The micro-steps of one --accum_steps K > 1 training loop.  The loader batches of an epoch form groups by position
-    (i // K): zero_grad before a group's first backward, the following backwards accumulate into the gradient arena
-    (engine.ParamArena.bind_grads: no copy, one gdn_grad_accumulate launch each), and after the group's last backward ONE
-    sync_gradients and ONE optimizer step with micro_batches = the number of micro-batches the group has -- K, or fewer for
-    the group an epoch ends with.  Groups never cross an epoch boundary.  Under data parallelism no micro-batch starts the
-    overlapped reducer (the model is marked like a graphed one): the local sums accumulate and the whole arena is reduced
-    once per update."""
-
-    def __init__(self, accum, model, optimizer, epoch_size, saver):
-        self.accum, self.model, self.optimizer, self.epoch_size, self.saver = accum, model, optimizer, epoch_size, saver
-        self.micro = 0                      # micro-batches of the open group so far; 0: between two groups
-        if D.world_size() > 1:
-            model._gdn_whole_arena_sync = True
-
-    def begin_epoch(self):
-        self.micro = 0
-
-    def update(self):
-        """The update of the open group (the loop calls it itself only where a loader ended without notice)."""
-        if self.micro == 0:
-            return
-        self.optimizer.micro_batches, self.micro = self.micro, 0
-        with tracing.span("gdn.allreduce"):
-            D.sync_gradients(self.model, self.optimizer)
-        with tracing.span("gdn.adam"):
-            self.optimizer.step()
-
-    def __call__(self, i, fwd_bwd, *inputs):
-        terms = fwd_bwd(*inputs, first=self.micro == 0)
-        self.micro += 1
-        if self.micro >= self.accum or i >= self.epoch_size - 1 or self.saver.last_batch(i):
-            self.update()
-        return terms
-
-    def close(self):
-        self.optimizer.micro_batches = 1
 
 
 def _start(progress, lr):
@@ -296,7 +273,37 @@ def _print_guard_epoch(optimizer):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# --graph: the step of a training loop replayed as a hipGraph
+# the step of a training loop in its three shapes: eager, replayed as a hipGraph (--graph), and as the
+# micro-steps of a group (--accum_steps K > 1)
+class _EagerStep:
+    """What the loop driver calls per loader batch: stepper(i, *inputs) -> the loss terms of batch i of the epoch.  This
+    one is the plain step -- fwd_bwd (forward, losses, zero_grad, backward), all-reduce, Adam -- and the no-op form of
+    what the driver tells every stepper: begin_epoch(), end_epoch(), close()."""
+    held = False                # a micro-batch group is open: the batch just taken has not reached the weights yet
+
+    def __init__(self, fwd_bwd, model, optimizer):
+        self.fwd_bwd, self.model, self.optimizer = fwd_bwd, model, optimizer
+
+    def update(self):
+        with tracing.span("gdn.allreduce"):
+            D.sync_gradients(self.model, self.optimizer)
+        with tracing.span("gdn.adam"):
+            self.optimizer.step()
+
+    def step(self, *inputs):
+        terms = self.fwd_bwd(*inputs)
+        self.update()
+        return terms
+
+    def __call__(self, i, *inputs):
+        return self.step(*inputs)
+
+    def begin_epoch(self):
+        pass
+
+    end_epoch = close = begin_epoch
+
+
 last_graph_report = None       # what the last --graph loop of this process printed: {'replayed', 'warmup', 'eager_steps'}
 
 
@@ -304,18 +311,20 @@ def _shapes(inputs):
     return [(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else None for t in inputs]
 
 
-class _GraphedLoopStep:
+class _GraphedStep(_EagerStep):
     """The step of one --graph training loop.  The first `graph_warmup` steps of the run (or of the resumed run) are the
     loop's ordinary eager steps on their own batches.  The next batch is captured around (prewarmed: the capture executes
     nothing) and replayed, and so is every later batch of its shapes -- provided an eager step has already run at these
     shapes and no larger batch has been seen: a last partial batch is never what gets captured once a full one has run.
     Every other batch (a partial one, or one that waits for such a capture) runs eagerly and is counted in `eager_steps`.
-    One graph at world 1, two around the eager all-reduce otherwise.  bind(loader, static_inputs) hands the static inputs
-    to a loader that can write into them."""
+    One graph at world 1, two around the eager all-reduce otherwise.  reads: the loader outputs the step's inputs are, in
+    the step's order -- a loader that can write into the static inputs (bind_outputs) is handed them in its own order."""
 
-    def __init__(self, args, model, optimizer, loader, step_fn, fwd_bwd_fn, bind):
-        self.model, self.optimizer, self.loader = model, optimizer, loader
-        self.step_fn, self.fwd_bwd_fn, self.bind = step_fn, fwd_bwd_fn, bind
+    def __init__(self, args, fwd_bwd, model, optimizer, loader, reads):
+        if not getattr(optimizer, "capturable", False):
+            raise U.GdnError("--graph needs optim.Adam(..., capturable=True): the step count must live on the device")
+        super().__init__(fwd_bwd, model, optimizer)
+        self.loader, self.reads = loader, reads
         self.warmup = max(1, int(getattr(args, "graph_warmup", 3) or 3))
         self.graphed, self.shapes, self.seen, self.largest = None, None, [], 0
         self.warm = self.replayed = self.eager_steps = 0
@@ -324,15 +333,16 @@ class _GraphedLoopStep:
     def _capture(self, inputs, shapes):
         from .graph import GraphedDataParallelStep, GraphedTrainStep
         if D.world_size() > 1:
-            self.graphed = GraphedDataParallelStep(self.fwd_bwd_fn, self.model, self.optimizer, inputs, prewarmed=True)
+            self.graphed = GraphedDataParallelStep(self.fwd_bwd, self.model, self.optimizer, inputs, prewarmed=True)
         else:
-            self.graphed = GraphedTrainStep(self.step_fn, inputs, self.optimizer, prewarmed=True)
+            self.graphed = GraphedTrainStep(self.step, inputs, self.optimizer, prewarmed=True)
         self.shapes = shapes
         if callable(getattr(self.loader, "bind_outputs", None)):
-            self.bind(self.loader, self.graphed.static_inputs)      # from the next batch on nothing is copied
+            static = self.graphed.static_inputs                     # from the next batch on nothing is copied
+            self.loader.bind_outputs(*[static[self.reads.index(j)] if j in self.reads else None for j in range(3)])
             self.bound = True
 
-    def __call__(self, *inputs):
+    def __call__(self, i, *inputs):
         shapes = _shapes(inputs)
         if self.graphed is None:
             n = inputs[0].shape[0]
@@ -346,10 +356,10 @@ class _GraphedLoopStep:
                 if shapes not in self.seen:
                     self.seen.append(shapes)
                 self.largest = max(self.largest, n)
-                return self.step_fn(*inputs)
+                return self.step(*inputs)
         if shapes != self.shapes:
             self.eager_steps += 1
-            return self.step_fn(*inputs)
+            return self.step(*inputs)
         with tracing.span("gdn.graph_step"):
             out = self.graphed(*inputs)
         self.replayed += 1
@@ -368,32 +378,147 @@ class _GraphedLoopStep:
                    self.warm + self.eager_steps, self.warm, self.eager_steps))
 
 
-def _loop_step(args, model, optimizer, loader, step_fn, fwd_bwd_fn, bind):
-    """(what the loop calls per batch, what it calls when it ends): the eager step itself without --graph."""
-    if not getattr(args, "graph", False):
-        return step_fn, lambda: None
-    if not getattr(optimizer, "capturable", False):
-        raise U.GdnError("--graph needs optim.Adam(..., capturable=True): the step count must live on the device")
-    run = _GraphedLoopStep(args, model, optimizer, loader, step_fn, fwd_bwd_fn, bind)
-    return run, run.close
+class _GroupedStep(_EagerStep):
+    """The micro-steps of one --accum_steps K > 1 training loop.  The loader batches of an epoch form groups by position
+    (i // K): zero_grad before a group's first backward, the following backwards accumulate into the gradient arena
+    (engine.ParamArena.bind_grads: no copy, one gdn_grad_accumulate launch each), and after the group's last backward ONE
+    sync_gradients and ONE optimizer step with micro_batches = the number of micro-batches the group has -- K, or fewer for
+    the group an epoch ends with.  Groups never cross an epoch boundary.  Under data parallelism no micro-batch starts the
+    overlapped reducer (the model is marked like a graphed one): the local sums accumulate and the whole arena is reduced
+    once per update."""
+
+    def __init__(self, fwd_bwd, model, optimizer, accum, epoch_size, saver):
+        super().__init__(fwd_bwd, model, optimizer)
+        self.accum, self.epoch_size, self.saver = accum, epoch_size, saver
+        self.micro = 0                      # micro-batches of the open group so far; 0: between two groups
+        if D.world_size() > 1:
+            model._gdn_whole_arena_sync = True
+
+    @property
+    def held(self):
+        return self.micro > 0
+
+    def begin_epoch(self):
+        self.micro = 0
+
+    def end_epoch(self):
+        """The update of the open group (the driver's own call matters only where a loader ended without notice)."""
+        if self.micro > 0:
+            self.optimizer.micro_batches, self.micro = self.micro, 0
+            self.update()
+
+    def __call__(self, i, *inputs):
+        terms = self.fwd_bwd(*inputs, first=self.micro == 0)
+        self.micro += 1
+        if self.micro >= self.accum or i >= self.epoch_size - 1 or self.saver.last_batch(i):
+            self.end_epoch()
+        return terms
+
+    def close(self):
+        self.optimizer.micro_batches = 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the loop driver: what train_AE_DtoD and train_AE_RtoD share (DESIGN.md 3.6)
+class _Cadence(typing.NamedTuple):
+    """What differs between the two training loops beside the step itself (the reference's trainer.py:498-506 / :784-792)."""
+    save_dir: str                   # './<dataset>' + this % (lr * 100000)
+    reads: tuple                    # the loader outputs the step reads, in its order; the last: sparse depth, None off KITTI
+    decay: tuple                    # (after this epoch, every so many batches, the divisor above 2e-5)
+    print_every: int
+    progress_line: str              # % (the step's loss terms..., images/s)
+    checkpoint_every: int
+    checkpoint_each_epoch: bool     # every epoch a step has run in prints its loss and ends with a checkpoint; without it a
+    #                                 run that wrote no checkpoint at all ends with one (and its state)
+
+
+_DTOD = _Cadence('_AE_DtoD_trained_model_lr000%d_color_uNet_gen2_nogradf', (0, 2), (5, 1900, 25), 50,
+                 "total_loss: %5f, output_loss: %5f, gradient_loss: %5f  (%.1f img/s)", 3000, True)
+_RTOD = _Cadence('_AE_RtoD_trained_model_lr000%d_color_uNet_gen2_nogradf', (1, 0, 2), (2, 2200, 60), 100,
+                 "total_loss: %5f, output_loss: %5f, smoothness_loss: %5f, latent_loss: %5f  (%.1f img/s)", 700, False)
+
+
+def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_epochs, lr, logger, progress):
+    """The epochs of one training run: fwd_bwd(*inputs, first=True) -> loss terms (the loss first) is the loop's own forward,
+    losses, zero_grad (where `first`) and backward; everything around it is here.  Returns the terms of the last step, None
+    if none ran.  progress: what load_training_state() returned -- the loop goes on after that step."""
+    if _is_main():
+        print("Training for %d epochs..." % n_epochs)
+    dev = _device_of(model)
+    save_dir = './' + args.dataset + cadence.save_dir % (lr * 100000)
+    epoch_size = getattr(args, "epoch_size", 0) or len(loader)
+    kitti = args.dataset == "KITTI"
+    dense, sparse_at = cadence.reads[:-1], cadence.reads[-1]
+    decay_after, decay_every, decay_div = cadence.decay
+    terms = None
+    epoch0, first, lr, model_num, seen, gstep = _start(progress, lr)
+    saver = _StateSaver(args, save_dir, model, optimizer, loader)
+    accum = _check_accum(args, progress)
+    if accum > 1:
+        stepper = _GroupedStep(fwd_bwd, model, optimizer, accum, epoch_size, saver)
+    elif getattr(args, "graph", False):
+        stepper = _GraphedStep(args, fwd_bwd, model, optimizer, loader, cadence.reads)
+    else:
+        stepper = _EagerStep(fwd_bwd, model, optimizer)
+
+    def checkpoint(counted=True):
+        nonlocal model_num
+        _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, terms[0].item()), optimizer)
+        if counted:
+            model_num += 1
+            saver.checkpointed()
+
+    t0 = time.time()
+    for epoch in range(epoch0, n_epochs):
+        model.train()
+        saver.begin_epoch()
+        stepper.begin_epoch()
+        for i, batch in enumerate(loader, first):
+            inputs = [_to_dev(batch[j], dev) for j in dense]
+            inputs.append(_to_dev(batch[sparse_at], dev) if kitti else None)       # None <=> NYU: unmasked BerHu
+            terms = stepper(i, *inputs)
+            seen += inputs[0].shape[0] * D.world_size()
+            gstep += 1
+            saver.stepped(gstep, stepper.held)
+            if i >= epoch_size - 1:
+                break
+            if epoch > decay_after and (i + 1) % decay_every == 0:
+                lr = _decay_lr(optimizer, lr, decay_div)
+            if (i + 1) % cadence.print_every == 0 and _is_main():
+                print("epoch: %d,  %d/%d" % (epoch + 1, i + 1, epoch_size))
+                print(cadence.progress_line % (tuple(t.item() for t in terms) + (seen / (time.time() - t0),)))
+                _print_guard_progress(optimizer)
+            if (i + 1) % cadence.checkpoint_every == 0:
+                checkpoint()
+            if saver.write_now(i):
+                saver.save(epoch, i, lr, model_num, seen, gstep)
+        first = 0                       # (only the epoch a resumed run starts in has batches already done)
+        stepper.end_epoch()
+        if not cadence.checkpoint_each_epoch:
+            _print_guard_epoch(optimizer)
+        elif terms is not None:
+            if _is_main():
+                print('\n', 'epoch: ', epoch + 1, '  loss: ', terms[0].item())
+            _print_guard_epoch(optimizer)
+            checkpoint()
+        if logger is not None and val_loader is not None:
+            _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
+        if saver.pending:               # after everything this epoch does: the resumed run starts the next one
+            saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
+    if not cadence.checkpoint_each_epoch and terms is not None and model_num == 0:
+        # no cadence save happened (the reference's per-epoch save is commented out, trainer.py:877-887): a run shorter than
+        # 700 steps per epoch -- a fine-tune, a trial -- leaves the weights it ends with instead of nothing
+        checkpoint(counted=False)
+        if saver.on_checkpoint:
+            saver.save(n_epochs, -1, lr, model_num, seen, gstep)
+    stepper.close()
+    return terms
 
 
 def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_loader, val_loader, batch_size,
                   n_epochs, lr, logger, train_writer, progress=None):
     """Depth->depth auto-encoder training; loss = BerHu + 3*imgrad_loss (trainer.py:411-468).
     progress: what load_training_state() returned -- the loop goes on after that step."""
-    if _is_main():
-        print("Training for %d epochs..." % n_epochs)
-    dev = _device_of(model)
-    save_dir = './' + args.dataset + '_AE_DtoD_trained_model_lr000%d_color_uNet_gen2_nogradf' % (lr * 100000)
-    epoch_size = getattr(args, "epoch_size", 0) or len(dataset_loader)
-    kitti = args.dataset == "KITTI"
-    loss = output_loss = gradient_loss = None
-    epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
-    saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
-    accum = _check_accum(args, progress)
-    groups = _Groups(accum, model, optimizer, epoch_size, saver) if accum > 1 else None
-
     def fwd_bwd(depths, sparse, first=True):
         with tracing.span("gdn.forward"):
             outputs = model(depths, istrain=False)
@@ -405,66 +530,8 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
             U.backward(terms[0])        # == loss.backward(), seed gradient cached
         return terms
 
-    def step(depths, sparse):
-        terms = fwd_bwd(depths, sparse)
-        with tracing.span("gdn.allreduce"):
-            D.sync_gradients(model, optimizer)
-        with tracing.span("gdn.adam"):
-            optimizer.step()
-        return terms
-
-    run_step, end_steps = _loop_step(args, model, optimizer, dataset_loader, step, fwd_bwd,
-                                     lambda loader, static: loader.bind_outputs(static[0], None, static[1]))
-    t0 = time.time()
-    for epoch in range(epoch0, n_epochs):
-        model.train()
-        due = held = False
-        if groups is not None:
-            groups.begin_epoch()
-        for i, (gt_data, _, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
-            depths = _to_dev(gt_data, dev)
-            sparse = _to_dev(gt_data_2, dev) if kitti else None       # None <=> NYU: unmasked BerHu
-            if groups is None:
-                loss, output_loss, gradient_loss = run_step(depths, sparse)
-            else:
-                loss, output_loss, gradient_loss = groups(i, fwd_bwd, depths, sparse)
-            seen += depths.shape[0] * D.world_size()
-            gstep += 1
-            due = saver.due(gstep) or (held and due)     # (held: a state that fell due inside a group waits for its end)
-            held = groups is not None and groups.micro > 0
-            if i >= epoch_size - 1:
-                break
-            if epoch > 5 and (i + 1) % 1900 == 0:
-                lr = _decay_lr(optimizer, lr, 25)
-            if (i + 1) % 50 == 0 and _is_main():
-                print("epoch: %d,  %d/%d" % (epoch + 1, i + 1, epoch_size))
-                print("total_loss: %5f, output_loss: %5f, gradient_loss: %5f  (%.1f img/s)" %
-                      (loss.item(), output_loss.item(), gradient_loss.item(), seen / (time.time() - t0)))
-                _print_guard_progress(optimizer)
-            if (i + 1) % 3000 == 0:
-                _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
-                model_num += 1
-                due = due or saver.on_checkpoint
-            if due and not held and not saver.last_batch(i):
-                saver.save(epoch, i, lr, model_num, seen, gstep)
-                due = False
-        if groups is not None:
-            groups.update()
-        if loss is not None:
-            if _is_main():
-                print('\n', 'epoch: ', epoch + 1, '  loss: ', loss.item())
-            _print_guard_epoch(optimizer)
-            _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
-            model_num += 1
-            due = due or saver.on_checkpoint
-        if logger is not None and val_loader is not None:
-            _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
-        if due:                  # after everything this epoch does: the resumed run starts the next one
-            saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
-    end_steps()
-    if groups is not None:
-        groups.close()
-    return loss
+    terms = _run_loop(args, _DTOD, fwd_bwd, model, optimizer, dataset_loader, val_loader, n_epochs, lr, logger, progress)
+    return None if terms is None else terms[0]
 
 
 def _cat_batch(a, b):
@@ -522,20 +589,8 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     loss = BerHu + latent (value only: G's features of the estimate are taken
     under no_grad, exactly as shipped, F3) + smoothness.  mode 'RtoD_single'
     drops the latent term."""
-    if _is_main():
-        print("Training for %d epochs..." % n_epochs)
-    dev = _device_of(model)
-    save_dir = './' + args.dataset + '_AE_RtoD_trained_model_lr000%d_color_uNet_gen2_nogradf' % (lr * 100000)
-    epoch_size = getattr(args, "epoch_size", 0) or len(dataset_loader)
-    kitti = args.dataset == "KITTI"
     single = args.mode == 'RtoD_single' or DtoD_model is None
-    loss = output_loss = None
-    latent = torch.zeros((), device=dev)
-    epoch0, skip, lr, model_num, seen, gstep = _start(progress, lr)
-    saver = _StateSaver(args, save_dir, model, optimizer, dataset_loader)
-    accum = _check_accum(args, progress)
-    groups = _Groups(accum, model, optimizer, epoch_size, saver) if accum > 1 else None
-    latent0 = latent
+    latent0 = torch.zeros((), device=_device_of(model))
 
     def fwd_bwd(inputs, depths, sparse, first=True):
         latent = latent0
@@ -557,66 +612,8 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
             U.backward(loss)            # == loss.backward(), seed gradient cached
         return loss, output_loss, smooth, latent
 
-    def step(inputs, depths, sparse):
-        terms = fwd_bwd(inputs, depths, sparse)
-        with tracing.span("gdn.allreduce"):
-            D.sync_gradients(model, optimizer)
-        with tracing.span("gdn.adam"):
-            optimizer.step()
-        return terms
-
-    run_step, end_steps = _loop_step(args, model, optimizer, dataset_loader, step, fwd_bwd,
-                                     lambda loader, static: loader.bind_outputs(static[1], static[0], static[2]))
-    t0 = time.time()
-    for epoch in range(epoch0, n_epochs):
-        model.train()
-        due = held = False
-        if groups is not None:
-            groups.begin_epoch()
-        for i, (gt_data, rgb_data, gt_data_2) in enumerate(dataset_loader, skip if epoch == epoch0 else 0):
-            inputs, depths = _to_dev(rgb_data, dev), _to_dev(gt_data, dev)
-            sparse = _to_dev(gt_data_2, dev) if kitti else None
-            if groups is None:
-                loss, output_loss, smooth, latent = run_step(inputs, depths, sparse)
-            else:
-                loss, output_loss, smooth, latent = groups(i, fwd_bwd, inputs, depths, sparse)
-            seen += depths.shape[0] * D.world_size()
-            gstep += 1
-            due = saver.due(gstep) or (held and due)     # (held: a state that fell due inside a group waits for its end)
-            held = groups is not None and groups.micro > 0
-            if i >= epoch_size - 1:
-                break
-            if epoch > 2 and (i + 1) % 2200 == 0:
-                lr = _decay_lr(optimizer, lr, 60)
-            if (i + 1) % 100 == 0 and _is_main():
-                print("epoch: %d,  %d/%d" % (epoch + 1, i + 1, epoch_size))
-                print("total_loss: %5f, output_loss: %5f, smoothness_loss: %5f, latent_loss: %5f  (%.1f img/s)" %
-                      (loss.item(), output_loss.item(), smooth.item(), latent.item(), seen / (time.time() - t0)))
-                _print_guard_progress(optimizer)
-            if (i + 1) % 700 == 0:
-                _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
-                model_num += 1
-                due = due or saver.on_checkpoint
-            if due and not held and not saver.last_batch(i):
-                saver.save(epoch, i, lr, model_num, seen, gstep)
-                due = False
-        if groups is not None:
-            groups.update()
-        _print_guard_epoch(optimizer)
-        if logger is not None and val_loader is not None:
-            _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
-        if due:
-            saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
-    if loss is not None and model_num == 0:
-        # no cadence save happened (the reference's per-epoch save is commented out, trainer.py:877-887): a run shorter than
-        # 700 steps per epoch -- a fine-tune, a trial -- leaves the weights it ends with instead of nothing
-        _save_checkpoint(model, save_dir + '/epoch_%d_AE_depth_loss_%.4f.pkl' % (model_num + 1, loss.item()), optimizer)
-        if saver.on_checkpoint:
-            saver.save(n_epochs, -1, lr, model_num, seen, gstep)
-    end_steps()
-    if groups is not None:
-        groups.close()
-    return loss, output_loss, latent
+    terms = _run_loop(args, _RTOD, fwd_bwd, model, optimizer, dataset_loader, val_loader, n_epochs, lr, logger, progress)
+    return (None, None, latent0) if terms is None else (terms[0], terms[1], terms[3])
 
 
 def _evaluate(val_loader, model, mode, metric, names, on_batch=None):

@@ -242,11 +242,8 @@ def _one_sync_worker(rank, world, port, q):
         model._gdn_reducer = D.GradReducer(arena, bucket_elems=200)
         assert backward(0) is True
         D.sync_gradients(model, opt)
-        # the loop's own bookkeeping (trainer._Groups): the model is marked, no micro-batch starts the reducer
+        # the loop's own bookkeeping (trainer._GroupedStep): the model is marked, no micro-batch starts the reducer
         saver = argparse.Namespace(last_batch=lambda i: False)
-        groups = T._Groups(K, model, opt, 100, saver)
-        assert model._gdn_whole_arena_sync is True
-        D.stats_begin()
         overlapped = []
 
         def fwd_bwd(step, first=True):
@@ -254,23 +251,28 @@ def _one_sync_worker(rank, world, port, q):
                 opt.zero_grad()
             overlapped.append(backward(step))
             return step
+        groups = T._GroupedStep(fwd_bwd, model, opt, K, 100, saver)
+        assert model._gdn_whole_arena_sync is True and not groups.held
+        D.stats_begin()
         for i in range(K):
-            assert D.STATS.syncs == 0 and opt.steps == 0
-            groups(i, fwd_bwd, 10 + i)
+            assert D.STATS.syncs == 0 and opt.steps == 0 and groups.held == (i > 0)
+            assert groups(i, 10 + i) == 10 + i
         assert overlapped == [False] * K
-        assert D.STATS.syncs == 1 and opt.steps == 1 and groups.micro == 0
+        assert D.STATS.syncs == 1 and opt.steps == 1 and groups.micro == 0 and not groups.held
         assert opt.grad_scale == 1.0 / world and opt.micro_batches == K
         assert arena.carry_reduced is None and arena.reduced
         want = [sum(g(10 + s, r)[i] for s in range(K) for r in range(world)) / (world * K) for i in range(len(params))]
         for p, w in zip(params, want):
             torch.testing.assert_close(p.grad * (opt.grad_scale / opt.micro_batches), w, rtol=1e-5, atol=1e-6)
         # a shorter last group: two micro-batches, closed by the epoch's end
-        groups = T._Groups(K, model, opt, 5, saver)
+        groups = T._GroupedStep(fwd_bwd, model, opt, K, 5, saver)
         groups.begin_epoch()
-        groups(3, fwd_bwd, 20)
-        assert groups.micro == 1 and D.STATS.syncs == 1
-        groups(4, fwd_bwd, 21)
+        groups(3, 20)
+        assert groups.micro == 1 and groups.held and D.STATS.syncs == 1
+        groups(4, 21)
         assert groups.micro == 0 and D.STATS.syncs == 2 and opt.steps == 2 and opt.micro_batches == 2
+        groups.end_epoch()                                 # nothing is open: the epoch's end adds no update
+        assert D.STATS.syncs == 2 and opt.steps == 2
         want = [sum(g(20 + s, r)[i] for s in range(2) for r in range(world)) / (world * 2) for i in range(len(params))]
         for p, w in zip(params, want):
             torch.testing.assert_close(p.grad * (opt.grad_scale / opt.micro_batches), w, rtol=1e-5, atol=1e-6)
