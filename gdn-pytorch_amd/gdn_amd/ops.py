@@ -613,8 +613,12 @@ class Conv:
         return res if len(res) > 1 else y
 
     def wino2_bwd(self, dy, w_tap, in_hw, state=None, dw_tap=None, need_dx=True, addsrc=None, bnb=None):
-        """Data gradient (returned; + addsrc) and / or weight gradient (into dw_tap, needs the forward's `state`)."""
+        """Data gradient (returned; + addsrc) and / or weight gradient (into dw_tap, needs the forward's `state`).
+        bnb: as wino_bwd's, for the callers that treat the paths alike -- but this path emits no BatchNorm-backward partials
+        (gdn_wino2conv_bwd has no such output), so anything but None is an error, not a partial buffer left unwritten."""
         _chk(dy, "dy")
+        if bnb is not None:
+            raise GdnError("wino2_bwd: this path emits no BatchNorm-backward partials (bnb)")
         B = dy.shape[0]
         H, W = in_hw
         _, ref, Ho, Wo = self.geom(B, H, W)

@@ -2,6 +2,8 @@
 import pytest
 import torch
 
+from int_conv_ref import TWO24, X3_PLANE_CASES, x3_bound, x3_plane_case
+
 pytestmark = pytest.mark.gpu
 
 
@@ -72,3 +74,21 @@ def test_gemm_x3_tn_exact_on_integers(gpu):
     ref = torch.bmm(A.double().transpose(1, 2), B.double())
     P = ops.gemm_x3_tn(A.to(gpu), B.to(gpu), 2).cpu().double().sum(0)
     assert torch.equal(P, ref)
+
+
+@pytest.mark.parametrize("name", sorted(X3_PLANE_CASES))
+def test_gemm_x3_planes_exact(gpu, name):
+    """Operands that need planes 2 and 3 of each side and the product a2 b2 (tests/int_conv_ref.py: x3_plane_case; the CPU test
+    test_x3_plane_cases_need_their_planes shows each case fails when a plane it targets is lost): both kernels must give the
+    integer result bit for bit.  The small-integer tests above fill the first plane of one operand only."""
+    from gdn_amd import ops
+    A, B = x3_plane_case(name)
+    assert x3_bound(A, B, 1.0) < TWO24
+    ref = torch.bmm(A, B.transpose(1, 2))
+    assert torch.equal(ref.float().double(), ref)
+    C = ops.gemm_x3_nt(A.float().to(gpu), ops.gemm_x3_pack(B.float().to(gpu)), B.shape[1]).cpu().double()
+    assert torch.equal(C, ref), "gemm_x3_nt %s: %d elements differ" % (name, int((C != ref).sum()))
+    At, Bt = A.transpose(1, 2).contiguous().float().to(gpu), B.transpose(1, 2).contiguous().float().to(gpu)      # [bins, T, NI], [bins, T, NJ]
+    for ns in (1, 2):
+        P = ops.gemm_x3_tn(At, Bt, ns).cpu().double().sum(0)
+        assert torch.equal(P, ref), "gemm_x3_tn %s / %d: %d elements differ" % (name, ns, int((P != ref).sum()))

@@ -8,9 +8,25 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+
+def _mm(a, b):
+    """Batched matrix product on contiguous copies (BLAS)."""
+    return torch.matmul(torch.from_numpy(np.ascontiguousarray(a)), torch.from_numpy(np.ascontiguousarray(b))).numpy()
+
+
+def _es(spec, *ops):
+    """einsum through torch (pairwise BLAS contractions): the models also run at the GPU tests' channel counts."""
+    return torch.einsum(spec, *[torch.from_numpy(np.ascontiguousarray(o)) for o in ops]).numpy()
+
+
 BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, -1, 0, 1]], np.float64)
 G = np.array([[1, 0], [.5, .5], [.5, -.5], [0, 1]], np.float64)
 AT = np.array([[1, 1, 1, 0], [0, 1, -1, 0], [0, 1, 1, 1]], np.float64)
+
+
+def _mats(mats, dtype):
+    """(B^T, G, A^T) in dtype: the scheme's own unless given (tests/int_conv_ref.py runs the model on their absolute values)."""
+    return [m.astype(dtype) for m in (mats or (BT, G, AT))]
 
 
 def test_f32_matrices_1d():
@@ -29,8 +45,9 @@ def _pad1(x, reflect, dtype):
     return xp
 
 
-def form_a_input(x, reflect, dtype=np.float64):
+def form_a_input(x, reflect, dtype=np.float64, mats=None):
     """V[16][tile][(a*2+b)*C + c] for the LARGE image x [C,H,W]; tiles of 3x3 outputs = 8x8 footprints at (6t - 1)."""
+    bt = _mats(mats, dtype)[0]
     C, H, W = x.shape
     Hy, Wy = H // 2, W // 2
     ty, tx = -(-Hy // 3), -(-Wy // 3)
@@ -44,80 +61,101 @@ def form_a_input(x, reflect, dtype=np.float64):
         for a in range(2):
             for b in range(2):
                 X = P[:, a::2, b::2]                          # X_ab[p][q] = P[2p + a][2q + b]
-                V[:, :, t, (a * 2 + b) * C:(a * 2 + b + 1) * C] = np.einsum("ij,cjk,lk->ilc", BT.astype(dtype), X, BT.astype(dtype))
+                V[:, :, t, (a * 2 + b) * C:(a * 2 + b + 1) * C] = _es("ij,cjk,lk->ilc", bt, X, bt)
     return V, ty, tx
 
 
-def form_a_weights(w, dtype=np.float64):
+def form_a_weights(w, dtype=np.float64, mats=None):
     """U[16][n][(a*2+b)*C + c] from w[n][c][4][4] (conv form)."""
+    gm = _mats(mats, dtype)[1]
     N, C = w.shape[:2]
     U = np.zeros((4, 4, N, 4 * C), dtype)
     for a in range(2):
         for b in range(2):
             g = w[:, :, a::2, b::2].astype(dtype)            # g_ab[u][v] = w[2u + a][2v + b]
-            U[:, :, :, (a * 2 + b) * C:(a * 2 + b + 1) * C] = np.einsum("ij,ncjk,lk->ilnc", G.astype(dtype), g, G.astype(dtype))
+            U[:, :, :, (a * 2 + b) * C:(a * 2 + b + 1) * C] = _es("ij,ncjk,lk->ilnc", gm, g, gm)
     return U
 
 
-def form_a_output(M, ty, tx, Hy, Wy):
+def form_a_output(M, ty, tx, Hy, Wy, keep=None, mats=None):
     """M[16][tile][n] -> y[n][Hy][Wy]."""
-    y9 = np.einsum("ij,jktn,lk->tnil", AT.astype(M.dtype), M, AT.astype(M.dtype))       # [T,N,3,3]
+    at = _mats(mats, M.dtype)[2]
+    y9 = _es("ij,jktn,lk->tnil", at, M, at)                                 # [T,N,3,3]
     y = y9.reshape(ty, tx, -1, 3, 3).transpose(2, 0, 3, 1, 4).reshape(-1, 3 * ty, 3 * tx)
+    if keep is not None:
+        keep.update(M=M, Y=y)
     return y[:, :Hy, :Wy]
 
 
-def strided_conv(x, w, reflect, dtype=np.float64):
-    """y = conv2d(pad1(x), w, stride 2) through form A.  Returns y and V."""
-    V, ty, tx = form_a_input(x, reflect, dtype)
-    U = form_a_weights(w, dtype)
-    M = np.einsum("iltk,ilnk->iltn", V, U).astype(dtype)
-    return form_a_output(M, ty, tx, x.shape[1] // 2, x.shape[2] // 2), V
+def strided_conv(x, w, reflect, dtype=np.float64, keep=None, mats=None):
+    """y = conv2d(pad1(x), w, stride 2) through form A.  Returns y and V.  keep: a dict that receives every intermediate
+    (tests/int_conv_ref.py: the exactness bound runs the scheme with mats = the absolute values of BT / G / AT)."""
+    V, ty, tx = form_a_input(x, reflect, dtype, mats)
+    U = form_a_weights(w, dtype, mats)
+    M = _mm(V, U.swapaxes(2, 3)).astype(dtype)
+    if keep is not None:
+        keep.update(V=V, U=U)
+    return form_a_output(M, ty, tx, x.shape[1] // 2, x.shape[2] // 2, keep, mats), V
 
 
-def transposed_conv(d, wt, Hout, Wout, off, dtype=np.float64):
+def transposed_conv(d, wt, Hout, Wout, off, dtype=np.float64, keep=None, mats=None):
     """z[r][s] = sum_{i,j} d[i][j] * wt[:, :, r + 1 - 2i, s + 1 - 2j] through form B; wt[cd][n][4][4].
-    off = 0: rows r in [0, Hout);  off = 1: the padded domain, out row = r + 1 for r in [-1, Hout - 2]."""
+    off = 0: rows r in [0, Hout);  off = 1: the padded domain, out row = r + 1 for r in [-1, Hout - 2].
+    (All tiles at once: one transform of the 4x4 patches, one product per output phase.)"""
+    bt, gm, at = _mats(mats, dtype)
     Cd, Hy, Wy = d.shape
     N = wt.shape[1]
     ty, tx = -(-(Hout + 1 - off) // 6), -(-(Wout + 1 - off) // 6)   # = cdiv(Hx + ext, 6): Hx = Hout - 2*off, ext = 1 + off
     dp = np.zeros((Cd, 3 * ty + 3, 3 * tx + 3), dtype)               # dp[s] = d[s - 1]
     dp[:, 1:Hy + 1, 1:Wy + 1] = d
     out = np.zeros((N, Hout, Wout), dtype)
-    for t in range(ty * tx):
-        a0, b0 = 3 * (t // tx), 3 * (t % tx)
-        Vd = np.einsum("ij,cjk,lk->ilc", BT.astype(dtype), dp[:, a0:a0 + 4, b0:b0 + 4], BT.astype(dtype))
-        for a in range(2):
-            for b in range(2):
-                g = np.stack([[wt[:, :, 3 - a - 2 * u, 3 - b - 2 * v] for v in range(2)] for u in range(2)])   # [2,2,cd,n]
-                Ug = np.einsum("ij,jkcn,lk->ilcn", G.astype(dtype), g.astype(dtype), G.astype(dtype))
-                m = np.einsum("ilc,ilcn->iln", Vd, Ug)
-                o = np.einsum("ij,jkn,lk->nil", AT.astype(dtype), m, AT.astype(dtype))                       # [n,3,3]
-                for i in range(3):
-                    for j in range(3):
-                        oy, ox = 6 * (t // tx) + 2 * i - a + off, 6 * (t % tx) + 2 * j - b + off
-                        if 0 <= oy < Hout and 0 <= ox < Wout:
-                            out[:, oy, ox] = o[:, i, j]
+    pat = np.stack([dp[:, 3 * a:3 * a + 4, 3 * b:3 * b + 4] for a in range(ty) for b in range(tx)])          # [T,Cd,4,4]
+    Vd = _es("ij,tcjk,lk->iltc", bt, pat, bt)
+    big, Us = 0.0, []
+    for a in range(2):
+        for b in range(2):
+            g = np.stack([[wt[:, :, 3 - a - 2 * u, 3 - b - 2 * v] for v in range(2)] for u in range(2)])   # [2,2,cd,n]
+            Ug = _es("ij,jkcn,lk->ilcn", gm, g.astype(dtype), gm)
+            m = _mm(Vd, Ug).astype(dtype)
+            o = _es("ij,jktn,lk->tnil", at, m, at).reshape(ty, tx, N, 3, 3)
+            big = max(big, float(np.abs(m).max()), float(np.abs(o).max()))
+            Us.append(Ug)
+            for i in range(3):
+                for j in range(3):
+                    oy, ox = 6 * np.arange(ty) + 2 * i - a + off, 6 * np.arange(tx) + 2 * j - b + off
+                    vy, vx = (oy >= 0) & (oy < Hout), (ox >= 0) & (ox < Wout)
+                    out[np.ix_(np.arange(N), oy[vy], ox[vx])] = o[vy][:, vx][..., i, j].transpose(2, 0, 1)
+    if keep is not None:
+        keep.update(V=Vd, Us=Us, big=big)
     return out
 
 
-def lift(sm, ty, tx):
+def lift(sm, ty, tx, dtype=np.float64, mats=None):
     """Dv[16][tile][n] = A s A^T of the 3x3 tiles of the small image."""
     N, Hy, Wy = sm.shape
-    gp = np.zeros((N, 3 * ty, 3 * tx))
+    gp = np.zeros((N, 3 * ty, 3 * tx), dtype)
     gp[:, :Hy, :Wy] = sm
     g9 = gp.reshape(N, ty, 3, tx, 3).transpose(1, 3, 0, 2, 4).reshape(ty * tx, N, 3, 3)
-    return np.einsum("ji,tnjk,kl->iltn", AT, g9, AT)
+    at = _mats(mats, dtype)[2]
+    return _es("ji,tnjk,kl->iltn", at, g9, at)
 
 
-def wgrad(V, sm, C):
-    """dw[n][c][4][4] from V (form A of the large image) and the small image sm [N,Hy,Wy]."""
+def wgrad(V, sm, C, dtype=np.float64, keep=None, P0=None, mats=None):
+    """dw[n][c][4][4] from V (form A of the large image) and the small image sm [N,Hy,Wy].
+    P0: the per-bin sums of the images before this one (a batch reduces over all its tiles before the tap fold)."""
     Hy, Wy = sm.shape[1:]
     ty, tx = -(-Hy // 3), -(-Wy // 3)
-    P = np.einsum("iltn,iltk->ilnk", lift(sm, ty, tx), V)
-    dw = np.zeros((sm.shape[0], C, 4, 4))
+    Dv = lift(sm, ty, tx, dtype, mats)
+    gm = _mats(mats, dtype)[1]
+    P = _mm(Dv.swapaxes(2, 3), V.astype(dtype)).astype(dtype)
+    if P0 is not None:
+        P = P + P0
+    if keep is not None:
+        keep.update(Dv=Dv, P=P)
+    dw = np.zeros((sm.shape[0], C, 4, 4), dtype)
     for a in range(2):
         for b in range(2):
-            dw[:, :, a::2, b::2] = np.einsum("ji,jknc,kl->ncil", G, P[:, :, :, (a * 2 + b) * C:(a * 2 + b + 1) * C], G)
+            dw[:, :, a::2, b::2] = _es("ji,jknc,kl->ncil", gm, P[:, :, :, (a * 2 + b) * C:(a * 2 + b + 1) * C], gm)
     return dw
 
 

@@ -8,40 +8,67 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+
+def _mm(a, b):
+    """Batched matrix product on contiguous copies (BLAS)."""
+    return torch.matmul(torch.from_numpy(np.ascontiguousarray(a)), torch.from_numpy(np.ascontiguousarray(b))).numpy()
+
+
+def _es(spec, *ops):
+    """einsum through torch (pairwise BLAS contractions): the models also run at the GPU tests' channel counts."""
+    return torch.einsum(spec, *[torch.from_numpy(np.ascontiguousarray(o)) for o in ops]).numpy()
+
+
 BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64)
 G = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64)
 AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64)
 
 
-def _tiles(x, dtype):
+def _tiles(x, dtype, reflect=False):
+    """4x4 patches at stride 2 from (-1, -1).  reflect: the border ring (row / column -1 and H / W) mirrors rows 1 and H - 2 as
+    wino_input_kernel reads it; anything further out (the second row of a ragged last tile) is zero either way."""
     C, H, W = x.shape
     ty, tx = -(-H // 2), -(-W // 2)
     xp = np.zeros((C, 2 * ty + 2, 2 * tx + 2), dtype)
-    xp[:, 1:H + 1, 1:W + 1] = x
+    if reflect:
+        xp[:, :H + 2, :W + 2] = np.pad(x, ((0, 0), (1, 1), (1, 1)), mode="reflect")
+    else:
+        xp[:, 1:H + 1, 1:W + 1] = x
     d = np.stack([xp[:, 2 * a:2 * a + 4, 2 * b:2 * b + 4] for a in range(ty) for b in range(tx)])     # [T,C,4,4]
     return d, ty, tx
 
 
-def wino_forward(x, w, dtype=np.float64):
+def wino_forward(x, w, dtype=np.float64, reflect=False, mats=None, keep=None):
+    """mats: (B^T, G, A^T) in place of the scheme's own (tests/int_conv_ref.py runs it on their absolute values);
+    keep: a dict that receives every intermediate (V, U, the per-bin sums M, the output transform before it is cropped)."""
+    bt, gm, at = [m.astype(dtype) for m in (mats or (BT, G, AT))]
     C, H, W = x.shape
-    d, ty, tx = _tiles(x.astype(dtype), dtype)
-    V = np.einsum("ij,tcjk,lk->iltc", BT.astype(dtype), d, BT.astype(dtype))
-    U = np.einsum("ij,ncjk,lk->ilnc", G.astype(dtype), w.astype(dtype), G.astype(dtype))
-    M = np.einsum("iltc,ilnc->iltn", V, U).astype(dtype)
-    y4 = np.einsum("ij,jktn,lk->tnil", AT.astype(dtype), M, AT.astype(dtype))                      # [T,N,2,2]
+    d, ty, tx = _tiles(x.astype(dtype), dtype, reflect)
+    V = _es("ij,tcjk,lk->iltc", bt, d, bt)
+    U = _es("ij,ncjk,lk->ilnc", gm, w.astype(dtype), gm)
+    M = _mm(V, U.swapaxes(2, 3)).astype(dtype)
+    y4 = _es("ij,jktn,lk->tnil", at, M, at)                                                       # [T,N,2,2]
     y = y4.reshape(ty, tx, -1, 2, 2).transpose(2, 0, 3, 1, 4).reshape(-1, 2 * ty, 2 * tx)
+    if keep is not None:
+        keep.update(V=V, U=U, M=M, Y=y)
     return y[:, :H, :W], V
 
 
-def wino_wgrad(V, gy):
+def wino_wgrad(V, gy, dtype=np.float64, mats=None, keep=None, P0=None):
+    """P0: the per-bin sums of the images before this one (a batch reduces over all its tiles before the tap fold)."""
+    _, gm, at = [m.astype(dtype) for m in (mats or (BT, G, AT))]
     N, H, W = gy.shape
     ty, tx = -(-H // 2), -(-W // 2)
-    gp = np.zeros((N, 2 * ty, 2 * tx))
+    gp = np.zeros((N, 2 * ty, 2 * tx), dtype)
     gp[:, :H, :W] = gy
     g4 = gp.reshape(N, ty, 2, tx, 2).transpose(1, 3, 0, 2, 4).reshape(ty * tx, N, 2, 2)
-    Dv = np.einsum("ji,tnjk,kl->iltn", AT, g4, AT)            # A dy A^T with A = AT^T
-    P = np.einsum("iltn,iltc->ilnc", Dv, V)
-    return np.einsum("ji,jknc,kl->ncil", G, P, G)             # G^T P G
+    Dv = _es("ji,tnjk,kl->iltn", at, g4, at)            # A dy A^T with A = AT^T
+    P = _mm(Dv.swapaxes(2, 3), V.astype(dtype)).astype(dtype)
+    if P0 is not None:
+        P = P + P0
+    if keep is not None:
+        keep.update(Dv=Dv, P=P)
+    return _es("ji,jknc,kl->ncil", gm, P, gm)           # G^T P G
 
 
 @pytest.mark.parametrize("C,N,H,W", [(3, 4, 8, 26), (4, 3, 9, 13), (2, 2, 1, 7), (2, 3, 2, 2)])
