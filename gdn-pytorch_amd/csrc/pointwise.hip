@@ -910,6 +910,206 @@ extern "C" int gdn_bn_eval_bwd(const void* dout, int32_t ld_dout, const void* y,
     return gdn_launch_status();
 }
 
+// ------------------------------------------------ BN backward on FROZEN statistics
+// A trained layer whose BatchNorm stays in eval(): out = [relu](y*scale + shift) with scale / shift from the RUNNING statistics.
+// dy = scale * dout * [z > 0] depends on no reduction, so one pass reads dout and y once, writes dy and leaves the per-block
+// sums of dz and dz*xhat (xhat = (y - running_mean) * invstd) that bn_bwd_finalize_kernel turns into dbeta / dgamma.
+__global__ void bn_frozen_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                        int C, float* scale, float* shift, float* mean, float* invstd) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    // (scale / shift: bn_eval_coeffs_kernel's expressions, letter for letter -- the two must agree to the bit)
+    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+    const float inv = 1.0f / sqrtf(rv[c] + eps);
+    scale[c] = g * inv;
+    shift[c] = b - rm[c] * g * inv;
+    mean[c] = rm[c];
+    invstd[c] = inv;
+}
+
+#define BNF_MAXBLK 2048
+// bn_bwd_reduce_kernel's block layout -- channel-vector lanes x pixel lanes over one contiguous pixel range per block, the same
+// 8 KB of LDS -- with the dy store added.  NH: 4-channel halves per lane (1: 16 bytes of fp32; 2: 16 bytes of bf16).
+// partial[blk][2][C]: a lane sums its pixels in order, lane 0 of each channel vector adds the pixel lanes in order -- a fixed
+// order, no atomics.  DY: dy is written, with bn_eval_bwd_kernel's arithmetic.
+template <int NH, bool DY>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(
+    const void* __restrict__ dout, int ld_dout, const void* __restrict__ y, int ldy,
+    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
+    const float* __restrict__ invstd, void* __restrict__ dy, int ld_dy, float* __restrict__ partial, int64_t npix, int C,
+    int relu, int dt) {
+    __shared__ float sh[256 * 8];
+    const int cv = C / (4 * NH);
+    const int CQ = cv < 256 ? cv : 256;      // channel-vector lanes
+    const int PY = 256 / CQ;                 // pixel lanes
+    const int tx = threadIdx.x % CQ, ty = threadIdx.x / CQ;
+    const int64_t per = cdiv64(npix, gridDim.x);
+    const int64_t p0 = blockIdx.x * per, p1 = (p0 + per < npix) ? p0 + per : npix;
+    for (int q0 = 0; q0 < cv; q0 += CQ) {    // (uniform trip count: the barriers below are reached by every lane)
+        const int q = q0 + tx;
+        const bool lane = ty < PY && q < cv;
+        const int c = q * 4 * NH;
+        f32x4 a1[NH], a2[NH];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) { a1[h] = f32x4{0.f, 0.f, 0.f, 0.f}; a2[h] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        if (lane) {
+            f32x4 s[NH], t[NH], mu[NH], is[NH];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                s[h] = *reinterpret_cast<const f32x4*>(scale + c + 4 * h);
+                t[h] = *reinterpret_cast<const f32x4*>(shift + c + 4 * h);
+                mu[h] = *reinterpret_cast<const f32x4*>(mean + c + 4 * h);
+                is[h] = *reinterpret_cast<const f32x4*>(invstd + c + 4 * h);
+            }
+            for (int64_t pix = p0 + ty; pix < p1; pix += PY) {
+                f32x4 d[NH], v[NH], o[NH];
+                if (NH == 2) ld8_any(dout, pix * ld_dout + c, dt & 1, d[0], d[NH - 1]);
+                else d[0] = ld4_any(dout, pix * ld_dout + c, dt & 1);
+                if (NH == 2) ld8_any(y, pix * ldy + c, dt & 2, v[0], v[NH - 1]);
+                else v[0] = ld4_any(y, pix * ldy + c, dt & 2);
+#pragma unroll
+                for (int h = 0; h < NH; ++h) {
+                    o[h] = d[h] * s[h];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float dz = d[h][e];
+                        if (relu) {
+                            const bool on = v[h][e] * s[h][e] + t[h][e] > 0.f;
+                            if (!on) { o[h][e] = 0.f; dz = 0.f; }
+                        }
+                        a1[h][e] += dz;
+                        a2[h][e] += dz * ((v[h][e] - mu[h][e]) * is[h][e]);
+                    }
+                }
+                if (DY) {
+                    if (NH == 2) st8_any(dy, pix * ld_dy + c, o[0], o[NH - 1], dt & 4);
+                    else st4_any(dy, pix * ld_dy + c, o[0], dt & 4);
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { sh[threadIdx.x * 8 + e] = a1[h][e]; sh[threadIdx.x * 8 + 4 + e] = a2[h][e]; }
+            __syncthreads();
+            if (ty == 0 && q < cv) {
+                f32x4 r1 = {0.f, 0.f, 0.f, 0.f}, r2 = {0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < PY; ++j) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { r1[e] += sh[(j * CQ + tx) * 8 + e]; r2[e] += sh[(j * CQ + tx) * 8 + 4 + e]; }
+                }
+                *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C + c + 4 * h) = r1;
+                *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C + c + 4 * h) = r2;
+            }
+        }
+    }
+}
+
+// The dy pass alone (the sums came from the producer of dout): nothing is reduced, so it is the flat grid-stride stream of
+// bn_eval_bwd_kernel -- that kernel itself for 4-channel lanes, this one for the 16-byte bf16 lanes; the same arithmetic.
+__global__ __launch_bounds__(256) void bn_frozen_apply8_kernel(const void* __restrict__ dout, int ld_dout,
+                                                               const void* __restrict__ y, int ldy,
+                                                               const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, void* __restrict__ dy,
+                                                               int ld_dy, int64_t npix, int C, int relu, int dt, int sh) {
+    const int co = C >> 3;
+    const int64_t total = npix * co;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t pix = sh >= 0 ? (i >> sh) : i / co;
+        const int c = (int)(sh >= 0 ? (i & (co - 1)) : (i - pix * co)) * 8;
+        f32x4 d[2], v[2], o[2];
+        ld8_any(dout, pix * ld_dout + c, dt & 1, d[0], d[1]);
+        if (relu) ld8_any(y, pix * ldy + c, dt & 2, v[0], v[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c + 4 * h);
+            o[h] = d[h] * s;
+            if (relu) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool on = v[h][e] * s[e] + t[e] > 0.f;
+                    if (!on) o[h][e] = 0.f;
+                }
+            }
+        }
+        st8_any(dy, pix * ld_dy + c, o[0], o[1], dt & 4);
+    }
+}
+
+static int bnf_blocks(int64_t npix) {
+    int64_t b = cdiv64(npix, 64);
+    if (b < 1) b = 1;
+    return (int)(b < BNF_MAXBLK ? b : BNF_MAXBLK);
+}
+
+template <int NH>
+static void bnf_launch(bool wdy, int nblk, hipStream_t st, const void* dout, int ld_dout, const void* y, int ldy,
+                       const float* scale, const float* shift, const float* mean, const float* invstd, void* dy, int ld_dy,
+                       float* partial, int64_t npix, int C, int relu, int dt) {
+#define BNF_GO(D)                                                                                                      \
+    hipLaunchKernelGGL((bn_frozen_bwd_kernel<NH, D>), dim3(nblk), dim3(256), 0, st, dout, ld_dout, y, ldy, scale, shift, \
+                       mean, invstd, dy, ld_dy, partial, npix, C, relu, dt)
+    if (wdy) BNF_GO(true);
+    else BNF_GO(false);
+#undef BNF_GO
+}
+
+extern "C" int gdn_bn_frozen_coeffs(const float* gamma, const float* beta, const float* running_mean,
+                                    const float* running_var, float eps, int32_t C, float* scale, float* shift,
+                                    float* mean, float* invstd, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!running_mean || !running_var || C <= 0 || !scale || !shift || !mean || !invstd) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(bn_frozen_coeffs_kernel, dim3(cdiv(C, 256)), dim3(256), 0, ST(stream), gamma, beta, running_mean,
+                       running_var, eps, C, scale, shift, mean, invstd);
+    return gdn_launch_status();
+}
+
+extern "C" size_t gdn_bn_frozen_bwd_workspace_bytes(int64_t npix, int32_t C) {
+    return ((size_t)bnf_blocks(npix) * 2 * C + 2 * (size_t)C) * sizeof(float);   // partials + the finalize kernel's two means
+}
+
+extern "C" int gdn_bn_frozen_bwd(const void* dout, int32_t ld_dout, const void* y, int32_t ldy, const float* scale,
+                                 const float* shift, const float* mean, const float* invstd, void* dy, int32_t ld_dy,
+                                 float* dgamma, float* dbeta, int64_t npix, int32_t C, int32_t relu,
+                                 const float* ext_partial, int64_t ext_slots, void* workspace, size_t workspace_bytes,
+                                 int32_t dtypes, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!scale || !shift || !mean || !invstd || npix <= 0 || C <= 0) return GDN_ERR_BAD_ARG;
+    if (ext_partial && (ext_slots <= 0 || ext_slots > 0x7fffffff)) return GDN_ERR_BAD_ARG;
+    const bool want_sums = dgamma || dbeta;
+    const bool sums = want_sums && !ext_partial;         // this call reduces itself
+    if ((dy || sums) && (!dout || !y)) return GDN_ERR_BAD_ARG;
+    if ((C % 4) || (ldy % 4) || (ld_dout % 4) || (dy && (ld_dy % 4))) return GDN_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < gdn_bn_frozen_bwd_workspace_bytes(npix, C)) return GDN_ERR_WORKSPACE;
+    const int nblk = bnf_blocks(npix);
+    float* partial = (float*)workspace;
+    float* k1 = partial + (size_t)nblk * 2 * C;
+    float* k2 = k1 + C;
+    const bool wide = dtypes && (C % 8) == 0 && (ldy % 8) == 0 && (ld_dout % 8) == 0 && (!dy || (ld_dy % 8) == 0);
+    if (dy && !sums) {
+        if (wide)
+            hipLaunchKernelGGL(bn_frozen_apply8_kernel, dim3(stream_blocks(npix * (C / 8))), dim3(256), 0, ST(stream), dout,
+                               ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu ? 1 : 0, dtypes, pow2_shift(C / 8));
+        else
+            hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(stream_blocks(npix * (C / 4))), dim3(256), 0, ST(stream), dout,
+                               ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu ? 1 : 0, dtypes, pow2_shift(C / 4));
+    } else if (sums) {
+        if (wide)
+            bnf_launch<2>(dy != nullptr, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, dy, ld_dy,
+                          partial, npix, C, relu ? 1 : 0, dtypes);
+        else
+            bnf_launch<1>(dy != nullptr, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, dy, ld_dy,
+                          partial, npix, C, relu ? 1 : 0, dtypes);
+    }
+    if (want_sums)
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, ST(stream),
+                           ext_partial ? ext_partial : (const float*)partial, ext_partial ? (int)ext_slots : nblk, C,
+                           (double)npix, dgamma, dbeta, k1, k2);
+    return gdn_launch_status();
+}
+
 extern "C" int gdn_upsample2x_fwd(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C,
                                   int32_t align_corners, int32_t dtypes, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread

@@ -51,6 +51,29 @@ class _HipModule(nn.Module):
         self._gdn_dtype = table[dtype]
         return self
 
+    _gdn_freeze_bn = False
+
+    def freeze_bn(self, on=True):
+        """Fine-tune on the stored running statistics: every BatchNorm2d / InstanceNorm2d below this module goes to eval() and
+        train() leaves it there while the flag is on, so the conv weights and the affine gamma / beta train through layers that
+        normalise by -- and never update -- their running mean / variance (engine._frozen_stats).  freeze_bn(False) restores
+        normal behaviour: the norm layers follow the module's mode again.  Neither changes the state_dict.  Returns self."""
+        self._gdn_freeze_bn = bool(on)
+        self.train(self.training)
+        return self
+
+    def train(self, mode=True):
+        super().train(mode)
+        frozen = set()
+        for m in self.modules():          # (a sub-module with its own flag keeps its norm layers frozen, too)
+            if isinstance(m, _HipModule) and m._gdn_freeze_bn:
+                frozen.update(id(n) for n in m.modules() if isinstance(n, (nn.BatchNorm2d, nn.InstanceNorm2d)))
+        if frozen:
+            for n in self.modules():
+                if id(n) in frozen:
+                    n.training = False
+        return self
+
     def _run(self, ctx, x):     # x: NHWC buffer -> tuple of NHWC buffers
         raise NotImplementedError
 
@@ -83,7 +106,7 @@ class _Bridge(torch.autograd.Function):
     @staticmethod
     def forward(fctx, module, arena, need_grad, select, x, anchor):
         ctx = E.Ctx(record=need_grad, arena=arena, input_needs_grad=need_grad and x.requires_grad,
-                    dtype=module._gdn_dtype)
+                    dtype=module._gdn_dtype, module_training=module.training)
         xin = E.to_nhwc(x)
         if ctx.dtype != xin.dtype and xin.shape[3] % 64 == 0:      # a 64k-channel feature map fed to a bf16 block
             xin = E.ops.cast(xin.contiguous(), ctx.dtype)
@@ -402,7 +425,7 @@ class AutoEncoder(_HipModule):
             raise GdnError("input is %dx%d but the model was built for %dx%d" %
                            (x.shape[2], x.shape[3], self.height, self.width))
         record = self.training and torch.is_grad_enabled()
-        if record and isinstance(self.N64_down, nn.InstanceNorm2d):
+        if record and isinstance(self.N64_down, nn.InstanceNorm2d) and self.N64_down.training:
             raise GdnError("AutoEncoder(norm='Instance') is inference-only on the HIP path: train-mode InstanceNorm is not "
                            "implemented for this network (build it with norm='Batch', or call eval())")
         with torch.enable_grad() if record else torch.no_grad():

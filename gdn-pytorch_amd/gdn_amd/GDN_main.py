@@ -40,6 +40,10 @@ on one GPU, two around the eager gradient all-reduce under data parallelism; the
 ``--accum_steps K`` applies the mean gradient of K loader batches in one Adam update: an effective batch of
 K x batch_size x ranks with one gradient all-reduce per update; guard, average and step count are per update.  Not with
 ``--graph`` yet.
+``--freeze_bn`` fine-tunes on the stored BatchNorm running statistics: the norm layers of the trained network
+stay in eval mode -- they normalise by their running mean / variance and never update them -- while conv weights, gamma and
+beta train.  It needs ``--init_from`` or ``--resume`` (a fresh network's statistics are mean 0 / variance 1) and is not
+stored in ``train_state.pt``: a resumed run repeats it.
 """
 import os
 import sys
@@ -135,6 +139,25 @@ def _check_accum(args):
                            "first, middle and last micro-step, which is a follow-up (drop one of the two flags)" % accum)
 
 
+def _check_freeze_bn(args):
+    """--freeze_bn trains on the stored running statistics; checked before anything touches the GPU."""
+    if not getattr(args, "freeze_bn", False):
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--freeze_bn freezes the BatchNorm statistics of a training run; --mode %s trains nothing" % args.mode)
+    if not (getattr(args, "init_from", None) or getattr(args, "resume", None)):
+        raise RuntimeError("--freeze_bn needs --init_from or --resume: the running statistics of a fresh network are mean 0 / "
+                           "variance 1, and freezing those is a mistake (start from a trained checkpoint, or drop the flag)")
+
+
+def _freeze_bn(model, args, rank):
+    """--freeze_bn on the network being trained (after --init_from; --resume loads into it afterwards)."""
+    if getattr(args, "freeze_bn", False):
+        model.freeze_bn()
+        if rank == 0:
+            print("=> %s: normalisation layers frozen on their running statistics" % type(model).__name__)
+
+
 def _resume(args, model, opt, train_loader, rank):
     """--resume: weights, optimizer, loader and progress from the state file; None without the flag."""
     path = getattr(args, "resume", None)
@@ -200,6 +223,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_ema(args)
     _check_graph(args)
     _check_accum(args)
+    _check_freeze_bn(args)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num
@@ -273,6 +297,7 @@ def run(args, train_loader=None, val_loader=None):
     if args.mode == 'DtoD':
         G = AutoEncoder_DtoD(norm=args.norm, input_dim=1, height=H, width=W).to(dev).compute_dtype(args.dtype)
         _init_from(G, args, rank)
+        _freeze_bn(G, args, rank)
         D.broadcast_parameters(G)             # rank 0's weights / BN buffers everywhere (identical seeds make this a no-op)
         opt = _make_optimizer(G, args)
         loss = train_AE_DtoD(args, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
@@ -293,6 +318,7 @@ def run(args, train_loader=None, val_loader=None):
                 G.requires_grad_(False)       # the guide only passes d(latent)/d(outputs) through
         R = _rtod_network(args, H, W).to(dev).compute_dtype(args.dtype)
         _init_from(R, args, rank)
+        _freeze_bn(R, args, rank)
         D.broadcast_parameters(R)
         opt = _make_optimizer(R, args)
         return train_AE_RtoD(args, R, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,

@@ -93,6 +93,9 @@ _SIGS = {
     "gdn_bn_bwd": (c_int32, [_P, _i32, _P, _i32, _P, _P, _P, _P, _P, _P, _i32, _P, _P, _i64, _i32, _i32, _P, _i64, _P, _sz, _i32, _P]),
     "gdn_bn_bwd_coeffs": (c_int32, [_P, _i32, _P, _i32, _P, _P, _P, _P, _P, _P, _P, _i64, _i32, _i32, _P, _i64, _P, _sz, _i32, _P]),
     "gdn_bn_eval_bwd": (c_int32, [_P, _i32, _P, _i32, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _P]),
+    "gdn_bn_frozen_coeffs": (c_int32, [_P, _P, _P, _P, _f, _i32, _P, _P, _P, _P, _P]),
+    "gdn_bn_frozen_bwd_workspace_bytes": (_sz, [_i64, _i32]),
+    "gdn_bn_frozen_bwd": (c_int32, [_P, _i32, _P, _i32, _P, _P, _P, _P, _P, _i32, _P, _P, _i64, _i32, _i32, _P, _i64, _P, _sz, _i32, _P]),
     "gdn_bn_apply_up2x": (c_int32, [_P, _P, _P, _P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
     "gdn_upsample2x_fwd": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
     "gdn_upsample2x_bwd": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
@@ -147,7 +150,8 @@ _STATUS_FUNCS = {n for n, (r, _) in _SIGS.items() if r is c_int32} - {"gdn_versi
 EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --
 # a stale build would take the arguments apart differently.  (gdn_grad_accumulate joined revision 223 without a new number:
-# _load() binds every name above, so a library built before it fails at load with the missing symbol.)
+# _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
+# and gdn_bn_frozen_bwd*, for the same reason.)
 ABI_VERSION = 223
 
 

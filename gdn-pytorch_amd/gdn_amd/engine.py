@@ -288,8 +288,9 @@ def ensure_arena(module, device):
 # Tape
 # ----------------------------------------------------------------------------
 class Ctx:
-    def __init__(self, record, arena=None, input_needs_grad=False, dtype=torch.float32):
+    def __init__(self, record, arena=None, input_needs_grad=False, dtype=torch.float32, module_training=True):
         self.record = record
+        self.module_training = module_training  # the called module is in train(): its eval-mode norm layers are frozen on purpose
         self.dtype = dtype                     # storage dtype of activations / activation gradients
         self.tape = []
         self.arena = arena
@@ -504,18 +505,44 @@ def _wgrad_into(ctx, mod, x, dy, x2=None):
         op.wgrad(x2, dy, gv, x.shape[3])
 
 
+def _eval_key(bn):
+    ar = getattr(bn.weight, "_gdn_arena", None)       # the fused Adam writes gamma / beta behind torch's version counters
+    return (_GRAPH_EPOCH, getattr(bn, "_gdn_stats_ver", 0), bn.running_mean._version, bn.running_var._version,
+            bn.weight._version, bn.bias._version, bn.running_mean.data_ptr(), bn.weight.data_ptr(),
+            None if ar is None else ar.generation)
+
+
 def _eval_coeffs(bn):
     """scale/shift of an eval-mode BatchNorm, cached until its tensors change."""
-    ar = getattr(bn.weight, "_gdn_arena", None)       # the fused Adam writes gamma / beta behind torch's version counters
-    key = (_GRAPH_EPOCH, getattr(bn, "_gdn_stats_ver", 0), bn.running_mean._version, bn.running_var._version,
-           bn.weight._version, bn.bias._version, bn.running_mean.data_ptr(), bn.weight.data_ptr(),
-           None if ar is None else ar.generation)
+    key = _eval_key(bn)
     c = getattr(bn, "_gdn_eval_cache", None)
     if c is None or c[0] != key:
         co = ops.bn_eval_coeffs(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
         c = (key, co)
         bn._gdn_eval_cache = c
     return c[1]
+
+
+def _frozen_coeffs(bn):
+    """[scale, shift, mean, invstd] of an eval-mode BatchNorm whose layer is being trained (ops.bn_frozen_coeffs), cached under
+    _eval_coeffs' key: it follows the arena generation, so a gamma / beta update by the fused Adam invalidates it."""
+    key = _eval_key(bn)
+    c = getattr(bn, "_gdn_frozen_cache", None)
+    if c is None or c[0] != key:
+        co = ops.bn_frozen_coeffs(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
+        c = (key, co)
+        bn._gdn_frozen_cache = c
+    return c[1]
+
+
+def _frozen_stats(ctx, conv, bn):
+    """A frozen-statistics trained layer (--freeze_bn): the tape is recording, the called module is in train()
+    while this norm layer stays in eval(), and the layer has something to train.  It normalises by the running statistics and
+    updates none of them, but keeps its raw conv output and trains conv weight, gamma and beta like a train-mode layer.  (A
+    module that is in eval() as a whole is inference: its layers keep the fused epilogue, and a backward reaches only layers
+    with nothing trainable.)"""
+    return bool(ctx.record and ctx.module_training and not bn.training
+                and (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad))
 
 
 def _conv_instnorm_train(ctx, x, conv, inorm, relu, op, w, reflect, need_dx):
@@ -595,10 +622,10 @@ def _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect):
     B, H, W = x.shape[0], x.shape[1], x.shape[2]
     lazy = isinstance(x, BnOut)
     fp32 = ldt == torch.float32 and x2 is None
-    # GDN_HINT_TRAIN: a trained layer in train mode (forward + backward + weight gradient) -- the frequency-domain path then
-    # tiles for the sum of both passes (40-point tiles on the 9x9 layers); frozen / eval-mode layers keep the forward-optimal
-    # plan.  Only such a layer keeps the transform-domain state of its forward (an eval-mode backward is for frozen layers).
-    train = bool(ctx.record and bn.training and conv.weight.requires_grad)
+    # GDN_HINT_TRAIN: a layer whose weight is trained (forward + backward + weight gradient), on batch statistics or on frozen
+    # ones -- the frequency-domain path then tiles for the sum of both passes (40-point tiles on the 9x9 layers); layers with a
+    # fixed weight and inference keep the forward-optimal plan.  Only such a layer keeps the transform-domain state of its forward.
+    train = bool(ctx.record and conv.weight.requires_grad and (bn.training or _frozen_stats(ctx, conv, bn)))
     path = functools.partial(ConvPath, c1_wgrad=False, up_fold=False, epilogue=conv.out_channels > 1)
     if fp32 and k >= _FFT_MIN_K and s == 1 and op.fft_ok(B, H, W, backward=ctx.record, train=train):
         if ctx.dtype == torch.bfloat16:
@@ -670,14 +697,22 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
         xt, kw = x.y, dict(in_affine=(x.co[0], x.co[1]), in_relu=x.relu)
     elif lazy:
         xt = x.dense(ctx.dtype)          # (the other loaders go straight to LDS: materialise)
-    co = None if bn.training else _eval_coeffs(bn)
+    # frozen-statistics trained layer: the running statistics normalise, nothing updates them, and the raw conv output is kept
+    # (no epilogue fold) with a train-mode layer's coefficient block, so everything downstream of a train-mode layer -- deferred
+    # activation, apply passes, the consumers' BatchNorm-backward partials -- works on it unchanged
+    frozen_stats = not bn.training and _frozen_stats(ctx, conv, bn)
+    co = None if bn.training else (_frozen_coeffs(bn) if frozen_stats else _eval_coeffs(bn))
     # eval-mode BN folded into the conv epilogue: conv + scale/shift + ReLU (+ residual) in one pass
-    fused = (not bn.training and path.epilogue and ldt == ctx.dtype and not (relu and residual is not None)
-             and (residual is None or residual.dtype == ldt))
+    fused = (not bn.training and not frozen_stats and path.epilogue and ldt == ctx.dtype
+             and not (relu and residual is not None) and (residual is None or residual.dtype == ldt))
     if fused:
         kw.update(affine=(co[0], co[1]), act=ops.ACT_RELU if relu else ops.ACT_NONE, addsrc=residual)
     r = path.fwd(xt, w, stats=bn.training, **kw)
     y, state, out_info = r, None, None   # state: what a trained transform-domain layer's forward keeps for its backward
+    if frozen_stats:
+        if isinstance(r, tuple):
+            y, state = r[0], (r[1] if len(r) > 1 else None)
+        out_info = BnOut(y, co, relu)
     if bn.training:
         y, st, state = r[0], r[1], (r[2] if len(r) > 2 else None)
         count = y.shape[0] * y.shape[1] * y.shape[2]
@@ -713,13 +748,31 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
             if da is None:
                 return
             frozen = not (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)
-            if not bn_training and not frozen:
-                raise GdnError("backward through an eval-mode BatchNorm is only implemented for frozen layers "
-                               "(requires_grad False on the conv and BN parameters): the guide network of --latent_grad")
+            if not bn_training and not frozen and not frozen_stats:
+                raise GdnError("backward through an eval-mode BatchNorm of a module in eval() is only implemented for layers "
+                               "with nothing to train (requires_grad False on the conv and BN parameters: the guide network of "
+                               "--latent_grad); to train on frozen statistics keep the module in train() and its norm layers in "
+                               "eval() (freeze_bn())")
             if residual is not None:
                 ctx.add_grad(residual, da)
             extra = {}
-            if bn_training and path.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32:
+            wtrain, written = not frozen, None   # (written None: all three parameters, as a train-mode layer always wrote them)
+            if frozen_stats:
+                # a frozen-statistics layer writes only the gradients that are asked for (NULL pointers for the rest)
+                dgam = bn.weight.grad if bn.weight.requires_grad else None
+                dbet = bn.bias.grad if bn.bias.requires_grad else None
+                wtrain = conv.weight.requires_grad
+                written = tuple(p for p in (bn.weight, bn.bias, conv.weight) if p.requires_grad)
+            if frozen_stats and path.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32:
+                # frequency-domain layer: the sums only; pass 3 of the BatchNorm backward with k1 = k2 = 0 IS scale * dz, so the
+                # dy transform applies scale and mask while loading and dy is never written
+                ops.bn_frozen_bwd(da, y, co, relu, dgam, dbet, partial=out_info.partial, need_dy=False)
+                out_info.partial = None
+                dy, extra["dyb"] = da, (y, co, ops.zeros((2, y.shape[3]), y.device), relu)
+            elif frozen_stats:
+                dy = ops.bn_frozen_bwd(da, y, co, relu, dgam, dbet, out_dtype=ldt, partial=out_info.partial)
+                out_info.partial = None
+            elif bn_training and path.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32:
                 # frequency-domain layer: dy has one reader (the dy transform), which applies pass 3 of the BatchNorm
                 # backward while loading -- dy is never written
                 kk = ops.bn_bwd_coeffs(da, y, co, relu, bn.weight.grad if not frozen else None,
@@ -735,7 +788,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
             want_dx = need_dx and ctx.wants_dx(x)
             if path.bwd is not None:
                 # one transform of dy feeds both gradients; the forward's transformed input is reused for dw
-                gv = None if frozen else _grad_tap(conv)
+                gv = _grad_tap(conv) if wtrain else None
                 if gv is not None or want_dx:
                     bnb = None
                     if xin is not None and want_dx and xin.y.dtype == torch.float32:
@@ -756,14 +809,16 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                         if bnb is not None:
                             xin.partial = bnb[3]
                 if not frozen:
-                    ctx.grads_done(bn.weight, bn.bias, conv.weight)
+                    ctx.grads_done(*(written or (bn.weight, bn.bias, conv.weight)))
                 return
             if not frozen:
-                if path.c1_wgrad and dy.is_contiguous():
+                if not wtrain:
+                    pass
+                elif path.c1_wgrad and dy.is_contiguous():
                     ops.conv_c1_wgrad(xt, dy, tap_view(conv.weight.grad, False), reflect=bool(reflect))
                 else:
                     _wgrad_into(ctx, conv, xt, dy, x2)
-                ctx.grads_done(bn.weight, bn.bias, conv.weight)
+                ctx.grads_done(*(written or (bn.weight, bn.bias, conv.weight)))
             if want_dx:
                 wt = ops.transpose_taps(_w_tap(conv)[0], dtype=ldt)
                 if x2 is None:

@@ -826,6 +826,34 @@ def bn_eval_bwd(dout, y, coeffs, relu, out_dtype=None):
     return dy
 
 
+def bn_frozen_coeffs(gamma, beta, running_mean, running_var, eps=BN_EPS):
+    """[scale, shift, mean, invstd] of a TRAINED layer whose BatchNorm stays in eval mode: bn_finalize_train's block, from the
+    running statistics (scale / shift: the bits of bn_eval_coeffs).  Updates nothing."""
+    C = running_mean.numel()
+    co = torch.empty((4, C), dtype=torch.float32, device=running_mean.device)
+    lib.gdn_bn_frozen_coeffs(_p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, C, _p(co[0]), _p(co[1]), _p(co[2]),
+                             _p(co[3]), stream())
+    return co
+
+
+def bn_frozen_bwd(dout, y, coeffs, relu, dgamma, dbeta, out_dtype=None, partial=None, need_dy=True, out=None):
+    """Backward through an eval-mode BatchNorm (+ReLU) of a trained layer, coeffs from bn_frozen_coeffs: one pass writes
+    dy = scale*dout*[z>0] (returned; the bits of bn_eval_bwd) and the sums behind dgamma / dbeta (overwritten; may be None).
+    need_dy=False: the sums only, returns None.  partial [slots,2,C]: the sums were emitted by the kernel that wrote dout.
+    out: the dy buffer (a channel slice of a wider one works)."""
+    B, H, W, C = y.shape
+    npix = B * H * W
+    dy = None
+    if need_dy:
+        dy = out if out is not None else torch.empty((B, H, W, C), dtype=out_dtype or y.dtype, device=y.device)
+    nb = int(lib.gdn_bn_frozen_bwd_workspace_bytes(npix, C))
+    ws = workspace(nb, y.device, "bnbwd")
+    lib.gdn_bn_frozen_bwd(_p(dout), 0 if dout is None else _ld(dout), _p(y), _ld(y), _p(coeffs[0]), _p(coeffs[1]), _p(coeffs[2]), _p(coeffs[3]),
+                          _p(dy), 0 if dy is None else _ld(dy), _p(dgamma), _p(dbeta), npix, C, 1 if relu else 0,
+                          _p(partial), 0 if partial is None else partial.shape[0], _p(ws), nb, _mask(dout, y, dy), stream())
+    return dy
+
+
 def upsample2x(x, align_corners=False):
     B, H, W, C = x.shape
     if not x.is_contiguous():

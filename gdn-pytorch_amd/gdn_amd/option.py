@@ -1,7 +1,7 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
---graph_warmup, --accum_steps).
+--graph_warmup, --accum_steps, --freeze_bn).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -126,6 +126,11 @@ def build_parser():
                         'K x batch_size x ranks at the given learning rate, with one gradient all-reduce per update.  '
                         'BatchNorm statistics and the BerHu threshold stay per batch, as they are per replica under data '
                         'parallelism; not with --graph yet; 1 = off')
+    p.add_argument('--freeze_bn', action='store_true',
+                   help='training (with --init_from or --resume): fine-tune on the stored BatchNorm running statistics -- every '
+                        'normalisation layer of the trained network stays in eval mode, normalises by its running mean / '
+                        'variance and never updates them, while the conv weights and the affine gamma / beta train; the flag is '
+                        'not stored in train_state.pt, a resumed run repeats it')
     return p
 
 

@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 /* The GDN_HINT_* bits (below) this library acts on.  A binding that sets a bit that CHANGES WHAT IS COMPUTED (GDN_HINT_FLIP_TAPS)
@@ -472,6 +472,30 @@ int gdn_bn_bwd_coeffs(const void* dout, int32_t ld_dout, const void* y, int32_t 
 int gdn_bn_eval_bwd(const void* dout, int32_t ld_dout, const void* y, int32_t ldy,
                     const float* scale, const float* shift, void* dy, int32_t ld_dy,
                     int64_t npix, int32_t C, int32_t relu, int32_t dtypes, void* stream);
+
+/* A TRAINED layer whose BatchNorm stays in eval mode (--freeze_bn: fine-tuning on the stored running statistics).
+ * gdn_bn_frozen_coeffs fills the four rows gdn_bn_finalize_train leaves for a train-mode layer from the running
+ * statistics: scale / shift exactly as gdn_bn_eval_coeffs (same bits), mean = running_mean, invstd = 1/sqrtf(running_var + eps);
+ * nothing is updated. */
+int gdn_bn_frozen_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                         float eps, int32_t C, float* scale, float* shift, float* mean, float* invstd, void* stream);
+/* Backward of out = [relu](y*scale + shift) with those coefficients, parameter gradients included:
+ *   dy = scale*dout*[z>0] (the bits of gdn_bn_eval_bwd, relu 0 / 1), dbeta = sum(dz), dgamma = sum(dz*xhat) with
+ *   dz = dout*[z>0], xhat = (y - mean)*invstd.
+ * dy depends on no reduction: ONE kernel reads dout and y once, writes dy and per-block partial sums (a grid that is a
+ * function of (npix, C) only, a fixed summation order, no atomics), and the finalize kernel of gdn_bn_bwd turns those into
+ * dgamma / dbeta (overwritten; either may be NULL, both NULL: no sums at all).  Operands, pitches, C % 4 and `dtypes`
+ * (bit0 dout, bit1 y, bit2 dy) as in gdn_bn_bwd; workspace from gdn_bn_frozen_bwd_workspace_bytes.
+ * dy == NULL: the sums only (a consumer applies scale and mask itself: gdn_fftconv_bwd dyb_* with kk = 0).
+ * ext_partial (nullable, [ext_slots][2][C]): the sums were emitted by the epilogue of the kernel that wrote dout; only the
+ * finalize kernel and the dy pass run (with dy == NULL as well, dout / y may be NULL). */
+size_t gdn_bn_frozen_bwd_workspace_bytes(int64_t npix, int32_t C);
+int gdn_bn_frozen_bwd(const void* dout, int32_t ld_dout, const void* y, int32_t ldy,
+                      const float* scale, const float* shift, const float* mean, const float* invstd,
+                      void* dy, int32_t ld_dy, float* dgamma, float* dbeta,
+                      int64_t npix, int32_t C, int32_t relu,
+                      const float* ext_partial, int64_t ext_slots,
+                      void* workspace, size_t workspace_bytes, int32_t dtypes, void* stream);
 
 /* ------------------------------------------------------------------------
  * x2 bilinear up-sampling: F.interpolate(align_corners=False) AE_model_unet.py:336,343,349,355
