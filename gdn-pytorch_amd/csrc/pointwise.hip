@@ -757,6 +757,100 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict_
 // one lane per 16 bytes (VEC) or per float, capped like the Adam update's grid; the rest is grid-strided
 inline int stream_rw_blocks(int64_t n, bool vec) { return stream_blocks(vec ? cdiv64(n, 4) : n, 256, 4096); }
 
+// ---- segmented forms (include/gdn_hip.h): one launch over an arena whose 64-float chunks belong to parameter groups.  map[c] is
+// the group of chunk c or SEG_SKIP.  A lane moves 16 bytes, so the 16 lanes l, l+1, ... l+15 (l % 16 == 0) of a wave share one
+// chunk in every trip of the grid-stride loop (the stride is a multiple of 256 and n of 64, so such a lane group is inside the
+// arena or outside it as a whole): its first lane reads the map byte and the others take it from that lane.  No atomics, no LDS.
+constexpr int SEG_SKIP = 0xFF;
+static_assert(sizeof(AdamDevState) == 32, "the step-state table is G x 32 bytes (include/gdn_hip.h)");
+__device__ __forceinline__ int seg_group(const uint8_t* __restrict__ map, int64_t i, bool inside) {
+    const int lane = (int)(threadIdx.x & 63u);
+    int k = SEG_SKIP;
+    if (inside && (lane & 15) == 0) k = (int)map[i >> 4];
+    return __shfl(k, lane & ~15);
+}
+__global__ __launch_bounds__(256) void adam_prep_seg_kernel(AdamDevState* states, const float* __restrict__ hyper, int G,
+                                                            const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;    // a skipped step takes no place in any group's bias corrections
+    const int k = (int)threadIdx.x;
+    if (k < G) adam_advance(states + k, hyper + 6 * k);
+}
+// One element of adam_update with the roundings of that loop's gfx950 code spelled out, so the bits are the same whatever
+// the compiler would contract in a four-wide body: there the weight decay is fused into the scaled gradient
+// (fma(wd, p, g * gscale)) and every other product and sum is rounded on its own.  tests/test_hip_seg_adam.py holds the two
+// forms to bit identity.
+__device__ __forceinline__ void adam_update1(float& p, float g, float& m, float& v, float step, float b1, float b2, float eps,
+                                             float wd, float bc2s, float gscale) {
+#pragma clang fp contract(off)
+    const float pi = p;
+    const float gi = fmaf(wd, pi, g * gscale);
+    const float mi = b1 * m + (1.f - b1) * gi;
+    const float vi = b2 * v + (1.f - b2) * gi * gi;
+    m = mi; v = vi;
+    p = pi - step * mi / (sqrtf(vi) / bc2s + eps);
+}
+__global__ __launch_bounds__(256) void adam_seg_kernel(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
+                                                       f32x4* __restrict__ v, int64_t nvec, const uint8_t* __restrict__ map,
+                                                       const float* __restrict__ hyper, const AdamDevState* __restrict__ states,
+                                                       const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;    // p, m, v are neither read nor written
+    const int64_t T = (int64_t)gridDim.x * 256;
+    for (int64_t i0 = blockIdx.x * 256ll; i0 < nvec; i0 += T) {      // (block-uniform bound: every lane reaches the shuffle)
+        const int64_t i = i0 + threadIdx.x;
+        const int k = seg_group(map, i, i < nvec);
+        if (k == SEG_SKIP) continue;
+        const float* __restrict__ h = hyper + 6 * k;
+        const AdamDevState* st = states + k;
+        const float gscale = guard != nullptr ? h[5] * guard->coef : h[5];
+        const float step = h[0] / st->bc1, b1 = h[1], b2 = h[2], eps = h[3], wd = h[4], bc2s = st->bc2s;
+        const f32x4 gi = g[i];
+        const f32x4 p4 = p[i], m4 = m[i], v4 = v[i];
+        float pe[4] = {p4.x, p4.y, p4.z, p4.w}, me[4] = {m4.x, m4.y, m4.z, m4.w}, ve[4] = {v4.x, v4.y, v4.z, v4.w};
+        const float ge[4] = {gi.x, gi.y, gi.z, gi.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) adam_update1(pe[e], ge[e], me[e], ve[e], step, b1, b2, eps, wd, bc2s, gscale);
+        m[i] = f32x4{me[0], me[1], me[2], me[3]};
+        v[i] = f32x4{ve[0], ve[1], ve[2], ve[3]};
+        p[i] = f32x4{pe[0], pe[1], pe[2], pe[3]};
+    }
+}
+// stage 1 of gdn_grad_sumsq_seg: adam_gradnorm_partial_kernel over the chunks that are not skipped (a skipped chunk is not
+// read, so a NaN there stays out of the sum); the same grid, the same per-lane partials and the same block reduction.
+__global__ __launch_bounds__(256) void adam_gradnorm_seg_partial_kernel(const f32x4* __restrict__ gv, int64_t nvec,
+                                                                  const uint8_t* __restrict__ map, double* __restrict__ partial) {
+    __shared__ double sh[4];
+    const int64_t T = (int64_t)gridDim.x * 256;
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i0 = blockIdx.x * 256ll; i0 < nvec; i0 += 2 * T) {
+        const int64_t i = i0 + threadIdx.x, j = i + T;
+        const int k0 = seg_group(map, i, i < nvec), k1 = seg_group(map, j, j < nvec);
+        f32x4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = {0.f, 0.f, 0.f, 0.f};
+        if (k0 != SEG_SKIP) x0 = gv[i];
+        if (k1 != SEG_SKIP) x1 = gv[j];
+        a0 += sq4_d(x0); a1 += sq4_d(x1);
+    }
+    const double s = block_sum_d256(a0 + a1, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+// ema_update_kernel per chunk: the warm-up weight comes from the step count of the chunk's own group
+__global__ __launch_bounds__(256) void ema_update_seg_kernel(f32x4* __restrict__ ev, const f32x4* __restrict__ pv, int64_t nvec,
+                                                      const uint8_t* __restrict__ map, double decay,
+                                                      const AdamDevState* __restrict__ states, const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;
+    const int64_t T = (int64_t)gridDim.x * 256;
+    for (int64_t i0 = blockIdx.x * 256ll; i0 < nvec; i0 += T) {
+        const int64_t i = i0 + threadIdx.x;
+        const int k = seg_group(map, i, i < nvec);
+        if (k == SEG_SKIP) continue;
+        const double t = (double)states[k].step;
+        const float w = (float)(1.0 - fmin(decay, (1.0 + t) / (10.0 + t)));
+        const f32x4 x = pv[i];
+        f32x4 a = ev[i];
+        a.x = ema1(w, x.x, a.x); a.y = ema1(w, x.y, a.y); a.z = ema1(w, x.z, a.z); a.w = ema1(w, x.w, a.w);
+        ev[i] = a;
+    }
+}
+
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
@@ -1322,6 +1416,44 @@ extern "C" int gdn_grad_accumulate(float* acc, const float* g, int64_t n, void* 
     const bool vec = (((uintptr_t)acc ^ (uintptr_t)g) & 15) == 0;
     const auto kernel = vec ? grad_accumulate_kernel<true> : grad_accumulate_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), acc, g, n);
+    return gdn_launch_status();
+}
+
+// ---- segmented Adam family (include/gdn_hip.h).  The map's CONTENTS are the caller's: entries < G or 0xFF.
+static bool seg_bad_range(int64_t n, const void* map, const void* a, const void* b, const void* c, const void* d) {
+    return n <= 0 || (n & 63) != 0 || !map || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) != 0;
+}
+extern "C" int gdn_adam_step_seg(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* map, int32_t G,
+                                 const float* hyper, void* states, const void* guard, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !g || !m || !v || !hyper || !states || G < 1 || G > 254 || seg_bad_range(n, map, p, g, m, v)) return GDN_ERR_BAD_ARG;
+    if (((uintptr_t)hyper & 3) || ((uintptr_t)states & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(adam_prep_seg_kernel, dim3(1), dim3(256), 0, ST(stream), (AdamDevState*)states, hyper, (int)G,
+                       (const AdamGuard*)guard);
+    hipLaunchKernelGGL(adam_seg_kernel, dim3(stream_rw_blocks(n, true)), dim3(256), 0, ST(stream), (f32x4*)p, (const f32x4*)g,
+                       (f32x4*)m, (f32x4*)v, n / 4, map, hyper, (const AdamDevState*)states, (const AdamGuard*)guard);
+    return gdn_launch_status();
+}
+extern "C" int gdn_grad_sumsq_seg(const float* g, int64_t n, const uint8_t* map, void* guard, int32_t accumulate, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!g || !guard || seg_bad_range(n, map, g, nullptr, nullptr, nullptr)) return GDN_ERR_BAD_ARG;
+    if (((uintptr_t)guard & 7) || ((uintptr_t)workspace & 7)) return GDN_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < gdn_grad_sumsq_workspace_bytes(n)) return GDN_ERR_WORKSPACE;
+    const int nb = gradnorm_blocks(n);
+    hipLaunchKernelGGL(adam_gradnorm_seg_partial_kernel, dim3(nb), dim3(256), 0, ST(stream), (const f32x4*)g, n / 4, map,
+                       (double*)workspace);
+    hipLaunchKernelGGL(adam_gradnorm_final_kernel, dim3(1), dim3(256), 0, ST(stream), (const double*)workspace, nb,
+                       (AdamGuard*)guard, accumulate);
+    return gdn_launch_status();
+}
+extern "C" int gdn_ema_update_seg(float* ema, const float* p, int64_t n, const uint8_t* map, double decay, const void* states,
+                                  const void* guard, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!ema || !p || !states || !(decay > 0.0 && decay < 1.0) || seg_bad_range(n, map, ema, p, nullptr, nullptr)) return GDN_ERR_BAD_ARG;
+    if (((uintptr_t)states & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(ema_update_seg_kernel, dim3(stream_rw_blocks(n, true)), dim3(256), 0, ST(stream), (f32x4*)ema, (const f32x4*)p,
+                       n / 4, map, decay, (const AdamDevState*)states, (const AdamGuard*)guard);
     return gdn_launch_status();
 }
 

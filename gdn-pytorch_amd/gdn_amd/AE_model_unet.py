@@ -9,13 +9,25 @@ forward/backward execute the hand-written gfx950 kernels through
 ``gdn_amd.engine``.  Tensors at the boundary are NCHW like the reference's;
 returned feature maps are zero-copy NCHW views of NHWC device buffers.
 """
+import fnmatch
 import math
+import re
 
 import torch
 import torch.nn as nn
 
 from . import engine as E
 from ._lib import GdnError
+
+
+_ENCODER = re.compile(r"downconv\d|res\d+_down\d|res512_\d|N\d+_down")
+
+
+def _in_encoder(name):
+    """Whether parameter `name` (a state_dict key) belongs to a layer the forward of the three networks runs before upconv0:
+    the downconv / res*_down* stages and the bottleneck blocks res512_1..6 (for the legacy AutoEncoder also its N*_down norm
+    layers) -- for AutoEncoder_DtoD exactly what guide_features() runs."""
+    return _ENCODER.fullmatch(name.split(".")[0]) is not None
 
 
 def _check_norm(norm):
@@ -74,6 +86,37 @@ class _HipModule(nn.Module):
                     n.training = False
         return self
 
+    def select_parameters(self, spec):
+        """Names (state_dict keys) of the parameters a SPEC of --freeze / --lr_mult selects, in parameter order: 'encoder' --
+        every layer the forward runs before upconv0 (what AutoEncoder_DtoD.guide_features runs) --, 'decoder' -- the rest --,
+        or an fnmatch pattern on the names."""
+        names = [n for n, _ in self.named_parameters()]
+        if spec == "encoder":
+            return [n for n in names if _in_encoder(n)]
+        if spec == "decoder":
+            return [n for n in names if not _in_encoder(n)]
+        return [n for n in names if fnmatch.fnmatchcase(n, spec)]
+
+    def freeze(self, specs):
+        """requires_grad = False on every parameter one of `specs` selects (select_parameters; a string is one SPEC).  A SPEC
+        that selects nothing is an error, and so is a network with nothing left to train.  Normalisation layers keep their
+        mode, as in torch: frozen gamma / beta still see batch statistics and the running statistics still move -- freeze_bn()
+        holds those.  The optimizer (optim.Adam(segmented=True)) skips frozen parameters and the backward does no work below
+        the lowest trainable layer.  Returns the names it froze."""
+        specs = [specs] if isinstance(specs, str) else list(specs)
+        params = dict(self.named_parameters())
+        frozen = []
+        for spec in specs:
+            hit = self.select_parameters(spec)
+            if not hit:
+                raise GdnError("freeze: %r selects no parameter of %s" % (spec, type(self).__name__))
+            frozen += [n for n in hit if n not in frozen]
+        if len(frozen) == len(params) or not any(p.requires_grad for n, p in params.items() if n not in frozen):
+            raise GdnError("freeze: %s would leave nothing to train" % ", ".join(repr(s) for s in specs))
+        for n in frozen:
+            params[n].requires_grad_(False)
+        return frozen
+
     def _run(self, ctx, x):     # x: NHWC buffer -> tuple of NHWC buffers
         raise NotImplementedError
 
@@ -127,7 +170,7 @@ class _Bridge(torch.autograd.Function):
         trainable = any(p.requires_grad for p in fctx.gdn_module.parameters())
         pending = E.begin_backward(fctx.gdn_module, arena, ctx, trainable)
         for o, g in zip(outs, gouts):
-            if g is None:
+            if g is None or not ctx.is_live(o):      # (an output nothing trainable feeds: a frozen encoder's feature map)
                 continue
             ctx.add_grad(o, E.grad_to_nhwc(g))
         ctx.backward()

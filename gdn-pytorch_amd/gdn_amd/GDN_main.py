@@ -44,7 +44,14 @@ K x batch_size x ranks with one gradient all-reduce per update; guard, average a
 stay in eval mode -- they normalise by their running mean / variance and never update them -- while conv weights, gamma and
 beta train.  It needs ``--init_from`` or ``--resume`` (a fresh network's statistics are mean 0 / variance 1) and is not
 stored in ``train_state.pt``: a resumed run repeats it.
+``--freeze SPEC[,SPEC...]`` (``encoder``, ``decoder`` or name patterns) trains only part of the network, ``--lr_mult SPEC=M,...``
+trains parts of it at a multiple of the learning rate and ``--no_decay_norm`` takes the weight decay off gamma / beta
+(DESIGN.md 3.8): the param groups they build all run in the fused Adam's one launch (``optim.Adam(segmented=True)``), and the
+backward does no work below the lowest trainable layer.  ``--freeze`` needs ``--init_from`` or ``--resume``; none of the three
+is stored in ``train_state.pt``: a resumed run repeats them.
 """
+import contextlib
+import io
 import os
 import sys
 
@@ -52,6 +59,7 @@ import torch
 
 from . import distributed as D
 from . import option
+from . import utils as U
 from .AE_model_unet import AutoEncoder, AutoEncoder_2, AutoEncoder_DtoD
 from .optim import Adam
 from .synthetic import SyntheticLoader
@@ -73,7 +81,41 @@ def _make_optimizer(model, args):
         guard["ema_decay"] = float(args.ema_decay)
     if getattr(args, "graph", False):
         guard["capturable"] = True            # the step counter lives on the device (the guard and the average imply it)
-    return Adam(model.parameters(), args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
+    params = model.parameters()
+    if _partial(args):
+        # --freeze / --lr_mult / --no_decay_norm: param groups over the one arena, all of them in the fused Adam's one launch
+        params, guard["segmented"] = param_groups(model, args), True
+    return Adam(params, args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
+
+
+def _partial(args):
+    return bool(getattr(args, "freeze", None) or getattr(args, "lr_mult", None) or getattr(args, "no_decay_norm", False))
+
+
+def param_groups(model, args):
+    """The param groups of --lr_mult / --no_decay_norm: one per distinct (lr_mult, weight_decay), in order of first
+    appearance among model.parameters(); every parameter is in one (a frozen one too: the optimizer skips it by its
+    requires_grad).  A group states 'lr_mult' only where it is not 1 and 'weight_decay' only where it is not the optimizer's."""
+    names = [n for n, _ in model.named_parameters()]
+    mult = dict.fromkeys(names, 1.0)
+    for spec, m in getattr(args, "lr_mult", None) or []:
+        hit = model.select_parameters(spec)
+        if not hit:
+            raise RuntimeError("--lr_mult %s=%g selects no parameter of %s" % (spec, m, type(model).__name__))
+        mult.update(dict.fromkeys(hit, float(m)))            # later entries win
+    groups = {}
+    for n, p in model.named_parameters():
+        decay = 0.0 if getattr(args, "no_decay_norm", False) and p.dim() == 1 else None
+        groups.setdefault((mult[n], decay), []).append(p)
+    out = []
+    for (m, decay), ps in groups.items():
+        g = {"params": ps}
+        if m != 1.0:
+            g["lr_mult"] = m
+        if decay is not None:
+            g["weight_decay"] = decay
+        out.append(g)
+    return out
 
 
 def _rtod_network(args, H, W):
@@ -158,6 +200,36 @@ def _freeze_bn(model, args, rank):
             print("=> %s: normalisation layers frozen on their running statistics" % type(model).__name__)
 
 
+def _check_partial(args, H, W):
+    """--freeze / --lr_mult / --no_decay_norm, checked before anything touches the GPU: the SPECs are matched against the
+    trained network's parameter names on a network built without storage."""
+    if not _partial(args):
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--freeze / --lr_mult / --no_decay_norm shape the optimizer of a training run; --mode %s trains "
+                           "nothing" % args.mode)
+    if getattr(args, "freeze", None) and not (getattr(args, "init_from", None) or getattr(args, "resume", None)):
+        raise RuntimeError("--freeze needs --init_from or --resume: freezing the random weights of a fresh network is a "
+                           "mistake (start from a trained checkpoint, or drop the flag)")
+    with torch.device("meta"), contextlib.redirect_stdout(io.StringIO()):
+        net = AutoEncoder_DtoD(norm=args.norm, input_dim=1, height=H, width=W) if args.mode == 'DtoD' else _rtod_network(args, H, W)
+    try:
+        if getattr(args, "freeze", None):
+            net.freeze(args.freeze)
+    except U.GdnError as e:
+        raise RuntimeError("--freeze %s: %s" % (",".join(args.freeze), e))
+    param_groups(net, args)              # (an --lr_mult SPEC that selects nothing)
+
+
+def _freeze(model, args, rank):
+    """--freeze on the network being trained (before the optimizer is built; --resume loads into it afterwards)."""
+    if getattr(args, "freeze", None):
+        frozen = model.freeze(args.freeze)
+        if rank == 0:
+            print("=> %s: %d of %d parameter tensors frozen (%s)" % (type(model).__name__, len(frozen),
+                                                                  sum(1 for _ in model.parameters()), ",".join(args.freeze)))
+
+
 def _resume(args, model, opt, train_loader, rank):
     """--resume: weights, optimizer, loader and progress from the state file; None without the flag."""
     path = getattr(args, "resume", None)
@@ -224,6 +296,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_graph(args)
     _check_accum(args)
     _check_freeze_bn(args)
+    _check_partial(args, args.height, args.width)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu_num.split(",")[0]   # reference: CUDA_VISIBLE_DEVICES=--gpu_num
@@ -298,6 +371,7 @@ def run(args, train_loader=None, val_loader=None):
         G = AutoEncoder_DtoD(norm=args.norm, input_dim=1, height=H, width=W).to(dev).compute_dtype(args.dtype)
         _init_from(G, args, rank)
         _freeze_bn(G, args, rank)
+        _freeze(G, args, rank)
         D.broadcast_parameters(G)             # rank 0's weights / BN buffers everywhere (identical seeds make this a no-op)
         opt = _make_optimizer(G, args)
         loss = train_AE_DtoD(args, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
@@ -319,6 +393,7 @@ def run(args, train_loader=None, val_loader=None):
         R = _rtod_network(args, H, W).to(dev).compute_dtype(args.dtype)
         _init_from(R, args, rank)
         _freeze_bn(R, args, rank)
+        _freeze(R, args, rank)
         D.broadcast_parameters(R)
         opt = _make_optimizer(R, args)
         return train_AE_RtoD(args, R, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,

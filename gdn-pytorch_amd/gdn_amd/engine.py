@@ -31,6 +31,9 @@ _FLIP_TAPS_K = (3, 5, 7)
 # train-mode BatchNorm: scale/shift/ReLU of a ResidualBlock's first half applied in the consumer's loader, BatchNorm-backward
 # reductions emitted by the data-gradient epilogues
 _FUSE_TRAIN_BN = True
+# No backward work below the lowest trainable layer (Ctx.is_live).  False: every activation counts as live, the
+# backward of a partly frozen network runs as it did before -- the A/B switch of tests/test_hip_partial_finetune.py.
+_PRUNE_FROZEN = True
 # x2 bilinear upsampling folded into the consumer convolution's loader and its backward's fold pass (north_star "bilinear-interp
 # ... fused"; csrc/up2x.h)
 _FUSE_UP2X = True
@@ -300,6 +303,7 @@ class Ctx:
         self.reducer = None                    # distributed.GradReducer while a backward is running
         self.bn_src = {}                       # id(activation) -> BnOut of the train-mode BatchNorm that produced it
         self.up_src = {}                       # id(upsampled tensor) -> (its low-resolution source, up2x mode): conv_bn_act(up_out=)
+        self.live = {}                         # id(activation) -> the activation, for every live one (is_live)
 
     def grads_done(self, *params):
         """Parameters whose gradient has just been written (lets the all-reduce start early)."""
@@ -319,8 +323,27 @@ class Ctx:
         return info if info is not None and info.claim() else None
 
     def wants_dx(self, x):
-        """Data gradients stop at the network input unless the caller asked for them."""
-        return x is not self.input or self.input_needs_grad
+        """Data gradients stop at the network input unless the caller asked for them -- and at every activation that is not
+        live: nothing it descends from trains (a frozen encoder), so no gradient below it is ever read."""
+        return (x is not self.input or self.input_needs_grad) and self.is_live(x)
+
+    # liveness (DESIGN.md 3.8): an activation is live when it descends from a trainable parameter or from an input that needs
+    # a gradient.  Nothing adds a gradient into an activation that is not live, so the layer that produced it finds none and
+    # its backward returns at once: no backward work below the lowest trainable layer.
+    def _descends(self, x):
+        return id(x) in self.live or (x is self.input and self.input_needs_grad)
+
+    def is_live(self, x):
+        return not _PRUNE_FROZEN or self._descends(x)
+
+    def mark_live(self, out, inputs=(), params=()):
+        """Called by every tape op while it records: `out` (a tensor, a BnOut or an Up2x) is live if one of `inputs` is, or
+        one of `params` trains.  Returns `out`."""
+        if not self.record:
+            return out
+        if any(p is not None and p.requires_grad for p in params) or any(x is not None and self._descends(x) for x in inputs):
+            self.live[id(out)] = out
+        return out
 
     # gradient slots are keyed by tensor identity
     def add_grad(self, t, g):
@@ -348,6 +371,7 @@ class Ctx:
         for fn in reversed(self.tape):
             fn()
         self.tape = None      # drop the saved activations
+        self.live = {}
 
 
 def _chan_slice(t):
@@ -419,9 +443,11 @@ class Up2x:
         x, align = self.src, self.align
         y = ops.upsample2x(x, align)
         if ctx.record:
+            ctx.mark_live(y, (x, self))
+
             def bwd():
                 dy = ctx.pop_grad(y)
-                if dy is None:
+                if dy is None or not ctx.is_live(x):
                     return
                 ctx.add_grad(x, ops.upsample2x_bwd(_dense(dy), align))
             ctx.tape.append(bwd)
@@ -573,6 +599,7 @@ def _conv_instnorm_train(ctx, x, conv, inorm, relu, op, w, reflect, need_dx):
     a = torch.cat(outs, 0)
     if ctx.record:
         in_hw = (H, W)
+        ctx.mark_live(a, (x,), (conv.weight, inorm.weight, inorm.bias))
 
         def bwd():
             da = ctx.pop_grad(a)
@@ -742,6 +769,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
     if ctx.record:
         in_hw = (x.shape[1], x.shape[2])
         bn_training = bn.training
+        ctx.mark_live(a, (x, x2, residual), (conv.weight, bn.weight, bn.bias))
 
         def bwd():
             da = ctx.pop_grad(a)
@@ -753,7 +781,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                                "with nothing to train (requires_grad False on the conv and BN parameters: the guide network of "
                                "--latent_grad); to train on frozen statistics keep the module in train() and its norm layers in "
                                "eval() (freeze_bn())")
-            if residual is not None:
+            if residual is not None and ctx.is_live(residual):
                 ctx.add_grad(residual, da)
             extra = {}
             wtrain, written = not frozen, None   # (written None: all three parameters, as a train-mode layer always wrote them)
@@ -785,7 +813,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                 out_info.partial = None
             else:
                 dy = ops.bn_eval_bwd(da, y, co, (2 if fused else 1) if relu else 0, out_dtype=ldt)
-            want_dx = need_dx and ctx.wants_dx(x)
+            want_dx = need_dx and (ctx.wants_dx(x) or (x2 is not None and ctx.wants_dx(x2)))
             if path.bwd is not None:
                 # one transform of dy feeds both gradients; the forward's transformed input is reused for dw
                 gv = _grad_tap(conv) if wtrain else None
@@ -843,8 +871,10 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
                 else:
                     dcat = op.dgrad(dy, wt, in_hw)
                     c1 = x.shape[3]
-                    ctx.add_grad(x, dcat[..., :c1])
-                    ctx.add_grad(x2, dcat[..., c1:])
+                    if ctx.is_live(x):
+                        ctx.add_grad(x, dcat[..., :c1])
+                    if ctx.is_live(x2):       # (the skip connection of a frozen encoder is not)
+                        ctx.add_grad(x2, dcat[..., c1:])
         ctx.tape.append(bwd)
     if up_out is None:
         return a
@@ -854,6 +884,7 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
     if ctx.record:
         align = bool(up_out)
         ctx.up_src[id(a_up)] = (a, 2 if align else 1)
+        ctx.mark_live(a_up, (a,))
 
         def up_bwd():                    # (after this tape entry in the forward = before the layer's own backward)
             dup = ctx.pop_grad(a_up)     # None when the consumer's fold pass already wrote dL/da (the usual case)
@@ -873,6 +904,7 @@ def conv_head_tanh(ctx, x, conv):
     out = op.fwd(x, w, act=ops.ACT_TANH)
     if ctx.record:
         in_hw = (x.shape[1], x.shape[2])
+        ctx.mark_live(out, (x,), (conv.weight,))
 
         def bwd():
             do = ctx.pop_grad(out)
@@ -889,6 +921,8 @@ def conv_head_tanh(ctx, x, conv):
                 else:
                     _wgrad_into(ctx, conv, x, dpre)
                 ctx.grads_done(conv.weight)
+            if not ctx.is_live(x):
+                return                   # only the head trains: nothing below it needs a gradient
             if c1:
                 dx = ops.conv_c1_fwd(dpre, w, flip=not tr, addsrc=ctx.pop_grad(x))      # fp32, like the generic path's
             else:
@@ -910,6 +944,7 @@ def conv_plain(ctx, x, conv, x2=None):
     y = op.fwd(x, w, x2=x2)
     if ctx.record:
         in_hw = (x.shape[1], x.shape[2])
+        ctx.mark_live(y, (x, x2), (conv.weight,))
 
         def bwd():
             dy = ctx.pop_grad(y)
@@ -925,11 +960,13 @@ def conv_plain(ctx, x, conv, x2=None):
             if x2 is None:
                 if ctx.wants_dx(x):
                     ctx.grads[id(x)] = (x, op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(x, ldt)))
-            else:
+            elif ctx.is_live(x) or ctx.is_live(x2):
                 dcat = op.dgrad(dy, wt, in_hw)
                 c1 = x.shape[3]
-                ctx.add_grad(x, dcat[..., :c1])
-                ctx.add_grad(x2, dcat[..., c1:])
+                if ctx.is_live(x):
+                    ctx.add_grad(x, dcat[..., :c1])
+                if ctx.is_live(x2):
+                    ctx.add_grad(x2, dcat[..., c1:])
         ctx.tape.append(bwd)
     return y
 
@@ -939,10 +976,11 @@ def upsample(ctx, x, align_corners=False):
     ConvBlock's loader interpolates; see conv_bn_act."""
     ctx.claim(x)
     if isinstance(x, BnOut):
-        x = x.dense(ctx.dtype)
+        x = ctx.mark_live(x.dense(ctx.dtype), (x,))
+    up = ctx.mark_live(Up2x(x, align_corners), (x,))
     if _FUSE_UP2X and ctx.dtype == torch.float32 and x.dtype == torch.float32 and x.is_contiguous():
-        return Up2x(x, align_corners)
-    return Up2x(x, align_corners).dense(ctx)
+        return up
+    return up.dense(ctx)
 
 
 # ----------------------------------------------------------------------------

@@ -1330,6 +1330,44 @@ def ema_update(ema, p, decay, state, guard=None):
     lib.gdn_ema_update(_p(ema), _p(p), p.numel(), float(decay), _p(state), _p(guard), stream())
 
 
+def _seg_groups(n, chunk_map, hyper, states):
+    """G of a segmented call, after the checks the library leaves to its caller: one map byte per 64-float chunk, one hyper
+    row and one 32-byte step state per group.  (The map's contents are checked where it is built: optim._Plan.)"""
+    if chunk_map.dtype != torch.uint8 or chunk_map.numel() * 64 != n:
+        raise GdnError("segmented Adam: a chunk map of %d %s entries for %d floats" % (chunk_map.numel(), chunk_map.dtype, n))
+    G = states.numel() // 32
+    if states.dtype != torch.uint8 or states.numel() != 32 * G or (hyper is not None and hyper.numel() != 6 * G):
+        raise GdnError("segmented Adam: %d bytes of step states beside %s hyper-parameters" %
+                       (states.numel(), "no" if hyper is None else hyper.numel()))
+    return G
+
+
+def adam_step_seg(p, g, m, v, chunk_map, hyper, states, guard=None):
+    """The capturable Adam update of every parameter group of an arena in ONE update launch: chunk_map uint8[n / 64] gives the
+    group of each 64-float chunk (0xFF: skip it), hyper float32[G, 6], states uint8[G * 32]; guard None for the unguarded
+    update (gdn_adam_step_seg)."""
+    n = p.numel()
+    G = _seg_groups(n, chunk_map, hyper, states)
+    lib.gdn_adam_step_seg(_p(p), _p(g), _p(m), _p(v), n, _p(chunk_map), G, _p(hyper), _p(states), _p(guard), stream())
+
+
+def grad_sumsq_seg(g, chunk_map, guard, accumulate=False):
+    """grad_sumsq over the chunks of `g` that chunk_map does not skip (gdn_grad_sumsq_seg)."""
+    n = g.numel()
+    if chunk_map.dtype != torch.uint8 or chunk_map.numel() * 64 != n:
+        raise GdnError("segmented Adam: a chunk map of %d %s entries for %d floats" % (chunk_map.numel(), chunk_map.dtype, n))
+    nb = int(lib.gdn_grad_sumsq_workspace_bytes(n))
+    ws = workspace(nb, g.device, "gradnorm")
+    lib.gdn_grad_sumsq_seg(_p(g), n, _p(chunk_map), _p(guard), 1 if accumulate else 0, _p(ws), nb, stream())
+
+
+def ema_update_seg(ema, p, chunk_map, decay, states, guard=None):
+    """ema_update per chunk, with the warm-up weight of the chunk's own group's step count (gdn_ema_update_seg)."""
+    n = p.numel()
+    _seg_groups(n, chunk_map, None, states)
+    lib.gdn_ema_update_seg(_p(ema), _p(p), n, _p(chunk_map), float(decay), _p(states), _p(guard), stream())
+
+
 def swap_(a, b):
     """Exchange the contents of two non-overlapping dense float32 buffers in place (gdn_swap_f32)."""
     lib.gdn_swap_f32(_p(a), _p(b), a.numel(), stream())

@@ -15,6 +15,10 @@ checkpoint that is deployed.
 
 Gradient accumulation (``micro_batches``): the gradient buffer holds the SUM of that many micro-batch gradients and the
 update takes their mean through its gradient scale -- one norm, one decision, one update per group.
+
+Parameter groups and frozen parameters (``segmented``): several param groups over one arena (their own ``weight_decay``, a
+learning-rate multiplier ``lr_mult``) and parameters with ``requires_grad = False`` keep the constant launch count -- the
+kernels read a map from 64-float chunks of the arena to groups and skip what is frozen.
 """
 import contextlib
 import struct
@@ -66,6 +70,57 @@ def _rank0():
     return not (torch.distributed.is_available() and torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
 
 
+_CHUNK = 64          # floats: engine._ALIGN, the alignment of every arena slice
+_SKIP = 0xFF         # chunk map entry: a frozen parameter, padding after the last parameter
+_STATE_BYTES = 32    # sizeof(AdamDevState): the 28 bytes of _STEP_FMT and 4 of tail padding
+
+
+def _lr(group):
+    """The learning rate the kernels see: lr * lr_mult in double (they round it to float32 once)."""
+    return float(group["lr"]) * float(group.get("lr_mult", 1.0))
+
+
+class _Plan:
+    """How a segmented optimizer runs one arena.
+
+    key      per item of the arena the index of its param group in optimizer.param_groups, -1 for a frozen parameter
+             (requires_grad False): what the plan was built from, and what makes it stale
+    groups   indices of the param groups with a live parameter here, in order of first appearance; a chunk map entry k
+             means groups[k]
+    map      uint8[numel / 64] on the device: the group of every 64-float chunk, or 0xFF (skip)
+    hyper    float32[G, 6] on the device and `hyper_host`, what the host last wrote there
+    states   uint8[G * 32] on the device, one step state per group; None while the live parameters' update counts differ
+             (an odd load_state_dict): such an arena runs per tensor
+    k_of     id(param) -> its chunk map entry, live parameters only"""
+
+    def __init__(self, items, numel, key, device):
+        self.key = tuple(key)
+        self.groups = []
+        for gi in self.key:
+            if gi >= 0 and gi not in self.groups:
+                self.groups.append(gi)
+        if not 1 <= len(self.groups) <= 254:
+            raise GdnError("segmented Adam: %d param groups with trainable parameters in one arena; the chunk map holds "
+                           "1 to 254" % len(self.groups))
+        cmap = bytearray([_SKIP]) * (numel // _CHUNK)
+        self.k_of = {}
+        for (p, o, n, _), gi in zip(items, self.key):
+            if o % _CHUNK or numel % _CHUNK:
+                raise GdnError("segmented Adam: an arena slice at float offset %d of %d is not %d-float aligned" % (o, numel, _CHUNK))
+            if gi >= 0:
+                k = self.k_of[id(p)] = self.groups.index(gi)
+                for c in range(o // _CHUNK, (o + n + _CHUNK - 1) // _CHUNK):
+                    cmap[c] = k
+        self.map = torch.frombuffer(cmap, dtype=torch.uint8).to(device)
+        self.hyper = torch.zeros(len(self.groups), 6, dtype=torch.float32, device=device)
+        self.hyper_host = None
+        self.states = None
+
+    def state(self, k):
+        """Group k's 28-byte step state, as the per-tensor entry points and the checkpoints take one."""
+        return self.states[_STATE_BYTES * k:_STATE_BYTES * k + struct.calcsize(_STEP_FMT)]
+
+
 class _Parked:
     """What load_state_dict() read, until the store it belongs to exists (the arena is built by the first forward, the
     stores by the first step).  Tensors in each parameter's LOGICAL layout; _Store.fill() and Adam._guard_record() take
@@ -112,6 +167,8 @@ class _Store:
     def _drop_dev(self):
         self.hyper = self.hyper_host = self.group = self.state = None
         self.pdev, self.full_dev = {}, False
+        # segmented optimizers only: the arena's _Plan, and the 'seg' entry of a loaded record until a plan takes it
+        self.plan = self.seg_rec = None
 
     @property
     def kind(self):
@@ -138,10 +195,17 @@ class _Store:
         it behind the host's back), the host's otherwise.  `memo` saves reading one step state twice."""
         memo = {} if memo is None else memo
 
-        def dev(t):
-            if id(t) not in memo:
-                memo[id(t)] = _unpack(_STEP_FMT, t)[2]
-            return memo[id(t)]
+        def dev(t, key=None):
+            key = id(t) if key is None else key
+            if key not in memo:
+                memo[key] = _unpack(_STEP_FMT, t)[2]
+            return memo[key]
+        if self.plan is not None and self.plan.states is not None:
+            if id(p) in self.pdev:
+                return dev(self.pdev[id(p)])
+            k = self.plan.k_of.get(id(p))
+            if k is not None:
+                return dev(self.plan.state(k), (id(self.plan), k))
         if self.state is not None:
             if self.pstep is None:
                 return dev(self.state)
@@ -154,18 +218,26 @@ class _Store:
     def record(self, index):
         """The store's entry of state_dict()['gdn']['stores']; `index`: id(param) -> its number in the param groups."""
         ids = [id(p) for p, _, _, _ in self.items]
-        return {"kind": self.kind, "params": [index[i] for i in ids], "step": int(self.step),
-                "pstep": None if self.pstep is None else [int(self.pstep[i]) for i in ids],
-                "full_dev": bool(self.full_dev),
-                "state": None if self.state is None else self.state.detach().cpu().clone(),
-                "pdev": {index[i]: self.pdev[i].detach().cpu().clone() for i in ids if i in self.pdev}}
+        rec = {"kind": self.kind, "params": [index[i] for i in ids], "step": int(self.step),
+               "pstep": None if self.pstep is None else [int(self.pstep[i]) for i in ids],
+               "full_dev": bool(self.full_dev),
+               "state": None if self.state is None else self.state.detach().cpu().clone(),
+               "pdev": {index[i]: self.pdev[i].detach().cpu().clone() for i in ids if i in self.pdev}}
+        if self.plan is not None:
+            # a segmented optimizer's group states: what the plan was built from, and the device's own bytes
+            rec["seg"] = {"key": list(self.plan.key),
+                          "states": None if self.plan.states is None else self.plan.states.detach().cpu().clone()}
+        elif self.seg_rec is not None:
+            rec["seg"] = self.seg_rec
+        return rec
 
     def take_record(self, rec, capturable):
         """Host counts and -- capturable -- the device step state from a record() whose indices are ids.  False: no usable
         record (a torch checkpoint, or device counts saved by a capturable optimizer and read by a host-side one), the
         counts come from 'step'."""
         self._drop_dev()
-        if rec is None or (rec.get("state") is not None and not capturable):
+        seg = None if rec is None else rec.get("seg")
+        if rec is None or ((rec.get("state") is not None or (seg or {}).get("states") is not None) and not capturable):
             return False
         self.step = int(rec["step"])
         if self.arena is not None and rec["pstep"] is not None:
@@ -177,6 +249,10 @@ class _Store:
             self.full_dev = bool(rec["full_dev"])
             if rec["pstep"] is not None:
                 self.pdev = {pid: t.to(device=self.device, copy=True) for pid, t in rec["pdev"].items()}
+        if seg is not None:
+            self.seg_rec = seg
+            self.pdev = {pid: t.to(device=self.device, copy=True) for pid, t in rec["pdev"].items()}
+            self.full_dev = bool(rec["full_dev"])
         return True
 
     def fill(self, parked, capturable, averaged, reset=False):
@@ -259,10 +335,23 @@ class Adam(torch.optim.Optimizer):
     UPDATE: one norm over the mean gradient, one decision, one count, one average update per group.  A NaN or an Inf in any
     micro-batch's gradient stays in the sum, so with skip_nonfinite the WHOLE group's update is skipped.  It describes the
     step being taken, not the run: state_dict() does not carry it.  Like every hyper-parameter of the capturable path it is
-    pushed to the device when it changes, which is refused inside a graph capture."""
+    pushed to the device when it changes, which is refused inside a graph capture.
+
+    segmented: an arena shared by several param groups, or holding parameters with requires_grad = False, is updated by the
+    chunk-mapped kernels (gdn_adam_step_seg, gdn_grad_sumsq_seg, gdn_ema_update_seg) in the same number of launches as an
+    arena one group covers -- without it such an arena takes one launch per tensor.  Every parameter of the arena must be in
+    a param group; freezing is requires_grad = False.  Implies capturable=True (one device step state per group).  The plan
+    of an arena -- chunk map, group table, step states -- follows (param group, requires_grad) of its parameters and is
+    rebuilt when they change, which is refused inside a graph capture.  A step in which a trainable parameter has no
+    gradient, or whose parameters have taken different numbers of updates, runs per tensor, as the one-launch path hands
+    over.  Each result is bit-identical to the per-tensor update of the same slice with the same group's records.
+
+    A param group may carry 'lr_mult' (default 1; never written into the defaults, so a state_dict() without it is what it
+    was): the kernels see lr * lr_mult, in double, rounded to float32 once -- a schedule that writes group['lr'] leaves the
+    multipliers alone."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, segmented=False):
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be positive (None: no clipping), got %r" % (max_grad_norm,))
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
@@ -278,7 +367,11 @@ class Adam(torch.optim.Optimizer):
         self.skip_nonfinite = bool(skip_nonfinite)
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self.ema_decay = None if ema_decay is None else float(ema_decay)
-        self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None
+        self.segmented = bool(segmented)
+        self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None or self.segmented
+        for g in self.param_groups:
+            if not float(g.get("lr_mult", 1.0)) >= 0.0:
+                raise ValueError("lr_mult must not be negative, got %r" % (g["lr_mult"],))
         # guarded: step() gathers its launches in _work, then runs the norm pass, the decision and the updates; _guard is
         # the device record (made by the first step)
         self._work, self._guard = None, None
@@ -302,14 +395,27 @@ class Adam(torch.optim.Optimizer):
         for st in self._stores.values():
             if st.hyper is not None:
                 self._push_hyper(st, st.group)
+            if st.plan is not None:
+                self._push_plan_hyper(st.plan)
+
+    def _hyper_vals(self, group):
+        return (_lr(group), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
+                float(group["weight_decay"]), self._scale())
 
     def _push_hyper(self, st, group):
-        vals = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
-                float(group["weight_decay"]), self._scale())
+        vals = self._hyper_vals(group)
         if st.hyper_host != vals:
             _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
             st.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
             st.hyper_host = vals
+
+    def _push_plan_hyper(self, plan):
+        """The group table of a plan: one row per group, every row with the optimizer's one gradient scale."""
+        vals = tuple(self._hyper_vals(self.param_groups[gi]) for gi in plan.groups)
+        if plan.hyper_host != vals:
+            _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
+            plan.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+            plan.hyper_host = vals
 
     def _arena_groups(self, group):
         """Split a param group into (arena, covers_whole_arena) and stragglers."""
@@ -345,13 +451,23 @@ class Adam(torch.optim.Optimizer):
             count, state = st.pstep[id(p)], st.pdev.get(id(p))
         if not self.capturable:
             b1, b2 = group["betas"]
-            ops.adam_step(w, grad, m, v, group["lr"], b1, b2, group["eps"], group["weight_decay"], count, self._scale())
-        elif self._work is not None:
-            self._work.append((w, grad, m, v, st.hyper, state, ema))
+            ops.adam_step(w, grad, m, v, _lr(group), b1, b2, group["eps"], group["weight_decay"], count, self._scale())
         else:
-            ops.adam_step_dev(w, grad, m, v, st.hyper, state)
+            self._launch(w, grad, m, v, st.hyper, state, ema)
+
+    def _launch(self, w, grad, m, v, hyper, state, ema, plan=None):
+        """One capturable update and the average's: now, or -- guarded -- gathered for _guarded_updates().  With `plan` the
+        range is a whole arena under the plan's chunk map, `hyper` its group table and `state` its table of step states."""
+        if self._work is not None:
+            self._work.append((w, grad, m, v, hyper, state, ema, plan))
+        elif plan is None:
+            ops.adam_step_dev(w, grad, m, v, hyper, state)
             if ema is not None:
                 ops.ema_update(ema, w, self.ema_decay, state)
+        else:
+            ops.adam_step_seg(w, grad, m, v, plan.map, hyper, state)
+            if ema is not None:
+                ops.ema_update_seg(ema, w, plan.map, self.ema_decay, state)
 
     def _guard_record(self, device):
         if self._guard is None:
@@ -373,9 +489,18 @@ class Adam(torch.optim.Optimizer):
         for k, w in enumerate(work):
             if w[0].device != guard.device:
                 raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (guard.device, w[0].device))
-            ops.grad_sumsq(w[1], guard, accumulate=k > 0)
+            if w[7] is None:
+                ops.grad_sumsq(w[1], guard, accumulate=k > 0)
+            else:
+                ops.grad_sumsq_seg(w[1], w[7].map, guard, accumulate=k > 0)      # frozen chunks are not read
+        # (the decision reads the gradient scale alone, which every row of a group table carries)
         ops.grad_guard_finalize(guard, work[0][4], self.max_grad_norm or 0.0, self.skip_nonfinite)
-        for pdata, grad, m, v, hyper, state, ema in work:
+        for pdata, grad, m, v, hyper, state, ema, plan in work:
+            if plan is not None:
+                ops.adam_step_seg(pdata, grad, m, v, plan.map, hyper, state, guard)
+                if ema is not None:
+                    ops.ema_update_seg(ema, pdata, plan.map, self.ema_decay, state, guard)
+                continue
             ops.adam_step_dev_guarded(pdata, grad, m, v, hyper, state, guard)
             if ema is not None:
                 ops.ema_update(ema, pdata, self.ema_decay, state, guard)      # the same skip decision
@@ -503,15 +628,134 @@ class Adam(torch.optim.Optimizer):
         self._guarded_updates()
         return loss
 
+    def _refuse_pending_carry(self, ar):
+        if getattr(ar, "carry_reduced", None) is not None:
+            # (backward, sync_gradients, backward) under data parallelism leaves the first micro-batch's
+            # REDUCED gradient aside until the next sync_gradients() adds it back; stepping now would drop it silently
+            raise GdnError("optimizer.step() with an accumulated, already all-reduced gradient pending: call "
+                           "sync_gradients() after the last backward of an accumulation")
+
+    # ---- segmented: every param group of an arena in one launch -----------------------------------------
+    def _arenas_and_loose(self):
+        """([arena], {id(param): index of its param group}, [(group, loose param)]) over all param groups: arenas in
+        order of first appearance, every parameter of an intact arena under its group's index."""
+        arenas, owner, loose, intact = [], {}, [], {}
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                ar = getattr(p, "_gdn_arena", None)
+                if ar is not None and id(ar) not in intact:
+                    intact[id(ar)] = ar.intact()
+                    if intact[id(ar)]:
+                        arenas.append(ar)
+                if ar is not None and intact[id(ar)]:
+                    owner[id(p)] = gi
+                else:
+                    loose.append((group, p))
+        return arenas, owner, loose
+
+    def _plan_key(self, ar, owner):
+        key = []
+        for p, _, _, _ in ar.items:
+            if id(p) not in owner:
+                raise GdnError("segmented Adam: a parameter of shape %s of the arena is in no param group; pass every "
+                               "parameter of the model and freeze with requires_grad = False" % (tuple(p.shape),))
+            key.append(owner[id(p)] if p.requires_grad else -1)
+        return tuple(key)
+
+    def _build_plan(self, st, key):
+        """The plan of store `st` for `key`, with step states that continue the counts the live parameters have: the bytes
+        a checkpoint brought for this very key, else a state of the previous plan's for the same param group at the same
+        count (graph replays and skipped steps are in it), else the host's powers for that count.  No states (the arena
+        runs per tensor) when the live parameters' counts differ or per-parameter states exist already."""
+        _no_capture("segmented Adam: the plan of an arena (chunk map, group table, step states) would be built inside a "
+                    "graph capture; run one eager step with the same param groups and requires_grad flags first")
+        plan = _Plan(st.items, st.arena.numel, key, st.device)
+        old, saved, st.seg_rec = st.plan, st.seg_rec, None
+        memo = {}
+        counts = {st.count(p, memo) for p, _, _, _ in st.items if id(p) in plan.k_of}
+        if len(counts) == 1 and not st.pdev:
+            t = counts.pop()
+            if saved is not None and tuple(saved["key"]) == plan.key and saved["states"] is not None:
+                plan.states = saved["states"].to(device=st.device, copy=True)        # the device's own bytes, verbatim
+            else:
+                rows = []
+                for gi in plan.groups:
+                    row = None
+                    if old is not None and old.states is not None and gi in old.groups:
+                        k0 = old.groups.index(gi)
+                        if _unpack(_STEP_FMT, old.state(k0))[2] == t:     # (a group nobody was left in keeps an older count)
+                            row = old.states[_STATE_BYTES * k0:_STATE_BYTES * (k0 + 1)].clone()
+                    if row is None:
+                        fresh = _step_state(self.param_groups[gi], t, st.device)
+                        row = torch.cat([fresh, torch.zeros(_STATE_BYTES - fresh.numel(), dtype=torch.uint8, device=st.device)])
+                    rows.append(row)
+                plan.states = torch.cat(rows)
+        st.plan = plan
+        return plan
+
+    def _step_arena_segmented(self, ar, owner):
+        """This step's update of one arena of a segmented optimizer."""
+        key = self._plan_key(ar, owner)
+        live = [item for item, gi in zip(ar.items, key) if gi >= 0]
+        have = sum(item[0].grad is not None for item in live)
+        if have == 0:
+            return                    # nothing trainable ran backward for this model: skip it, like torch.optim.Adam
+        st = self._stores.get(id(ar))
+        if st is None:
+            st = self._stores[id(ar)] = self._new_store(ar.items, ar)
+        if st.pstep is None:          # a segmented store counts per parameter: a frozen one stays where it is
+            st.pstep = {id(p): st.step for p, _, _, _ in st.items}
+        plan = st.plan if st.plan is not None and st.plan.key == key else self._build_plan(st, key)
+        self._push_plan_hyper(plan)
+        if plan.states is not None and not st.pdev and have == len(live):
+            for p, _, _, _ in live:
+                st.pstep[id(p)] += 1
+            st.step = max(st.pstep.values())
+            st.full_dev = True
+            self._launch(st.weights, ar.grad, st.m, st.v, plan.hyper, plan.states, st.ema, plan)
+        else:
+            self._step_partial_segmented(st, plan, live)
+        st.touch()
+
+    def _step_partial_segmented(self, st, plan, live):
+        """_step_partial for a segmented store: per-tensor updates with each parameter's own group's row of the table,
+        each parameter's device step state a stream-ordered copy of its group's when the segmented launches drove it."""
+        ar = st.arena
+        for item in live:
+            p, o, n, _ = item
+            if p.grad is None:
+                continue
+            k = plan.k_of[id(p)]
+            gslice = ar.grad[o:o + n]
+            if p.grad.data_ptr() != gslice.data_ptr():
+                gslice = torch.empty_like(p, memory_format=torch.preserve_format).copy_(p.grad)
+            st.pstep[id(p)] += 1
+            if id(p) not in st.pdev:
+                if plan.states is not None:
+                    _no_capture("capturable Adam: a per-parameter step counter would be created inside a graph capture "
+                                "(every replay would reset it); run one eager step with this gradient coverage first")
+                    st.pdev[id(p)] = plan.state(k).clone()            # the group's device counter so far (no host read)
+                else:
+                    st.pdev[id(p)] = _step_state(self.param_groups[plan.groups[k]], st.pstep[id(p)] - 1, st.device)
+            self._launch(st.weights[o:o + n], gslice, st.m[o:o + n], st.v[o:o + n], plan.hyper[k], st.pdev[id(p)],
+                         None if st.ema is None else st.ema[o:o + n])
+        st.step = max(st.pstep.values())
+
+    def _step_groups_segmented(self):
+        arenas, owner, loose = self._arenas_and_loose()
+        for ar in arenas:
+            self._refuse_pending_carry(ar)
+            self._step_arena_segmented(ar, owner)
+        for group, p in loose:
+            self._step_store(group, [(p, 0, p.numel(), None)])
+
     def _step_groups(self):
+        if self.segmented:
+            return self._step_groups_segmented()
         for group in self.param_groups:
             arenas, loose = self._arena_groups(group)
             for ar, ps in arenas.values():
-                if getattr(ar, "carry_reduced", None) is not None:
-                    # (backward, sync_gradients, backward) under data parallelism leaves the first micro-batch's
-                    # REDUCED gradient aside until the next sync_gradients() adds it back; stepping now would drop it silently
-                    raise GdnError("optimizer.step() with an accumulated, already all-reduced gradient pending: call "
-                                   "sync_gradients() after the last backward of an accumulation")
+                self._refuse_pending_carry(ar)
                 if len(ps) != len(ar.items):
                     loose.extend(ps)      # partial coverage: fall back to per-tensor launches
                 else:
@@ -580,6 +824,12 @@ class Adam(torch.optim.Optimizer):
         """Every store that holds the state of this optimizer's parameters as they are grouped and laid out now, parameters
         in param_groups order within a store."""
         out = []
+        if self.segmented:
+            arenas, owner, loose = self._arenas_and_loose()
+            for ar in arenas:
+                if id(ar) in self._stores and all(id(p) in owner for p, _, _, _ in ar.items):
+                    out.append(self._stores[id(ar)])
+            return out + [self._stores[id(p)] for _, p in loose if id(p) in self._stores]
         for group in self.param_groups:
             arenas, loose = self._arena_groups(group)
             for ar, ps in arenas.values():
@@ -613,7 +863,10 @@ class Adam(torch.optim.Optimizer):
         state, recs, memo = {}, [], {}
         for st in self._live_stores():
             for item in st.items:
-                state[index[id(item[0])]] = entry(st.count(item[0], memo), st.view(st.m, item), st.view(st.v, item))
+                count = st.count(item[0], memo)
+                if count == 0 and self.segmented and st.arena is not None:
+                    continue          # a parameter that never stepped (frozen from the start) has no entry, as in torch
+                state[index[id(item[0])]] = entry(count, st.view(st.m, item), st.view(st.v, item))
             recs.append(st.record(index))
         # loaded, but no step since: hand back what was loaded
         for pid, s in self._parked.moments.items():

@@ -1,7 +1,7 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
---graph_warmup, --accum_steps, --freeze_bn).
+--graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -27,6 +27,29 @@ def _positive_int(text):
     if v < 1:
         raise argparse.ArgumentTypeError("%r is not a positive integer" % (text,))
     return v
+
+
+def freeze_specs(text):
+    """--freeze: 'SPEC[,SPEC...]' -> [SPEC, ...] (encoder, decoder or fnmatch patterns on parameter names)."""
+    specs = [s.strip() for s in text.split(",")]
+    if not text.strip() or not all(specs):
+        raise argparse.ArgumentTypeError("%r is not a comma-separated list of SPECs (encoder, decoder or a name pattern)" % (text,))
+    return specs
+
+
+def lr_mults(text):
+    """--lr_mult: 'SPEC=M[,SPEC=M...]' -> [(SPEC, M), ...] in the order given (later entries win), M >= 0."""
+    out = []
+    for entry in text.split(","):
+        spec, sep, mult = entry.rpartition("=")
+        try:
+            m = float(mult)
+        except ValueError:
+            m = -1.0
+        if not sep or not spec.strip() or not m >= 0.0 or m == float("inf"):
+            raise argparse.ArgumentTypeError("%r is not SPEC=M with a multiplier M >= 0" % (entry,))
+        out.append((spec.strip(), m))
+    return out
 
 
 def build_parser():
@@ -131,6 +154,20 @@ def build_parser():
                         'normalisation layer of the trained network stays in eval mode, normalises by its running mean / '
                         'variance and never updates them, while the conv weights and the affine gamma / beta train; the flag is '
                         'not stored in train_state.pt, a resumed run repeats it')
+    p.add_argument('--freeze', type=freeze_specs, default=[], metavar='SPEC[,SPEC...]',
+                   help='training (with --init_from or --resume): do not train the selected parameters.  A SPEC is encoder '
+                        '(every layer the forward runs before upconv0), decoder (the rest) or an fnmatch pattern on parameter '
+                        'names (state_dict keys without module.).  The fused Adam skips them in its one launch and the backward '
+                        'does no work below the lowest trainable layer.  Normalisation layers keep their mode, as in torch: '
+                        'add --freeze_bn to hold their running statistics.  Not stored in train_state.pt, a resumed run '
+                        'repeats it')
+    p.add_argument('--lr_mult', type=lr_mults, default=[], metavar='SPEC=M[,SPEC=M...]',
+                   help='training: the selected parameters (SPEC as for --freeze) train at M x the learning rate, M >= 0; '
+                        'later entries win, parameters no entry selects keep 1.  The schedule decays --lr, the multipliers '
+                        'stay.  Not stored in train_state.pt, a resumed run repeats it')
+    p.add_argument('--no_decay_norm', action='store_true',
+                   help='training: every 1-D parameter (BatchNorm / InstanceNorm gamma, beta) takes weight decay 0 instead of '
+                        'the 5e-4 the reference applies to it too.  Not stored in train_state.pt, a resumed run repeats it')
     return p
 
 

@@ -777,6 +777,32 @@ int gdn_swap_f32(float* a, float* b, int64_t n, void* stream);
  * (a missing symbol), never silently at the first accumulating backward. */
 int gdn_grad_accumulate(float* acc, const float* g, int64_t n, void* stream);
 
+/* Segmented forms of the capturable update, the gradient norm and the weight average (no reference counterpart; DESIGN.md
+ * 3.8): ONE launch over an arena whose parameters belong to several parameter groups, some of them frozen.  Arena slices
+ * are 64-float aligned, so a 64-float chunk belongs to one parameter or to padding:
+ *   map     uint8[n / 64] in device memory: the group 0 .. G-1 of each chunk, or 0xFF for a chunk to skip (a frozen
+ *           parameter, padding after the last parameter).  The padding floats inside a live parameter's last chunk are
+ *           updated like its elements (they are zero and stay zero).  The CONTENTS of the map are the caller's to check.
+ *   hyper   float[G][6], per group the fields of gdn_adam_step_dev's hyper;
+ *   states  G x 32 bytes, per group the step state of gdn_adam_step_dev (8-byte aligned);
+ *   guard   the record of gdn_grad_guard_finalize, or NULL (gdn_adam_step_seg, gdn_ema_update_seg).
+ * gdn_adam_step_seg: a one-block launch advances each of the G step states as gdn_adam_step_dev advances its own (none of
+ *   them when guard->skip != 0), then ONE launch updates every element of a chunk mapped to group k with hyper[k], states[k]
+ *   and the gradient scale hyper[k][5] (times guard->coef): bit-identical to gdn_adam_step_dev[_guarded] on that slice with
+ *   those records.  p, g, m, v of a skipped chunk are neither read nor written.
+ * gdn_grad_sumsq_seg: gdn_grad_sumsq over the chunks that are not skipped (a NaN in a skipped chunk does not reach the sum);
+ *   same workspace, a grid that is a function of n alone, double partial sums in a fixed order, no floating-point atomics.
+ * gdn_ema_update_seg: gdn_ema_update with the warm-up weight of the chunk's own group's step count; skipped chunks untouched.
+ * All move 16 bytes per lane; the 16 lanes of a chunk read its map byte once.  A NULL pointer (guard excepted), n <= 0,
+ * n % 64 != 0, G outside 1 .. 254 or a buffer base that is not 16-byte aligned return GDN_ERR_BAD_ARG before any launch.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+int gdn_adam_step_seg(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* map, int32_t G,
+                      const float* hyper, void* states, const void* guard, void* stream);
+int gdn_grad_sumsq_seg(const float* g, int64_t n, const uint8_t* map, void* guard, int32_t accumulate, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int gdn_ema_update_seg(float* ema, const float* p, int64_t n, const uint8_t* map, double decay, const void* states,
+                       const void* guard, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
