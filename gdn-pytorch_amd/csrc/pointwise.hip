@@ -851,6 +851,29 @@ __global__ __launch_bounds__(256) void ema_update_seg_kernel(f32x4* __restrict__
     }
 }
 
+// ---- learning-rate schedule on the device (include/gdn_hip.h): lane k turns the update count of group k into the rate of the
+// update about to run, hyper[k][0] = (float)(base_lr[k] * s(u)).  Contraction is off for the whole function and the division is
+// the IEEE one, so warm-up, the linear decay and the final product are the host's plain double arithmetic bit for bit; only
+// cos() is the device library's.  Ordinary loads and stores, no LDS, no atomics; lanes >= G do nothing.
+__global__ __launch_bounds__(256) void lr_schedule_kernel(float* __restrict__ hyper, const double* __restrict__ base_lr,
+                                                          const AdamDevState* __restrict__ states, int G, int kind, int warmup,
+                                                          int total, double floor) {
+#pragma clang fp contract(off)
+    const int k = (int)threadIdx.x;
+    if (k >= G) return;
+    const double u = (double)states[k].step;
+    double s = 1.0;
+    if (u < (double)warmup) {
+        s = __ddiv_rn(u + 1.0, (double)warmup);
+    } else if (kind != 0) {
+        const int span = total - warmup > 1 ? total - warmup : 1;
+        const double x = fmin(1.0, __ddiv_rn(u - (double)warmup, (double)span));
+        const double shape = kind == 1 ? 1.0 - x : 0.5 * (1.0 + cos(3.141592653589793 * x));
+        s = floor + (1.0 - floor) * shape;
+    }
+    hyper[6 * k] = (float)(base_lr[k] * s);
+}
+
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
@@ -1454,6 +1477,17 @@ extern "C" int gdn_ema_update_seg(float* ema, const float* p, int64_t n, const u
     if (((uintptr_t)states & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
     hipLaunchKernelGGL(ema_update_seg_kernel, dim3(stream_rw_blocks(n, true)), dim3(256), 0, ST(stream), (f32x4*)ema, (const f32x4*)p,
                        n / 4, map, decay, (const AdamDevState*)states, (const AdamGuard*)guard);
+    return gdn_launch_status();
+}
+
+extern "C" int gdn_lr_schedule(float* hyper, const double* base_lr, const void* states, int32_t G, int32_t kind, int32_t warmup,
+                               int32_t total, double floor, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!hyper || !base_lr || !states || G < 1 || G > 254 || kind < 0 || kind > 2 || warmup < 0 || total < 1) return GDN_ERR_BAD_ARG;
+    if (!(floor >= 0.0 && floor <= 1.0)) return GDN_ERR_BAD_ARG;          // (a NaN fails both comparisons)
+    if (((uintptr_t)hyper & 3) || ((uintptr_t)base_lr & 7) || ((uintptr_t)states & 7)) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(G <= 64 ? 64 : 256), 0, ST(stream), hyper, base_lr,
+                       (const AdamDevState*)states, (int)G, (int)kind, (int)warmup, (int)total, floor);
     return gdn_launch_status();
 }
 

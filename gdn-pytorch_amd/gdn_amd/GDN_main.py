@@ -49,6 +49,12 @@ trains parts of it at a multiple of the learning rate and ``--no_decay_norm`` ta
 (DESIGN.md 3.8): the param groups they build all run in the fused Adam's one launch (``optim.Adam(segmented=True)``), and the
 backward does no work below the lowest trainable layer.  ``--freeze`` needs ``--init_from`` or ``--resume``; none of the three
 is stored in ``train_state.pt``: a resumed run repeats them.
+``--warmup_steps W`` / ``--lr_schedule {reference,constant,linear,cosine}`` / ``--lr_floor F`` set the rate of every update on
+the device: one small launch in front of the fused Adam turns the device's own count of applied updates into
+``lr x lr_mult x s(u)`` -- a warm-up over W updates, then the reference's decay as ever (``reference``), no decay, or a linear /
+cosine decay to ``F x lr`` at the run's last update (``epochs x ceil(epoch_size / accum_steps)``).  Nothing is written from the
+host per step, so ``--graph`` replays it; ``train_state.pt`` stores the schedule and a resumed run must repeat it.
+``--lr_schedule reference`` without a warm-up is the run without these flags.
 """
 import contextlib
 import io
@@ -63,8 +69,8 @@ from . import utils as U
 from .AE_model_unet import AutoEncoder, AutoEncoder_2, AutoEncoder_DtoD
 from .optim import Adam
 from .synthetic import SyntheticLoader
-from .trainer import (load_checkpoint, load_training_state, read_training_state, train_AE_DtoD, train_AE_RtoD, validate,
-                      validate_NYU)
+from .trainer import (load_checkpoint, load_training_state, lr_schedule_of, read_training_state, train_AE_DtoD, train_AE_RtoD,
+                      validate, validate_NYU)
 
 TEST_MODES = ('DtoD_test', 'RtoD_test')
 
@@ -85,6 +91,10 @@ def _make_optimizer(model, args):
     if _partial(args):
         # --freeze / --lr_mult / --no_decay_norm: param groups over the one arena, all of them in the fused Adam's one launch
         params, guard["segmented"] = param_groups(model, args), True
+    # --warmup_steps / --lr_schedule: the rate of every update set on the device (None: today's run, nothing is launched)
+    schedule = lr_schedule_of(args, getattr(args, "epochs", 0), getattr(args, "epoch_size", 0))
+    if schedule is not None:
+        guard["schedule"] = schedule
     return Adam(params, args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
 
 
@@ -179,6 +189,20 @@ def _check_accum(args):
     if getattr(args, "graph", False):
         raise RuntimeError("--graph with --accum_steps %d is not supported yet: a group would need captured graphs of its "
                            "first, middle and last micro-step, which is a follow-up (drop one of the two flags)" % accum)
+
+
+def _check_schedule(args):
+    """--warmup_steps / --lr_schedule / --lr_floor set the rates of a training run; checked before anything touches the GPU.
+    (Whether the warm-up fits into the run is the trainer's to say: the run's length needs the loader.)"""
+    flag = getattr(args, "lr_schedule", None) or "reference"
+    warmup, floor = int(getattr(args, "warmup_steps", 0) or 0), float(getattr(args, "lr_floor", 0.0) or 0.0)
+    if flag == "reference" and warmup == 0 and floor == 0.0:
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--warmup_steps / --lr_schedule / --lr_floor set the learning rate of a training run; --mode %s "
+                           "trains nothing" % args.mode)
+    if floor != 0.0 and flag not in ("linear", "cosine"):
+        raise RuntimeError("--lr_floor %g is where a decay ends, and --lr_schedule %s has none (linear or cosine do)" % (floor, flag))
 
 
 def _check_freeze_bn(args):
@@ -295,6 +319,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_ema(args)
     _check_graph(args)
     _check_accum(args)
+    _check_schedule(args)
     _check_freeze_bn(args)
     _check_partial(args, args.height, args.width)
     rank, local_rank, world = D.env_rank()

@@ -144,6 +144,7 @@ _SIGS = {
     "gdn_adam_step_seg": (c_int32, [_P, _P, _P, _P, _i64, _P, _i32, _P, _P, _P, _P]),
     "gdn_grad_sumsq_seg": (c_int32, [_P, _i64, _P, _P, _i32, _P, _sz, _P]),
     "gdn_ema_update_seg": (c_int32, [_P, _P, _i64, _P, c_double, _P, _P, _P]),
+    "gdn_lr_schedule": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, c_double, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),
@@ -154,7 +155,7 @@ EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --
 # a stale build would take the arguments apart differently.  (gdn_grad_accumulate joined revision 223 without a new number:
 # _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
-# and gdn_bn_frozen_bwd*, and the three gdn_*_seg entry points of the segmented Adam, for the same reason.)
+# and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam and gdn_lr_schedule, for the same reason.)
 ABI_VERSION = 223
 
 

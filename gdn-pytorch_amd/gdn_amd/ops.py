@@ -1368,6 +1368,25 @@ def ema_update_seg(ema, p, chunk_map, decay, states, guard=None):
     lib.gdn_ema_update_seg(_p(ema), _p(p), n, _p(chunk_map), float(decay), _p(states), _p(guard), stream())
 
 
+LR_SCHEDULE_KINDS = ("constant", "linear", "cosine")        # the `kind` argument of gdn_lr_schedule: 0, 1, 2
+
+
+def lr_schedule(hyper, base_lr, states, kind, warmup, total, floor):
+    """hyper[k][0] = float32(base_lr[k] * s(t_k)) for every group k, t_k the update count in group k's step state: warm-up
+    over `warmup` updates, then constant / linear / cosine decay to `floor` at update `total` (gdn_lr_schedule).  hyper
+    float32[G, 6] (or [6]), base_lr float64[G], states the 28-byte step state of a plain store (G = 1) or uint8[G * 32].
+    One launch, no sync, capturable."""
+    G = base_lr.numel()
+    if base_lr.dtype != torch.float64 or hyper.dtype != torch.float32 or hyper.numel() != 6 * G or states.dtype != torch.uint8 \
+            or states.numel() < 32 * (G - 1) + 28:
+        raise GdnError("lr_schedule: %d %s base rates beside %d %s hyper-parameters and %d bytes of step states" %
+                       (G, base_lr.dtype, hyper.numel(), hyper.dtype, states.numel()))
+    if not (hyper.is_contiguous() and base_lr.is_contiguous() and states.is_contiguous()):
+        raise GdnError("lr_schedule: hyper, base_lr and states must be dense")
+    k = LR_SCHEDULE_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    lib.gdn_lr_schedule(_p(hyper), _p(base_lr), _p(states), G, k, int(warmup), int(total), float(floor), stream())
+
+
 def swap_(a, b):
     """Exchange the contents of two non-overlapping dense float32 buffers in place (gdn_swap_f32)."""
     lib.gdn_swap_f32(_p(a), _p(b), a.numel(), stream())

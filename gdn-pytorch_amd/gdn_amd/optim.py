@@ -19,6 +19,10 @@ update takes their mean through its gradient scale -- one norm, one decision, on
 Parameter groups and frozen parameters (``segmented``): several param groups over one arena (their own ``weight_decay``, a
 learning-rate multiplier ``lr_mult``) and parameters with ``requires_grad = False`` keep the constant launch count -- the
 kernels read a map from 64-float chunks of the arena to groups and skip what is frozen.
+
+Learning-rate schedule (``schedule``): warm-up and a constant / linear / cosine decay evaluated on the device from the
+device's own update count, one small launch per arena in front of the update -- no host write per step, capturable
+(DESIGN.md 3.9).
 """
 import contextlib
 import struct
@@ -80,6 +84,28 @@ def _lr(group):
     return float(group["lr"]) * float(group.get("lr_mult", 1.0))
 
 
+def _base_rates(rates, device):
+    """double[G] on the device: what gdn_lr_schedule scales (a blocking copy, made only when a rate changes)."""
+    return torch.tensor(rates, dtype=torch.float64).to(device)
+
+
+def check_schedule(schedule):
+    """Adam(schedule=...) in its one spelling: None, or {'kind': 'constant' | 'linear' | 'cosine', 'warmup': W >= 0,
+    'total': T >= 1, 'floor': F in [0, 1]} with plain Python numbers."""
+    if schedule is None:
+        return None
+    unknown = set(schedule) - {"kind", "warmup", "total", "floor"}
+    if unknown or "kind" not in schedule:
+        raise ValueError("schedule must be a dict with the keys 'kind', 'warmup', 'total', 'floor', got %r" % (schedule,))
+    kind, warmup, total = schedule["kind"], int(schedule.get("warmup", 0)), int(schedule.get("total", 1))
+    floor = float(schedule.get("floor", 0.0))
+    if kind not in ops.LR_SCHEDULE_KINDS:
+        raise ValueError("schedule kind %r is not one of %s" % (kind, " / ".join(ops.LR_SCHEDULE_KINDS)))
+    if warmup < 0 or total < 1 or not 0.0 <= floor <= 1.0:
+        raise ValueError("schedule needs warmup >= 0, total >= 1 and a floor in [0, 1], got %r" % (schedule,))
+    return {"kind": kind, "warmup": warmup, "total": total, "floor": floor}
+
+
 class _Plan:
     """How a segmented optimizer runs one arena.
 
@@ -89,6 +115,7 @@ class _Plan:
              means groups[k]
     map      uint8[numel / 64] on the device: the group of every 64-float chunk, or 0xFF (skip)
     hyper    float32[G, 6] on the device and `hyper_host`, what the host last wrote there
+    base_lr  (Adam(schedule=...) only) float64[G] on the device, each group's lr * lr_mult, and `base_host`
     states   uint8[G * 32] on the device, one step state per group; None while the live parameters' update counts differ
              (an odd load_state_dict): such an arena runs per tensor
     k_of     id(param) -> its chunk map entry, live parameters only"""
@@ -115,6 +142,7 @@ class _Plan:
         self.hyper = torch.zeros(len(self.groups), 6, dtype=torch.float32, device=device)
         self.hyper_host = None
         self.states = None
+        self.base_lr = self.base_host = None          # a scheduled optimizer: double[G] lr * lr_mult on the device, and the host's copy
 
     def state(self, k):
         """Group k's 28-byte step state, as the per-tensor entry points and the checkpoints take one."""
@@ -166,6 +194,7 @@ class _Store:
 
     def _drop_dev(self):
         self.hyper = self.hyper_host = self.group = self.state = None
+        self.base_lr = self.base_host = None      # Adam(schedule=...): float64[1] lr * lr_mult on the device, and the host's copy
         self.pdev, self.full_dev = {}, False
         # segmented optimizers only: the arena's _Plan, and the 'seg' entry of a loaded record until a plan takes it
         self.plan = self.seg_rec = None
@@ -348,10 +377,19 @@ class Adam(torch.optim.Optimizer):
 
     A param group may carry 'lr_mult' (default 1; never written into the defaults, so a state_dict() without it is what it
     was): the kernels see lr * lr_mult, in double, rounded to float32 once -- a schedule that writes group['lr'] leaves the
-    multipliers alone."""
+    multipliers alone.
+
+    schedule ({'kind': 'constant' | 'linear' | 'cosine', 'warmup': W, 'total': T, 'floor': F}): the rate of
+    every update is set on the device from the device's own update count u (0 for the first update): lr * lr_mult * s(u),
+    s(u) = (u + 1) / W during the first W updates, then 1 (constant) or a linear / cosine decay from 1 to F at update T, F from
+    then on.  One gdn_lr_schedule launch per arena in front of the update writes it into the hyper-parameter table; the host
+    pushes nothing per step, so captured graphs replay it.  Implies capturable=True.  A skipped step does not advance u.
+    Code that writes group['lr'] (the reference's decay) still works: the base rate is pushed when it changes, outside a
+    capture.  current_lr() reads the rates the last update used.  state_dict()['gdn']['schedule'] carries the four values
+    and load_state_dict() refuses another schedule."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, segmented=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, segmented=False, schedule=None):
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be positive (None: no clipping), got %r" % (max_grad_norm,))
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
@@ -368,7 +406,9 @@ class Adam(torch.optim.Optimizer):
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.segmented = bool(segmented)
-        self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None or self.segmented
+        self.schedule = check_schedule(schedule)
+        self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None or self.segmented or \
+            self.schedule is not None
         for g in self.param_groups:
             if not float(g.get("lr_mult", 1.0)) >= 0.0:
                 raise ValueError("lr_mult must not be negative, got %r" % (g["lr_mult"],))
@@ -408,6 +448,14 @@ class Adam(torch.optim.Optimizer):
             _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
             st.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
             st.hyper_host = vals
+        if self.schedule is not None and st.base_host != (vals[0],):
+            # the rate the schedule scales, in double; hyper[0] above is what the next gdn_lr_schedule launch overwrites
+            _no_capture("optimizer learning rate changed inside a graph capture; call refresh_hyper() before it")
+            if st.base_lr is None:
+                st.base_lr = _base_rates([vals[0]], st.device)
+            else:
+                st.base_lr.copy_(torch.tensor([vals[0]], dtype=torch.float64))   # in place: captured graphs hold its address
+            st.base_host = (vals[0],)
 
     def _push_plan_hyper(self, plan):
         """The group table of a plan: one row per group, every row with the optimizer's one gradient scale."""
@@ -416,6 +464,14 @@ class Adam(torch.optim.Optimizer):
             _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
             plan.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
             plan.hyper_host = vals
+        rates = tuple(v[0] for v in vals)
+        if self.schedule is not None and plan.base_host != rates:
+            _no_capture("optimizer learning rate changed inside a graph capture; call refresh_hyper() before it")
+            if plan.base_lr is None:
+                plan.base_lr = _base_rates(rates, plan.hyper.device)
+            else:
+                plan.base_lr.copy_(torch.tensor(rates, dtype=torch.float64))     # in place: captured graphs hold its address
+            plan.base_host = rates
 
     def _arena_groups(self, group):
         """Split a param group into (arena, covers_whole_arena) and stragglers."""
@@ -453,14 +509,24 @@ class Adam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             ops.adam_step(w, grad, m, v, _lr(group), b1, b2, group["eps"], group["weight_decay"], count, self._scale())
         else:
-            self._launch(w, grad, m, v, st.hyper, state, ema)
+            self._launch(w, grad, m, v, st.hyper, state, ema, base=st.base_lr)
 
-    def _launch(self, w, grad, m, v, hyper, state, ema, plan=None):
+    def _set_rates(self, hyper, base, state):
+        """A scheduled optimizer: this update's rates from the update counts in `state`, written into `hyper` in front of
+        the update that reads them (one launch; the table's other fields stay the host's)."""
+        if self.schedule is not None:
+            s = self.schedule
+            ops.lr_schedule(hyper, base, state, s["kind"], s["warmup"], s["total"], s["floor"])
+
+    def _launch(self, w, grad, m, v, hyper, state, ema, plan=None, base=None):
         """One capturable update and the average's: now, or -- guarded -- gathered for _guarded_updates().  With `plan` the
-        range is a whole arena under the plan's chunk map, `hyper` its group table and `state` its table of step states."""
+        range is a whole arena under the plan's chunk map, `hyper` its group table and `state` its table of step states.
+        `base`: the base rates beside `hyper` that a schedule scales."""
         if self._work is not None:
-            self._work.append((w, grad, m, v, hyper, state, ema, plan))
-        elif plan is None:
+            self._work.append((w, grad, m, v, hyper, state, ema, plan, base))
+            return
+        self._set_rates(hyper, base, state)
+        if plan is None:
             ops.adam_step_dev(w, grad, m, v, hyper, state)
             if ema is not None:
                 ops.ema_update(ema, w, self.ema_decay, state)
@@ -495,7 +561,9 @@ class Adam(torch.optim.Optimizer):
                 ops.grad_sumsq_seg(w[1], w[7].map, guard, accumulate=k > 0)      # frozen chunks are not read
         # (the decision reads the gradient scale alone, which every row of a group table carries)
         ops.grad_guard_finalize(guard, work[0][4], self.max_grad_norm or 0.0, self.skip_nonfinite)
-        for pdata, grad, m, v, hyper, state, ema, plan in work:
+        for pdata, grad, m, v, hyper, state, ema, plan, base in work:
+            # (right in front of its own update: per-tensor launches of one store share a row of the table)
+            self._set_rates(hyper, base, state)
             if plan is not None:
                 ops.adam_step_seg(pdata, grad, m, v, plan.map, hyper, state, guard)
                 if ema is not None:
@@ -516,6 +584,26 @@ class Adam(torch.optim.Optimizer):
             return {"norm": 0.0, "coef": 1.0, "steps": steps, "clipped": clipped, "skipped": skipped}
         _, norm, coef, _, steps, clipped, skipped = _unpack(_GUARD_FMT, self._guard)
         return {"norm": norm, "coef": coef, "steps": steps, "clipped": clipped, "skipped": skipped}
+
+    def current_lr(self):
+        """The float32 rates the last update used, one per param group, as the kernels read them from the device table:
+        with a schedule what gdn_lr_schedule wrote, without one float32(lr * lr_mult).  None for a group no update has
+        reached yet (or whose parameters are all frozen).  A small device-to-host copy per table, i.e. a sync: for print
+        cadence, not for every step; not inside a capture."""
+        if not self.capturable:
+            raise GdnError("current_lr(): the rates of this optimizer are launch arguments, not device memory (capturable)")
+        _no_capture("optimizer current_lr() inside a graph capture")
+        out = [None] * len(self.param_groups)
+        index = {id(g): gi for gi, g in enumerate(self.param_groups)}
+        for st in self._stores.values():
+            if st.plan is not None:
+                table = st.plan.hyper[:, 0].cpu().tolist()
+                for k, gi in enumerate(st.plan.groups):
+                    if out[gi] is None:
+                        out[gi] = table[k]
+            elif st.hyper is not None and out[index[id(st.group)]] is None:
+                out[index[id(st.group)]] = float(st.hyper[0].item())
+        return out
 
     # ---- weight average ----------------------------------------------------------------------------------------------
     def _ema_views(self):
@@ -712,7 +800,7 @@ class Adam(torch.optim.Optimizer):
                 st.pstep[id(p)] += 1
             st.step = max(st.pstep.values())
             st.full_dev = True
-            self._launch(st.weights, ar.grad, st.m, st.v, plan.hyper, plan.states, st.ema, plan)
+            self._launch(st.weights, ar.grad, st.m, st.v, plan.hyper, plan.states, st.ema, plan, base=plan.base_lr)
         else:
             self._step_partial_segmented(st, plan, live)
         st.touch()
@@ -738,7 +826,8 @@ class Adam(torch.optim.Optimizer):
                 else:
                     st.pdev[id(p)] = _step_state(self.param_groups[plan.groups[k]], st.pstep[id(p)] - 1, st.device)
             self._launch(st.weights[o:o + n], gslice, st.m[o:o + n], st.v[o:o + n], plan.hyper[k], st.pdev[id(p)],
-                         None if st.ema is None else st.ema[o:o + n])
+                         None if st.ema is None else st.ema[o:o + n],
+                         base=None if plan.base_lr is None else plan.base_lr[k:k + 1])
         st.step = max(st.pstep.values())
 
     def _step_groups_segmented(self):
@@ -880,6 +969,8 @@ class Adam(torch.optim.Optimizer):
             gs = self.guard_stats()
             priv["guard"] = {"max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite,
                              "steps": gs["steps"], "clipped": gs["clipped"], "skipped": gs["skipped"]}
+        if self.schedule is not None:
+            priv["schedule"] = dict(self.schedule)
         if self.ema_decay is not None:
             # every parameter, so the averaged model can be put together from this key alone (no update yet: avg_0 = p_0)
             views = self._ema_views()
@@ -897,6 +988,12 @@ class Adam(torch.optim.Optimizer):
         before the load still holds the old device step state -- capture after loading."""
         _no_capture("optimizer load_state_dict() inside a graph capture")
         self._refuse_swapped("load_state_dict()")
+        if "gdn" in state_dict:
+            # (a torch.optim.Adam checkpoint has no such key and says nothing about a schedule)
+            theirs = check_schedule((state_dict["gdn"] or {}).get("schedule"))
+            if theirs != self.schedule:
+                raise GdnError("optimizer state written under the learning-rate schedule %r loaded into an optimizer with the "
+                               "schedule %r: the update counts it carries would mean other rates" % (theirs, self.schedule))
         groups = state_dict["param_groups"]
         mine = [len(g["params"]) for g in self.param_groups]
         theirs = [len(g["params"]) for g in groups]

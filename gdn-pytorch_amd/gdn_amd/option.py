@@ -1,7 +1,8 @@
 """Command-line flags: every flag name and default of the reference's option.py:5-48,
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
---graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm).
+--graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm, --warmup_steps, --lr_schedule,
+--lr_floor).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -26,6 +27,20 @@ def _positive_int(text):
     v = int(text)
     if v < 1:
         raise argparse.ArgumentTypeError("%r is not a positive integer" % (text,))
+    return v
+
+
+def _non_negative_int(text):
+    v = int(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError("%r is not a non-negative integer" % (text,))
+    return v
+
+
+def _unit_float(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError("%r is not a number in [0, 1]" % (text,))
     return v
 
 
@@ -168,6 +183,18 @@ def build_parser():
     p.add_argument('--no_decay_norm', action='store_true',
                    help='training: every 1-D parameter (BatchNorm / InstanceNorm gamma, beta) takes weight decay 0 instead of '
                         'the 5e-4 the reference applies to it too.  Not stored in train_state.pt, a resumed run repeats it')
+    p.add_argument('--warmup_steps', type=_non_negative_int, default=0, metavar='W',
+                   help='training: the first W Adam updates run at (u + 1) / W of the learning rate (u = 0, 1, ... counts '
+                        'APPLIED updates: a step --skip_nonfinite drops does not advance it), every --lr_mult group at its own '
+                        'multiple.  Evaluated on the device in front of the fused Adam, so --graph replays it; 0 = off')
+    p.add_argument('--lr_schedule', default='reference', choices=['reference', 'constant', 'linear', 'cosine'],
+                   help='training: what follows the warm-up.  reference: the hand-rolled decay of the reference (after epoch 2 / '
+                        '5, every 1900 / 2200 batches), as ever.  constant / linear / cosine: that decay is off and the device '
+                        'holds --lr, or takes it from --lr to --lr_floor x --lr over the run, linearly or along half a cosine; '
+                        'the run\'s length is counted in updates, epochs x ceil(epoch_size / accum_steps).  Stored in '
+                        'train_state.pt: a resumed run must repeat it')
+    p.add_argument('--lr_floor', type=_unit_float, default=0.0, metavar='F',
+                   help='with --lr_schedule linear / cosine: the share of --lr the decay ends at, in [0, 1]')
     return p
 
 

@@ -91,7 +91,8 @@ def training_state(model, optimizer, loader, progress):
     (optim.Adam: real moments and the device step state), the loader's state of every rank, the torch RNG state and
     `progress`: 'epoch', 'i' (the batch of that epoch the last completed step used; -1: the epoch is about to start),
     'lr', 'model_num', 'seen', 'step' (iterations over the whole run), and 'accum_steps' where the run accumulates
-    gradients (--accum_steps > 1; a run without it writes the file it always wrote).  The guide network of RtoD is frozen and not part
+    gradients (--accum_steps > 1; a run without it writes the file it always wrote) and 'schedule' where the device sets the
+    learning rate (--warmup_steps / --lr_schedule: the flag and the optimizer's four values).  The guide network of RtoD is frozen and not part
     of it.  Collective under data parallelism: every rank calls it, the loader states are gathered to rank 0, which gets
     the dict; the other ranks get None (weights and moments are identical on all ranks)."""
     i = int(progress.get("i", -1))
@@ -113,6 +114,8 @@ def training_state(model, optimizer, loader, progress):
         state[k] = float(v) if k == "lr" else int(v)
     if int(progress.get("accum_steps", 1)) > 1:
         state["accum_steps"] = int(progress["accum_steps"])
+    if progress.get("schedule") is not None:
+        state["schedule"] = dict(progress["schedule"])
     return state
 
 
@@ -123,6 +126,11 @@ def load_training_state(state, model, optimizer, loader):
     if saved != world:
         raise U.GdnError("training state was saved by %d rank(s), this run has %d: the loaders' shards and streams do not "
                          "carry over" % (saved, world))
+    theirs, mine = state.get("schedule"), getattr(optimizer, "schedule", None)
+    if (None if theirs is None else {k: v for k, v in theirs.items() if k != "lr_schedule"}) != mine:
+        raise U.GdnError("the training state was written under the learning-rate schedule %r, this run has %r "
+                         "(--lr_schedule / --warmup_steps / --lr_floor / the run's length): the update counts it carries would "
+                         "mean other rates" % (theirs, mine))
     model.load_state_dict(state["model"])
     ar = getattr(model, "_gdn_param_arena", None)
     if ar is not None:
@@ -139,6 +147,8 @@ def load_training_state(state, model, optimizer, loader):
     progress = {k: state[k] for k in PROGRESS_KEYS}
     if "accum_steps" in state:
         progress["accum_steps"] = int(state["accum_steps"])
+    if "schedule" in state:
+        progress["schedule"] = dict(state["schedule"])
     return progress
 
 
@@ -177,6 +187,7 @@ class _StateSaver:
 
     def __init__(self, args, save_dir, model, optimizer, loader):
         self.accum = _accum_steps(args)
+        self.schedule = None               # the state file's 'schedule' entry: set by the loop where the run has one
         self.on_checkpoint = bool(getattr(args, "save_state", False))
         self.every = max(0, int(getattr(args, "save_state_every", 0) or 0))
         self.path = save_dir + '/' + STATE_FILE
@@ -205,6 +216,8 @@ class _StateSaver:
         progress = {"epoch": epoch, "i": i, "lr": lr, "model_num": model_num, "seen": seen, "step": step}
         if self.accum > 1:
             progress["accum_steps"] = self.accum
+        if self.schedule is not None:
+            progress["schedule"] = self.schedule
         save_training_state(self.path, *self.objs, progress)
         self.pending = False
 
@@ -226,6 +239,55 @@ def _check_accum(args, progress):
         raise U.GdnError("the training state was written with --accum_steps %d, this run has --accum_steps %d: the resumed "
                          "run would group its batches differently" % (int(progress.get("accum_steps", 1)), accum))
     return accum
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --warmup_steps / --lr_schedule / --lr_floor: the rate of every update set on the device
+def schedule_total(args, n_epochs, epoch_size):
+    """The run's length in Adam UPDATES: n_epochs x ceil(epoch_size / accum_steps) -- the groups of --accum_steps never cross
+    an epoch's end, so the one an epoch ends with may be shorter and still is one update."""
+    accum = _accum_steps(args)
+    return int(n_epochs) * ((int(epoch_size) + accum - 1) // accum)
+
+
+def lr_schedule_of(args, n_epochs, epoch_size):
+    """optim.Adam's `schedule` for this command line, None where the run has none (--lr_schedule reference without
+    --warmup_steps: today's run).  reference with a warm-up is the device's 'constant' kind under the reference's decay,
+    which keeps writing group['lr']; constant / linear / cosine own the rate.  A function of the command line alone, so a
+    resumed run computes the same schedule."""
+    flag = getattr(args, "lr_schedule", None) or "reference"
+    warmup = int(getattr(args, "warmup_steps", 0) or 0)
+    if flag == "reference" and warmup == 0:
+        return None
+    total = schedule_total(args, n_epochs, epoch_size)
+    decays = flag in ("linear", "cosine")
+    if total < 1:
+        raise U.GdnError("--lr_schedule %s over a run of %d updates" % (flag, total))
+    if decays and warmup >= total:
+        raise U.GdnError("--warmup_steps %d leaves nothing of the %d updates of this run (epochs x ceil(epoch_size / "
+                         "accum_steps)) to the %s decay" % (warmup, total, flag))
+    return {"kind": "constant" if flag == "reference" else flag, "warmup": warmup, "total": total,
+            "floor": float(getattr(args, "lr_floor", 0.0) or 0.0) if decays else 0.0}
+
+
+def _check_schedule(args, schedule, optimizer, progress):
+    """The loop's schedule against the optimizer it was handed and the training state it resumes; raises before any step.
+    Returns the state file's 'schedule' entry (None: the run has none and writes the file it always wrote)."""
+    have = getattr(optimizer, "schedule", None)
+    if have != schedule:
+        raise U.GdnError("this run's learning-rate schedule is %r, its optimizer was built with %r: build it with "
+                         "optim.Adam(schedule=trainer.lr_schedule_of(args, epochs, epoch_size))" % (schedule, have))
+    entry = None if schedule is None else dict(schedule, lr_schedule=getattr(args, "lr_schedule", None) or "reference")
+    if progress is not None and progress.get("schedule") != entry:
+        raise U.GdnError("the training state was written under the learning-rate schedule %r, this run has %r: the resumed "
+                         "run would take other rates" % (progress.get("schedule"), entry))
+    return entry
+
+
+def _print_lr(optimizer):
+    """The rates the last update used, one per param group (a device read: only where the loops print anyway)."""
+    if getattr(optimizer, "schedule", None) is not None and _is_main():
+        print("lr: " + "  ".join("-" if r is None else "%.6e" % r for r in optimizer.current_lr()))
 
 
 def _start(progress, lr):
@@ -454,6 +516,9 @@ def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_ep
     epoch0, first, lr, model_num, seen, gstep = _start(progress, lr)
     saver = _StateSaver(args, save_dir, model, optimizer, loader)
     accum = _check_accum(args, progress)
+    # the device sets the rate; under constant / linear / cosine the reference's decay is off
+    saver.schedule = _check_schedule(args, lr_schedule_of(args, n_epochs, epoch_size), optimizer, progress)
+    host_decay = (getattr(args, "lr_schedule", None) or "reference") == "reference"
     if accum > 1:
         stepper = _GroupedStep(fwd_bwd, model, optimizer, accum, epoch_size, saver)
     elif getattr(args, "graph", False):
@@ -482,12 +547,13 @@ def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_ep
             saver.stepped(gstep, stepper.held)
             if i >= epoch_size - 1:
                 break
-            if epoch > decay_after and (i + 1) % decay_every == 0:
+            if host_decay and epoch > decay_after and (i + 1) % decay_every == 0:
                 lr = _decay_lr(optimizer, lr, decay_div)
             if (i + 1) % cadence.print_every == 0 and _is_main():
                 print("epoch: %d,  %d/%d" % (epoch + 1, i + 1, epoch_size))
                 print(cadence.progress_line % (tuple(t.item() for t in terms) + (seen / (time.time() - t0),)))
                 _print_guard_progress(optimizer)
+                _print_lr(optimizer)
             if (i + 1) % cadence.checkpoint_every == 0:
                 checkpoint()
             if saver.write_now(i):

@@ -803,6 +803,26 @@ int gdn_grad_sumsq_seg(const float* g, int64_t n, const uint8_t* map, void* guar
 int gdn_ema_update_seg(float* ema, const float* p, int64_t n, const uint8_t* map, double decay, const void* states,
                        const void* guard, void* stream);
 
+/* Learning-rate schedule on the device (no reference counterpart): turns each group's update count into the
+ * rate of the update about to run, in front of gdn_adam_step_dev[_guarded] / gdn_adam_step_seg on the same stream.
+ *   hyper    float[G][6], the table of gdn_adam_step_dev (G = 1) / gdn_adam_step_seg; only hyper[k][0] is written;
+ *   base_lr  double[G] in device memory: per group lr * lr_mult;
+ *   states   G x 32 bytes, the step states (8-byte aligned); only read.  u = states[k].t is the number of updates applied so
+ *            far, i.e. the 0-based index of the update about to run (a skipped step leaves it where it was);
+ *   hyper[k][0] = (float)(base_lr[k] * s(u)), everything in double and rounded to float32 once, s(u) = w(u) * d(u):
+ *     w(u) = (u + 1) / warmup for u < warmup, else 1;
+ *     d(u) = 1 for u < warmup and for kind 0 (constant); otherwise, with x = min(1, (u - warmup) / max(1, total - warmup)),
+ *     kind 1 (linear):  d = floor + (1 - floor) * (1 - x)
+ *     kind 2 (cosine):  d = floor + (1 - floor) * (0.5 * (1 + cos(pi * x)))
+ *   Warm-up, the linear decay and the product are IEEE double operations without contraction: a host that evaluates the same
+ *   expressions in plain double gets the same bits.  cos is the device library's (within double ulps of the host's).
+ * One launch of one workgroup, lane k < G does group k; no allocation, no sync, no host read: capturable.  A NULL pointer, G
+ * outside 1 .. 254, kind outside 0 .. 2, warmup < 0, total < 1, floor outside [0, 1] or NaN, base_lr or states not 8-byte
+ * aligned or hyper not 4-byte aligned return GDN_ERR_BAD_ARG before any launch.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+int gdn_lr_schedule(float* hyper, const double* base_lr, const void* states, int32_t G, int32_t kind, int32_t warmup,
+                    int32_t total, double floor, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
