@@ -1,6 +1,8 @@
 // HBM-bound glue kernels of the GDN hot path for gfx950: BatchNorm finalize /
 // apply / backward, x2 bilinear up-sampling, layout transforms, fused Adam.
 // All are 16-byte-per-lane streaming kernels (NHWC, channel count % 4 == 0).
+#include <type_traits>
+
 #include "common.h"
 #include "up2x.h"
 
@@ -549,7 +551,7 @@ __global__ void fill_kernel(float* __restrict__ p, float v, int64_t n) {
 // ------------------------------------------------------------------------ Adam
 // torch.optim.Adam: g += wd*p; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
 // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
-// The update loop of all three Adam kernels: `step` = lr / bc1, `gscale` the gradient's scale (grad_scale, times the guard's coef).
+// The update loop of adam_kernel and adam_dev_kernel: `step` = lr / bc1, `gscale` the gradient's scale (grad_scale, times the guard's coef).
 __device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, int64_t n, float step, float b1, float b2, float eps,
                                             float wd, float bc2s, float gscale) {
@@ -572,6 +574,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // Capturable Adam: the step counter and the running powers beta^t live in device memory, so a captured training step
 // advances them on every replay.  state = { double beta1^t, double beta2^t, int32 t, float bc1, float bc2s }.
 struct AdamDevState { double p1, p2; int step; float bc1, bc2s; };
+static_assert(sizeof(AdamDevState) == 32, "the step-state table is G x 32 bytes (include/gdn_hip.h)");
+// The gradient guard's record (below; include/gdn_hip.h): every capturable kernel takes one, or null for an unguarded update.
+struct AdamGuard { double sumsq; float norm, coef; int skip, steps, clipped, skipped; };
+static_assert(sizeof(AdamGuard) == 32, "guard record layout is part of the C ABI");
 __device__ __forceinline__ void adam_advance(AdamDevState* st, const float* __restrict__ hyper) {
     st->step += 1;
     st->p1 *= (double)hyper[1];
@@ -579,23 +585,27 @@ __device__ __forceinline__ void adam_advance(AdamDevState* st, const float* __re
     st->bc1 = (float)(1.0 - st->p1);
     st->bc2s = (float)sqrt(1.0 - st->p2);
 }
-__global__ void adam_prep_kernel(AdamDevState* st, const float* __restrict__ hyper) { adam_advance(st, hyper); }
-// the update of both capturable kernels: `gscale` is hyper[5] (adam_dev_kernel) or hyper[5] * coef (adam_dev_guarded_kernel)
-__device__ __forceinline__ void adam_dev_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
-                                                const AdamDevState* st, float gscale) {
-    adam_update(p, g, m, v, n, hyper[0] / st->bc1, hyper[1], hyper[2], hyper[3], hyper[4], st->bc2s, gscale);
+// The prep launch of every capturable update: lane k advances the step state of row k of a G-row table (G = 1: the one state
+// of gdn_adam_step_dev[_guarded], of which only the 28 bytes before the tail padding are touched).
+__global__ __launch_bounds__(256) void adam_prep_kernel(AdamDevState* states, const float* __restrict__ hyper, int G,
+                                                        const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;    // a skipped step takes no place in any row's bias corrections
+    const int k = (int)threadIdx.x;
+    if (k < G) adam_advance(states + k, hyper + 6 * k);
 }
+inline dim3 adam_prep_block(int G) { return dim3(G <= 64 ? 64 : 256); }       // one wave where it holds every row
+// The capturable update of a contiguous range: the gradient's scale is hyper[5], times the guard's coefficient under a guard.
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                       const float* __restrict__ hyper, const AdamDevState* st) {
-    adam_dev_update(p, g, m, v, n, hyper, st, hyper[5]);
+                                                       const float* __restrict__ hyper, const AdamDevState* st,
+                                                       const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;    // p, m, v are neither read nor written
+    adam_update(p, g, m, v, n, hyper[0] / st->bc1, hyper[1], hyper[2], hyper[3], hyper[4], st->bc2s,
+                guard != nullptr ? hyper[5] * guard->coef : hyper[5]);
 }
 
 // ---- gradient guard: global gradient norm, clipping coefficient and the decision to skip a non-finite step, all in device
 // memory (capturable; no host read).  The record (include/gdn_hip.h) is written with ordinary stores by single threads.
-struct AdamGuard { double sumsq; float norm, coef; int skip, steps, clipped, skipped; };
-static_assert(sizeof(AdamGuard) == 32, "guard record layout is part of the C ABI");
 
 // blocks of the partial-sum launch: a function of n alone, so the order of every addition is too
 constexpr int GRADNORM_MAX_BLOCKS = 1024;
@@ -670,110 +680,93 @@ __global__ void adam_guard_finalize_kernel(AdamGuard* guard, const float* __rest
     if (coef32 < 1.f && !skip) guard->clipped += 1;
     guard->skipped += skip;
 }
-__global__ void adam_prep_guarded_kernel(AdamDevState* st, const float* __restrict__ hyper, const AdamGuard* guard) {
-    if (guard->skip == 0) adam_advance(st, hyper);       // a skipped step takes no place in the bias corrections
-}
-__global__ __launch_bounds__(256) void adam_dev_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                               const float* __restrict__ hyper, const AdamDevState* st,
-                                                               const AdamGuard* guard) {
-    if (guard->skip != 0) return;                        // p, m, v are neither read nor written
-    adam_dev_update(p, g, m, v, n, hyper, st, hyper[5] * guard->coef);
-}
 
-// ---- weight EMA and the in-place exchange of two float ranges (include/gdn_hip.h).  Pure streaming: the body moves 16 bytes per
-// lane, up to 3 head elements bring it to a 16-byte boundary and fewer than 4 tail elements follow it (lanes of block 0, as in
-// adam_gradnorm_partial_kernel); VEC = false is the scalar form for operands whose bases differ modulo 16.  No atomics, no LDS.
-__device__ __forceinline__ float ema1(float w, float p, float e) { return fmaf(w, p - e, e); }
-// e += w_t (p - e) with w_t = 1 - min(decay, (1 + t) / (10 + t)), t = the step count the Adam update of this store has just
-// advanced; every thread computes w_t itself, in double, rounded once.  A skipped step (guard->skip) reads and writes nothing.
-template <bool VEC>
-__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n,
-                                                         double decay, const AdamDevState* st, const AdamGuard* guard) {
-    if (guard != nullptr && guard->skip != 0) return;
-    const double t = (double)st->step;
-    const float w = (float)(1.0 - fmin(decay, (1.0 + t) / (10.0 + t)));
+// ---- weight EMA, the in-place exchange of two float ranges and the gradient-accumulation sum (include/gdn_hip.h): three element
+// operations on one streaming skeleton over two ranges a and b.  The body moves 16 bytes per lane, up to 3 head elements bring it
+// to a 16-byte boundary of `a` and fewer than 4 tail elements follow it (lanes of block 0, as in adam_gradnorm_partial_kernel);
+// VEC = false is the scalar form for operands whose bases differ modulo 16.  No atomics, no LDS.  An Op has
+//     B              float, or const float where `b` is only read (then nothing is stored there)
+//     begin()        once per thread before anything is read; false: the launch reads and writes nothing
+//     op(a, b)       the element operation, on copies of a[i] and b[i] that go back afterwards
+template <bool VEC, class Op>
+__global__ __launch_bounds__(256) void stream2_kernel(float* __restrict__ a, typename Op::B* __restrict__ b, int64_t n, Op op) {
+    constexpr bool WRITES_B = !std::is_const<typename Op::B>::value;
+    using B4 = typename std::conditional<WRITES_B, f32x4, const f32x4>::type;
+    if (!op.begin()) return;
+    const auto one = [&](int64_t i) {
+        float x = a[i], y = b[i];
+        op(x, y);
+        a[i] = x;
+        if constexpr (WRITES_B) b[i] = y;
+    };
     const int64_t T = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
     if (!VEC) {
-        for (int64_t i = tid; i < n; i += T) e[i] = ema1(w, p[i], e[i]);
-        return;
-    }
-    const StreamSplit s = stream_split(e, n);
-    f32x4* __restrict__ ev = reinterpret_cast<f32x4*>(e + s.head);
-    const f32x4* __restrict__ pv = reinterpret_cast<const f32x4*>(p + s.head);
-    for (int64_t i = tid; i < s.nvec; i += T) {
-        const f32x4 x = pv[i];
-        f32x4 a = ev[i];
-        a.x = ema1(w, x.x, a.x); a.y = ema1(w, x.y, a.y); a.z = ema1(w, x.z, a.z); a.w = ema1(w, x.w, a.w);
-        ev[i] = a;
-    }
-    if (blockIdx.x == 0) {
-        const int64_t l = threadIdx.x;
-        if (l < s.head) e[l] = ema1(w, p[l], e[l]);
-        if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); e[i] = ema1(w, p[i], e[i]); }
-    }
-}
-template <bool VEC>
-__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
-    const int64_t T = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
-    if (!VEC) {
-        for (int64_t i = tid; i < n; i += T) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
+        for (int64_t i = tid; i < n; i += T) one(i);
         return;
     }
     const StreamSplit s = stream_split(a, n);
     f32x4* __restrict__ av = reinterpret_cast<f32x4*>(a + s.head);
-    f32x4* __restrict__ bv = reinterpret_cast<f32x4*>(b + s.head);
-    for (int64_t i = tid; i < s.nvec; i += T) { const f32x4 x = av[i]; av[i] = bv[i]; bv[i] = x; }
-    if (blockIdx.x == 0) {
-        const int64_t l = threadIdx.x;
-        if (l < s.head) { const float x = a[l]; a[l] = b[l]; b[l] = x; }
-        if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); const float x = a[i]; a[i] = b[i]; b[i] = x; }
-    }
-}
-// acc[i] = acc[i] + g[i]: one IEEE float32 add per element (nothing to contract into an FMA, subnormals kept), the sum of a
-// gradient-accumulation group (include/gdn_hip.h).  `g` is only read.
-template <bool VEC>
-__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n) {
-    const int64_t T = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
-    if (!VEC) {
-        for (int64_t i = tid; i < n; i += T) acc[i] = acc[i] + g[i];
-        return;
-    }
-    const StreamSplit s = stream_split(acc, n);
-    f32x4* __restrict__ av = reinterpret_cast<f32x4*>(acc + s.head);
-    const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + s.head);
+    B4* __restrict__ bv = reinterpret_cast<B4*>(b + s.head);
     for (int64_t i = tid; i < s.nvec; i += T) {
-        const f32x4 x = gv[i];
-        f32x4 a = av[i];
-        a.x = a.x + x.x; a.y = a.y + x.y; a.z = a.z + x.z; a.w = a.w + x.w;
-        av[i] = a;
+        const f32x4 y4 = bv[i], x4 = av[i];
+        float x[4] = {x4.x, x4.y, x4.z, x4.w}, y[4] = {y4.x, y4.y, y4.z, y4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) op(x[e], y[e]);
+        av[i] = f32x4{x[0], x[1], x[2], x[3]};
+        if constexpr (WRITES_B) bv[i] = f32x4{y[0], y[1], y[2], y[3]};
     }
     if (blockIdx.x == 0) {
         const int64_t l = threadIdx.x;
-        if (l < s.head) acc[l] = acc[l] + g[l];
-        if (l >= 64 && s.tail0 + (l - 64) < n) { const int64_t i = s.tail0 + (l - 64); acc[i] = acc[i] + g[i]; }
+        if (l < s.head) one(l);
+        if (l >= 64 && s.tail0 + (l - 64) < n) one(s.tail0 + (l - 64));
     }
 }
+__device__ __forceinline__ float ema1(float w, float p, float e) { return fmaf(w, p - e, e); }
+// e += w_t (p - e) with w_t = 1 - min(decay, (1 + t) / (10 + t)), t = the step count the Adam update of this store has just
+// advanced; every thread computes w_t itself, in double, rounded once.  A skipped step (guard->skip) reads and writes nothing.
+struct EmaOp {
+    using B = const float;
+    double decay; const AdamDevState* st; const AdamGuard* guard; float w;
+    __device__ bool begin() {
+        if (guard != nullptr && guard->skip != 0) return false;
+        const double t = (double)st->step;
+        w = (float)(1.0 - fmin(decay, (1.0 + t) / (10.0 + t)));
+        return true;
+    }
+    __device__ void operator()(float& e, float p) const { e = ema1(w, p, e); }
+};
+struct SwapOp {
+    using B = float;
+    __device__ bool begin() { return true; }
+    __device__ void operator()(float& a, float& b) const { const float x = a; a = b; b = x; }
+};
+// acc[i] = acc[i] + g[i]: one IEEE float32 add per element (nothing to contract into an FMA, subnormals kept), the sum of a
+// gradient-accumulation group.  `g` is only read.
+struct AccumulateOp {
+    using B = const float;
+    __device__ bool begin() { return true; }
+    __device__ void operator()(float& acc, float g) const { acc = acc + g; }
+};
 // one lane per 16 bytes (VEC) or per float, capped like the Adam update's grid; the rest is grid-strided
 inline int stream_rw_blocks(int64_t n, bool vec) { return stream_blocks(vec ? cdiv64(n, 4) : n, 256, 4096); }
+// stream2_kernel in the form the two bases allow: VEC where they sit at the same offset within 16 bytes
+template <class Op>
+inline void stream2_launch(float* a, typename Op::B* b, int64_t n, Op op, void* stream) {
+    const bool vec = (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0;
+    const auto kernel = vec ? stream2_kernel<true, Op> : stream2_kernel<false, Op>;
+    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, (hipStream_t)stream, a, b, n, op);
+}
 
 // ---- segmented forms (include/gdn_hip.h): one launch over an arena whose 64-float chunks belong to parameter groups.  map[c] is
 // the group of chunk c or SEG_SKIP.  A lane moves 16 bytes, so the 16 lanes l, l+1, ... l+15 (l % 16 == 0) of a wave share one
 // chunk in every trip of the grid-stride loop (the stride is a multiple of 256 and n of 64, so such a lane group is inside the
 // arena or outside it as a whole): its first lane reads the map byte and the others take it from that lane.  No atomics, no LDS.
 constexpr int SEG_SKIP = 0xFF;
-static_assert(sizeof(AdamDevState) == 32, "the step-state table is G x 32 bytes (include/gdn_hip.h)");
 __device__ __forceinline__ int seg_group(const uint8_t* __restrict__ map, int64_t i, bool inside) {
     const int lane = (int)(threadIdx.x & 63u);
     int k = SEG_SKIP;
     if (inside && (lane & 15) == 0) k = (int)map[i >> 4];
     return __shfl(k, lane & ~15);
-}
-__global__ __launch_bounds__(256) void adam_prep_seg_kernel(AdamDevState* states, const float* __restrict__ hyper, int G,
-                                                            const AdamGuard* guard) {
-    if (guard != nullptr && guard->skip != 0) return;    // a skipped step takes no place in any group's bias corrections
-    const int k = (int)threadIdx.x;
-    if (k < G) adam_advance(states + k, hyper + 6 * k);
 }
 // One element of adam_update with the roundings of that loop's gfx950 code spelled out, so the bits are the same whatever
 // the compiler would contract in a four-wide body: there the weight decay is fused into the scaled gradient
@@ -832,7 +825,7 @@ __global__ __launch_bounds__(256) void adam_gradnorm_seg_partial_kernel(const f3
     const double s = block_sum_d256(a0 + a1, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
-// ema_update_kernel per chunk: the warm-up weight comes from the step count of the chunk's own group
+// EmaOp per chunk: the warm-up weight comes from the step count of the chunk's own group
 __global__ __launch_bounds__(256) void ema_update_seg_kernel(f32x4* __restrict__ ev, const f32x4* __restrict__ pv, int64_t nvec,
                                                       const uint8_t* __restrict__ map, double decay,
                                                       const AdamDevState* __restrict__ states, const AdamGuard* guard) {
@@ -1368,13 +1361,19 @@ extern "C" int gdn_adam_step(float* p, const float* g, float* m, float* v, int64
     return gdn_launch_status();
 }
 
+// gdn_adam_step_dev (guard null) and gdn_adam_step_dev_guarded: the prep launch for the one state, then the update
+static void adam_dev_launch(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, void* state,
+                            const void* guard, void* stream) {
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), adam_prep_block(1), 0, ST(stream), (AdamDevState*)state, hyper, 1,
+                       (const AdamGuard*)guard);
+    hipLaunchKernelGGL(adam_dev_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n, hyper,
+                       (const AdamDevState*)state, (const AdamGuard*)guard);
+}
 extern "C" int gdn_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, void* state,
                                  void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!p || !g || !m || !v || n <= 0 || !hyper || !state) return GDN_ERR_BAD_ARG;
-    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, ST(stream), (AdamDevState*)state, hyper);
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n, hyper,
-                       (const AdamDevState*)state);
+    adam_dev_launch(p, g, m, v, n, hyper, state, nullptr, stream);
     return gdn_launch_status();
 }
 
@@ -1403,10 +1402,7 @@ extern "C" int gdn_adam_step_dev_guarded(float* p, const float* g, float* m, flo
                                          void* state, const void* guard, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!p || !g || !m || !v || n <= 0 || !hyper || !state || !guard) return GDN_ERR_BAD_ARG;
-    hipLaunchKernelGGL(adam_prep_guarded_kernel, dim3(1), dim3(1), 0, ST(stream), (AdamDevState*)state, hyper,
-                       (const AdamGuard*)guard);
-    hipLaunchKernelGGL(adam_dev_guarded_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n,
-                       hyper, (const AdamDevState*)state, (const AdamGuard*)guard);
+    adam_dev_launch(p, g, m, v, n, hyper, state, guard, stream);
     return gdn_launch_status();
 }
 
@@ -1415,10 +1411,7 @@ extern "C" int gdn_ema_update(float* ema, const float* p, int64_t n, double deca
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!ema || !p || n <= 0 || !state || !(decay > 0.0 && decay < 1.0)) return GDN_ERR_BAD_ARG;
     if (((uintptr_t)ema & 3) || ((uintptr_t)p & 3) || ((uintptr_t)state & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
-    const bool vec = (((uintptr_t)ema ^ (uintptr_t)p) & 15) == 0;
-    const auto kernel = vec ? ema_update_kernel<true> : ema_update_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), ema, p, n, decay,
-                       (const AdamDevState*)state, (const AdamGuard*)guard);
+    stream2_launch(ema, p, n, EmaOp{decay, (const AdamDevState*)state, (const AdamGuard*)guard, 0.f}, stream);
     return gdn_launch_status();
 }
 extern "C" int gdn_swap_f32(float* a, float* b, int64_t n, void* stream) {
@@ -1426,9 +1419,7 @@ extern "C" int gdn_swap_f32(float* a, float* b, int64_t n, void* stream) {
     if (!a || !b || n <= 0 || ((uintptr_t)a & 3) || ((uintptr_t)b & 3)) return GDN_ERR_BAD_ARG;
     const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
     if (ua < ub + bytes && ub < ua + bytes) return GDN_ERR_BAD_ARG;       // overlapping ranges (a == b included)
-    const bool vec = (((uintptr_t)a ^ (uintptr_t)b) & 15) == 0;
-    const auto kernel = vec ? swap_f32_kernel<true> : swap_f32_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), a, b, n);
+    stream2_launch(a, b, n, SwapOp{}, stream);
     return gdn_launch_status();
 }
 extern "C" int gdn_grad_accumulate(float* acc, const float* g, int64_t n, void* stream) {
@@ -1436,9 +1427,7 @@ extern "C" int gdn_grad_accumulate(float* acc, const float* g, int64_t n, void* 
     if (!acc || !g || n <= 0 || ((uintptr_t)acc & 3) || ((uintptr_t)g & 3)) return GDN_ERR_BAD_ARG;
     const uintptr_t ua = (uintptr_t)acc, ug = (uintptr_t)g, bytes = (uintptr_t)n * sizeof(float);
     if (ua < ug + bytes && ug < ua + bytes) return GDN_ERR_BAD_ARG;       // overlapping ranges (acc == g included)
-    const bool vec = (((uintptr_t)acc ^ (uintptr_t)g) & 15) == 0;
-    const auto kernel = vec ? grad_accumulate_kernel<true> : grad_accumulate_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(stream_rw_blocks(n, vec)), dim3(256), 0, ST(stream), acc, g, n);
+    stream2_launch(acc, g, n, AccumulateOp{}, stream);
     return gdn_launch_status();
 }
 
@@ -1451,7 +1440,7 @@ extern "C" int gdn_adam_step_seg(float* p, const float* g, float* m, float* v, i
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!p || !g || !m || !v || !hyper || !states || G < 1 || G > 254 || seg_bad_range(n, map, p, g, m, v)) return GDN_ERR_BAD_ARG;
     if (((uintptr_t)hyper & 3) || ((uintptr_t)states & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
-    hipLaunchKernelGGL(adam_prep_seg_kernel, dim3(1), dim3(256), 0, ST(stream), (AdamDevState*)states, hyper, (int)G,
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), adam_prep_block(G), 0, ST(stream), (AdamDevState*)states, hyper, (int)G,
                        (const AdamGuard*)guard);
     hipLaunchKernelGGL(adam_seg_kernel, dim3(stream_rw_blocks(n, true)), dim3(256), 0, ST(stream), (f32x4*)p, (const f32x4*)g,
                        (f32x4*)m, (f32x4*)v, n / 4, map, hyper, (const AdamDevState*)states, (const AdamGuard*)guard);

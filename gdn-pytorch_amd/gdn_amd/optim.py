@@ -24,6 +24,7 @@ Learning-rate schedule (``schedule``): warm-up and a constant / linear / cosine 
 device's own update count, one small launch per arena in front of the update -- no host write per step, capturable
 (DESIGN.md 3.9).
 """
+import collections
 import contextlib
 import struct
 
@@ -106,21 +107,64 @@ def check_schedule(schedule):
     return {"kind": kind, "warmup": warmup, "total": total, "floor": floor}
 
 
-class _Plan:
-    """How a segmented optimizer runs one arena.
+_Row = collections.namedtuple("_Row", "hyper state base_lr")
+# one capturable update, gathered: the ranges of the weights, the moments and the average, the gradient, and the device records
+_Launch = collections.namedtuple("_Launch", "w m v ema grad hyper state base_lr map")
+
+
+class _Table:
+    """The device side of the capturable path for a set of rows, one per param group: what the kernels read beside the
+    weights and the moments.  A plain store owns a table of one row; a segmented store's _Plan is a table with a chunk map.
+
+    param_groups  the rows' param groups (the optimizer's own dicts); None for a table a checkpoint brought the step state
+                  of, until the first step says which group it belongs to
+    hyper         float32[G, 6] on the device and `hyper_host`, what the host last wrote there
+    states        uint8[G * 32] on the device, one step state per row (the 28 bytes of _STEP_FMT and 4 of padding), or None
+    base_lr       (Adam(schedule=...) only) float64[G] on the device, each row's lr * lr_mult, and `base_host`
+    map           None: a single row, no chunk map, the plain entry points (gdn_adam_step_dev[_guarded], gdn_ema_update)"""
+    map = None
+
+    def __init__(self, param_groups, rows, device):
+        self.param_groups = param_groups
+        self.hyper = torch.zeros(rows, 6, dtype=torch.float32, device=device)
+        self.hyper_host = self.states = self.base_lr = self.base_host = None
+        self._rows = {}
+
+    def put(self, **buffers):
+        """Give the table its `states` or its `base_lr` (the views row() made of the old ones are dropped)."""
+        self.__dict__.update(buffers)
+        self._rows = {}
+
+    def row(self, k):
+        """Row k as the per-tensor entry points take one: hyper[k], the 28 bytes of its step state that checkpoints carry
+        (None without states) and base_lr[k:k+1] (None without a schedule).  The same three views every time, so a launch
+        costs the host no slicing."""
+        r = self._rows.get(k)
+        if r is None:
+            n = struct.calcsize(_STEP_FMT)
+            r = self._rows[k] = _Row(self.hyper[k], None if self.states is None else self.states[_STATE_BYTES * k:_STATE_BYTES * k + n],
+                                     None if self.base_lr is None else self.base_lr[k:k + 1])
+        return r
+
+
+def _state_row(state):
+    """A 28-byte step state as a row of a table's `states`."""
+    return torch.cat([state, torch.zeros(_STATE_BYTES - state.numel(), dtype=torch.uint8, device=state.device)])
+
+
+class _Plan(_Table):
+    """How a segmented optimizer runs one arena: a _Table with one row per param group that has a live
+    parameter in the arena, and
 
     key      per item of the arena the index of its param group in optimizer.param_groups, -1 for a frozen parameter
              (requires_grad False): what the plan was built from, and what makes it stale
     groups   indices of the param groups with a live parameter here, in order of first appearance; a chunk map entry k
-             means groups[k]
+             means groups[k], row k of the table
     map      uint8[numel / 64] on the device: the group of every 64-float chunk, or 0xFF (skip)
-    hyper    float32[G, 6] on the device and `hyper_host`, what the host last wrote there
-    base_lr  (Adam(schedule=...) only) float64[G] on the device, each group's lr * lr_mult, and `base_host`
-    states   uint8[G * 32] on the device, one step state per group; None while the live parameters' update counts differ
-             (an odd load_state_dict): such an arena runs per tensor
+    states   None while the live parameters' update counts differ (an odd load_state_dict): such an arena runs per tensor
     k_of     id(param) -> its chunk map entry, live parameters only"""
 
-    def __init__(self, items, numel, key, device):
+    def __init__(self, items, numel, key, param_groups, device):
         self.key = tuple(key)
         self.groups = []
         for gi in self.key:
@@ -138,15 +182,8 @@ class _Plan:
                 k = self.k_of[id(p)] = self.groups.index(gi)
                 for c in range(o // _CHUNK, (o + n + _CHUNK - 1) // _CHUNK):
                     cmap[c] = k
+        super().__init__([param_groups[gi] for gi in self.groups], len(self.groups), device)
         self.map = torch.frombuffer(cmap, dtype=torch.uint8).to(device)
-        self.hyper = torch.zeros(len(self.groups), 6, dtype=torch.float32, device=device)
-        self.hyper_host = None
-        self.states = None
-        self.base_lr = self.base_host = None          # a scheduled optimizer: double[G] lr * lr_mult on the device, and the host's copy
-
-    def state(self, k):
-        """Group k's 28-byte step state, as the per-tensor entry points and the checkpoints take one."""
-        return self.states[_STATE_BYTES * k:_STATE_BYTES * k + struct.calcsize(_STEP_FMT)]
 
 
 class _Parked:
@@ -173,10 +210,11 @@ class _Store:
              average beside them (None without ema_decay); view() gives an item's logical-shape view of any of the three
     step     the host's count of updates; `pstep` is None while every parameter has taken that many and becomes
              {id(param): count} once an arena's coverage has been partial (always None for a loose parameter)
-    hyper, hyper_host, group, state, pdev, full_dev
-             the device side of the capturable path: float32[6] hyper-parameters and what the host last wrote there, their
-             param group, the store's step state, {id(param): step state} of the per-tensor path, and whether `state` has
-             taken every update so far (then it may be copied for a parameter: ADVICE r4)
+    table, plan, pdev, full_dev
+             the device side of the capturable path: the store's own one-row _Table (hyper-parameters, step state, base rate;
+             `hyper`, `state` and `base_lr` read its row) or -- an arena of a segmented optimizer -- its _Plan,
+             {id(param): 28-byte step state} of the per-tensor path, and whether the table's or the plan's step states have
+             taken every update so far (then one may be copied for a parameter: ADVICE r4)
     The optimizer keeps its stores in Adam._stores, by id(arena) or id(param); torch.optim.Optimizer.state is not used."""
 
     def __init__(self, items, arena=None):
@@ -193,11 +231,14 @@ class _Store:
         self._drop_dev()
 
     def _drop_dev(self):
-        self.hyper = self.hyper_host = self.group = self.state = None
-        self.base_lr = self.base_host = None      # Adam(schedule=...): float64[1] lr * lr_mult on the device, and the host's copy
-        self.pdev, self.full_dev = {}, False
+        self.table, self.pdev, self.full_dev = None, {}, False
         # segmented optimizers only: the arena's _Plan, and the 'seg' entry of a loaded record until a plan takes it
         self.plan = self.seg_rec = None
+
+    # the one row of a plain store's table, as the entry points take it
+    hyper = property(lambda self: None if self.table is None or self.table.param_groups is None else self.table.row(0).hyper)
+    state = property(lambda self: None if self.table is None else self.table.row(0).state)
+    base_lr = property(lambda self: None if self.table is None else self.table.row(0).base_lr)
 
     @property
     def kind(self):
@@ -212,6 +253,13 @@ class _Store:
         """`item`'s logical-shape view of the store buffer `buf` (tap-major underneath for convolution weights)."""
         p, o, _, tr = item
         return buf if self.arena is None else self.arena._view(buf, o, p.shape, tr)
+
+    def ranges(self, item=None):
+        """(weights, m, v, average or None): the whole buffers, or `item`'s slice of each."""
+        if item is None:
+            return self.weights, self.m, self.v, self.ema
+        _, o, n, _ = item
+        return self.weights[o:o + n], self.m[o:o + n], self.v[o:o + n], None if self.ema is None else self.ema[o:o + n]
 
     def touch(self):
         """The weights changed behind torch's back: bf16 shadow, eval-BatchNorm coefficients."""
@@ -234,7 +282,7 @@ class _Store:
                 return dev(self.pdev[id(p)])
             k = self.plan.k_of.get(id(p))
             if k is not None:
-                return dev(self.plan.state(k), (id(self.plan), k))
+                return dev(self.plan.row(k).state, (id(self.plan), k))
         if self.state is not None:
             if self.pstep is None:
                 return dev(self.state)
@@ -274,14 +322,14 @@ class _Store:
         else:
             self.pstep = None
         if rec.get("state") is not None:
-            self.state = rec["state"].to(device=self.device, copy=True)        # the device's own bytes, verbatim
+            # the device's own bytes, verbatim, in a table that waits for its param group (Adam._ensure_dev)
+            self.table = _Table(None, 1, self.device)
+            self.table.put(states=_state_row(rec["state"].to(device=self.device, copy=True)))
+        self.seg_rec = seg
+        if rec.get("state") is not None or seg is not None:
             self.full_dev = bool(rec["full_dev"])
-            if rec["pstep"] is not None:
+            if seg is not None or rec["pstep"] is not None:
                 self.pdev = {pid: t.to(device=self.device, copy=True) for pid, t in rec["pdev"].items()}
-        if seg is not None:
-            self.seg_rec = seg
-            self.pdev = {pid: t.to(device=self.device, copy=True) for pid, t in rec["pdev"].items()}
-            self.full_dev = bool(rec["full_dev"])
         return True
 
     def fill(self, parked, capturable, averaged, reset=False):
@@ -433,107 +481,79 @@ class Adam(torch.optim.Optimizer):
     def refresh_hyper(self):
         """Push (lr, betas, eps, weight_decay, grad_scale / micro_batches) to the device buffers of the capturable path if they changed."""
         for st in self._stores.values():
-            if st.hyper is not None:
-                self._push_hyper(st, st.group)
-            if st.plan is not None:
-                self._push_plan_hyper(st.plan)
+            for table in (st.table, st.plan):
+                if table is not None and table.param_groups is not None:
+                    self._push_hyper(table)
 
     def _hyper_vals(self, group):
         return (_lr(group), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                 float(group["weight_decay"]), self._scale())
 
-    def _push_hyper(self, st, group):
-        vals = self._hyper_vals(group)
-        if st.hyper_host != vals:
+    def _push_hyper(self, table):
+        """The rows of a table from their param groups, every row with the optimizer's one gradient scale: written when
+        the host's copy says they changed, which a graph capture cannot hold."""
+        vals = tuple(self._hyper_vals(g) for g in table.param_groups)
+        if table.hyper_host != vals:
             _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
-            st.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
-            st.hyper_host = vals
-        if self.schedule is not None and st.base_host != (vals[0],):
-            # the rate the schedule scales, in double; hyper[0] above is what the next gdn_lr_schedule launch overwrites
-            _no_capture("optimizer learning rate changed inside a graph capture; call refresh_hyper() before it")
-            if st.base_lr is None:
-                st.base_lr = _base_rates([vals[0]], st.device)
-            else:
-                st.base_lr.copy_(torch.tensor([vals[0]], dtype=torch.float64))   # in place: captured graphs hold its address
-            st.base_host = (vals[0],)
-
-    def _push_plan_hyper(self, plan):
-        """The group table of a plan: one row per group, every row with the optimizer's one gradient scale."""
-        vals = tuple(self._hyper_vals(self.param_groups[gi]) for gi in plan.groups)
-        if plan.hyper_host != vals:
-            _no_capture("optimizer hyper-parameters changed inside a graph capture; call refresh_hyper() before it")
-            plan.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
-            plan.hyper_host = vals
+            table.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+            table.hyper_host = vals
         rates = tuple(v[0] for v in vals)
-        if self.schedule is not None and plan.base_host != rates:
+        if self.schedule is not None and table.base_host != rates:
+            # the rates the schedule scales, in double; hyper[k][0] above is what the next gdn_lr_schedule launch overwrites
             _no_capture("optimizer learning rate changed inside a graph capture; call refresh_hyper() before it")
-            if plan.base_lr is None:
-                plan.base_lr = _base_rates(rates, plan.hyper.device)
+            if table.base_lr is None:
+                table.put(base_lr=_base_rates(rates, table.hyper.device))
             else:
-                plan.base_lr.copy_(torch.tensor(rates, dtype=torch.float64))     # in place: captured graphs hold its address
-            plan.base_host = rates
-
-    def _arena_groups(self, group):
-        """Split a param group into (arena, covers_whole_arena) and stragglers."""
-        arenas, loose = {}, []
-        for p in group["params"]:
-            ar = getattr(p, "_gdn_arena", None)
-            if ar is not None and ar.intact():
-                arenas.setdefault(id(ar), (ar, []))[1].append(p)
-            else:
-                loose.append(p)
-        return arenas, loose
+                table.base_lr.copy_(torch.tensor(rates, dtype=torch.float64))    # in place: captured graphs hold its address
+            table.base_host = rates
 
     def _ensure_dev(self, st, group, steps_taken):
-        """Device side of the capturable path for one store: hyper float32[6] and the step state; `steps_taken` = the
-        host-side count of updates this store has had (a resume folds it in by advancing the powers on the host first)."""
-        if st.hyper is None:
-            st.hyper = torch.zeros(6, dtype=torch.float32, device=st.device)
-            if st.state is None:           # (a loaded checkpoint brings the device's own bytes: _Store.take_record)
-                st.state = _step_state(group, steps_taken, st.device)
-            st.group = group
-        self._push_hyper(st, group)
+        """Device side of the capturable path for one plain store: its one-row table with the step state; `steps_taken` =
+        the host-side count of updates this store has had (a resume folds it in by advancing the powers on the host first)."""
+        if st.table is None:
+            st.table = _Table(None, 1, st.device)
+        table = st.table
+        if table.param_groups is None:
+            if table.states is None:       # (a loaded checkpoint brings the device's own bytes: _Store.take_record)
+                table.put(states=_state_row(_step_state(group, steps_taken, st.device)))
+            table.param_groups = [group]
+        self._push_hyper(table)
 
-    def _update(self, st, group, grad, item=None):
-        """One update of store `st` with `grad` (in the weights' physical layout): the whole store, or `item` of it with
-        that parameter's own step count.  Host path: launched now.  Capturable: launched now, followed by the update of
-        the same range of the weight average from the same step state, or -- guarded -- gathered until the norm of ALL
-        gradients is known."""
-        if item is None:
-            w, m, v, ema, count, state = st.weights, st.m, st.v, st.ema, st.step, st.state
-        else:
-            p, o, n, _ = item
-            w, m, v, ema = st.weights[o:o + n], st.m[o:o + n], st.v[o:o + n], None if st.ema is None else st.ema[o:o + n]
-            count, state = st.pstep[id(p)], st.pdev.get(id(p))
-        if not self.capturable:
-            b1, b2 = group["betas"]
-            ops.adam_step(w, grad, m, v, _lr(group), b1, b2, group["eps"], group["weight_decay"], count, self._scale())
-        else:
-            self._launch(w, grad, m, v, st.hyper, state, ema, base=st.base_lr)
+    def _host_update(self, st, group, grad, item=None):
+        """One update of the host path, launched now: the whole store with its count, or `item` with that parameter's own."""
+        w, m, v, _ = st.ranges(item)
+        b1, b2 = group["betas"]
+        ops.adam_step(w, grad, m, v, _lr(group), b1, b2, group["eps"], group["weight_decay"],
+                      st.step if item is None else st.pstep[id(item[0])], self._scale())
 
-    def _set_rates(self, hyper, base, state):
-        """A scheduled optimizer: this update's rates from the update counts in `state`, written into `hyper` in front of
-        the update that reads them (one launch; the table's other fields stay the host's)."""
-        if self.schedule is not None:
-            s = self.schedule
-            ops.lr_schedule(hyper, base, state, s["kind"], s["warmup"], s["total"], s["floor"])
-
-    def _launch(self, w, grad, m, v, hyper, state, ema, plan=None, base=None):
-        """One capturable update and the average's: now, or -- guarded -- gathered for _guarded_updates().  With `plan` the
-        range is a whole arena under the plan's chunk map, `hyper` its group table and `state` its table of step states.
-        `base`: the base rates beside `hyper` that a schedule scales."""
+    def _launch(self, st, grad, row, state, cmap=None, item=None):
+        """One capturable update of store `st` (all of it, or `item`) with `grad` in the weights' physical layout, and the
+        average's over the same range from the same step state: now, or -- guarded -- gathered until the norm of ALL
+        gradients is known.  `row` (a table's row(k)) gives the hyper-parameters and the base rates a schedule scales, `state`
+        the step state; under `cmap` the range is a whole arena, `row` the plan itself and `state` its table of states."""
+        job = _Launch(*st.ranges(item), grad, row.hyper, state, row.base_lr, cmap)
         if self._work is not None:
-            self._work.append((w, grad, m, v, hyper, state, ema, plan, base))
-            return
-        self._set_rates(hyper, base, state)
-        if plan is None:
-            ops.adam_step_dev(w, grad, m, v, hyper, state)
-            if ema is not None:
-                ops.ema_update(ema, w, self.ema_decay, state)
+            self._work.append(job)
         else:
-            ops.adam_step_seg(w, grad, m, v, plan.map, hyper, state)
-            if ema is not None:
-                ops.ema_update_seg(ema, w, plan.map, self.ema_decay, state)
+            self._issue(job, None)
+
+    def _issue(self, job, guard):
+        """One gathered update with its average's, under `guard` (None: unguarded).  The schedule launch sits right in
+        front of its own update: per-tensor launches of one store share a row of the table."""
+        if self.schedule is not None:         # this update's rates from the counts in `state`, written into `hyper`
+            s = self.schedule
+            ops.lr_schedule(job.hyper, job.base_lr, job.state, s["kind"], s["warmup"], s["total"], s["floor"])
+        if job.map is not None:
+            ops.adam_step_seg(job.w, job.grad, job.m, job.v, job.map, job.hyper, job.state, guard)
+            if job.ema is not None:
+                ops.ema_update_seg(job.ema, job.w, job.map, self.ema_decay, job.state, guard)
+            return
+        if guard is None:
+            ops.adam_step_dev(job.w, job.grad, job.m, job.v, job.hyper, job.state)
+        else:
+            ops.adam_step_dev_guarded(job.w, job.grad, job.m, job.v, job.hyper, job.state, guard)
+        if job.ema is not None:
+            ops.ema_update(job.ema, job.w, self.ema_decay, job.state, guard)      # the same skip decision
 
     def _guard_record(self, device):
         if self._guard is None:
@@ -551,27 +571,18 @@ class Adam(torch.optim.Optimizer):
         work, self._work = self._work, None
         if not work:
             return
-        guard = self._guard_record(work[0][0].device)
-        for k, w in enumerate(work):
-            if w[0].device != guard.device:
-                raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (guard.device, w[0].device))
-            if w[7] is None:
-                ops.grad_sumsq(w[1], guard, accumulate=k > 0)
+        guard = self._guard_record(work[0].w.device)
+        for k, job in enumerate(work):
+            if job.w.device != guard.device:
+                raise GdnError("guarded Adam: parameters on %s and %s; one gradient norm needs one device" % (guard.device, job.w.device))
+            if job.map is None:
+                ops.grad_sumsq(job.grad, guard, accumulate=k > 0)
             else:
-                ops.grad_sumsq_seg(w[1], w[7].map, guard, accumulate=k > 0)      # frozen chunks are not read
-        # (the decision reads the gradient scale alone, which every row of a group table carries)
-        ops.grad_guard_finalize(guard, work[0][4], self.max_grad_norm or 0.0, self.skip_nonfinite)
-        for pdata, grad, m, v, hyper, state, ema, plan, base in work:
-            # (right in front of its own update: per-tensor launches of one store share a row of the table)
-            self._set_rates(hyper, base, state)
-            if plan is not None:
-                ops.adam_step_seg(pdata, grad, m, v, plan.map, hyper, state, guard)
-                if ema is not None:
-                    ops.ema_update_seg(ema, pdata, plan.map, self.ema_decay, state, guard)
-                continue
-            ops.adam_step_dev_guarded(pdata, grad, m, v, hyper, state, guard)
-            if ema is not None:
-                ops.ema_update(ema, pdata, self.ema_decay, state, guard)      # the same skip decision
+                ops.grad_sumsq_seg(job.grad, job.map, guard, accumulate=k > 0)      # frozen chunks are not read
+        # (the decision reads the gradient scale alone, which every row of a table carries)
+        ops.grad_guard_finalize(guard, work[0].hyper, self.max_grad_norm or 0.0, self.skip_nonfinite)
+        for job in work:
+            self._issue(job, guard)
 
     def guard_stats(self):
         """{'norm', 'coef', 'steps', 'clipped', 'skipped'} of the guard: norm and coefficient of the last step, counts over
@@ -596,13 +607,14 @@ class Adam(torch.optim.Optimizer):
         out = [None] * len(self.param_groups)
         index = {id(g): gi for gi, g in enumerate(self.param_groups)}
         for st in self._stores.values():
-            if st.plan is not None:
-                table = st.plan.hyper[:, 0].cpu().tolist()
-                for k, gi in enumerate(st.plan.groups):
-                    if out[gi] is None:
-                        out[gi] = table[k]
-            elif st.hyper is not None and out[index[id(st.group)]] is None:
-                out[index[id(st.group)]] = float(st.hyper[0].item())
+            table = st.plan if st.plan is not None else st.table
+            if table is None or table.param_groups is None:
+                continue
+            rows = [(k, index[id(g)]) for k, g in enumerate(table.param_groups) if out[index[id(g)]] is None]
+            if rows:
+                rates = table.hyper[:, 0].cpu().tolist()
+                for k, gi in rows:
+                    out[gi] = rates[k]
         return out
 
     # ---- weight average ----------------------------------------------------------------------------------------------
@@ -654,14 +666,41 @@ class Adam(torch.optim.Optimizer):
             raise GdnError("optimizer %s while weights and averages are exchanged: call swap_averaged() again first" % what)
 
     # ---- the step ----------------------------------------------------------------------------------------------------
-    def _step_partial(self, st, group):
-        """Per-tensor updates ON SLICES OF THE FLAT MOMENTS for the parameters that have a gradient (torch.optim.Adam skips
-        the others).  Host path: per-parameter step counts (`pstep`), back to the one-launch update once every parameter
-        THAT TAKES GRADIENTS is level again.  Capturable path: the step counter is device memory, so each parameter gets a
-        device state of its own -- a stream-ordered copy of the arena's when the one-launch path ran before -- and the
+    def _step_per_tensor(self, st, items, table=None, clone=False, group=None):
+        """Per-tensor updates ON SLICES OF THE FLAT MOMENTS for those of `items` that have a gradient (torch.optim.Adam
+        skips the others), each with the parameter's own step count.  Host path (`group`): the count is a launch argument.
+        Capturable path (`table`: the plain store's, or the plan): the step counter is device memory, so a parameter gets a
+        device state of its own the first time it runs here -- `clone`: a stream-ordered copy of its row's (no host read),
+        else one made on the host for the updates it has taken -- and is updated with its row's hyper-parameters.  The
         arena stays on per-tensor launches from then on (replays advance those counters behind the host's back, so the
         host cannot tell when they are level)."""
         ar = st.arena
+        for item in items:
+            p, o, n, _ = item
+            if p.grad is None:
+                continue
+            gslice = ar.grad[o:o + n]
+            if p.grad.data_ptr() != gslice.data_ptr():
+                # a caller-owned gradient: bring it into the parameter's physical (tap-major) order
+                gslice = torch.empty_like(p, memory_format=torch.preserve_format).copy_(p.grad)
+            st.pstep[id(p)] += 1
+            if table is None:
+                self._host_update(st, group, gslice, item)
+                continue
+            k = 0 if table.map is None else table.k_of[id(p)]
+            row = table.row(k)
+            if id(p) not in st.pdev:
+                if clone:
+                    _no_capture("capturable Adam: a per-parameter step counter would be created inside a graph capture "
+                                "(every replay would reset it); run one eager step with this gradient coverage first")
+                    st.pdev[id(p)] = row.state.clone()        # the row's device counter so far
+                else:
+                    st.pdev[id(p)] = _step_state(table.param_groups[k], st.pstep[id(p)] - 1, st.device)
+            self._launch(st, gslice, row, st.pdev[id(p)], item=item)
+
+    def _step_partial(self, st, group):
+        """_step_per_tensor for a plain store.  Host path: per-parameter step counts (`pstep`), back to the one-launch
+        update once every parameter THAT TAKES GRADIENTS is level again; the capturable path never goes back."""
         if st.pstep is None:
             st.pstep = {id(p): st.step for p, _, _, _ in st.items}
         if self.capturable:
@@ -670,26 +709,8 @@ class Adam(torch.optim.Optimizer):
             # is no such counter and every parameter starts from its host count
             had_dev = st.full_dev
             self._ensure_dev(st, group, st.step)
-        for item in st.items:
-            p, o, n, _ = item
-            if p.grad is None:
-                continue
-            g = p.grad
-            gslice = ar.grad[o:o + n]
-            if g.data_ptr() != gslice.data_ptr():
-                # a caller-owned gradient: bring it into the parameter's physical (tap-major) order
-                gslice = torch.empty_like(p, memory_format=torch.preserve_format).copy_(g)
-            st.pstep[id(p)] += 1
-            if self.capturable and id(p) not in st.pdev:
-                if had_dev:
-                    _no_capture("capturable Adam: a per-parameter step counter would be created inside a graph capture "
-                                "(every replay would reset it); run one eager step with this gradient coverage first")
-                    st.pdev[id(p)] = st.state.clone()         # the arena's device counter so far (no host read)
-                else:
-                    st.pdev[id(p)] = _step_state(group, st.pstep[id(p)] - 1, st.device)
-            self._update(st, group, gslice, item)
-        if self.capturable:
-            return
+            return self._step_per_tensor(st, st.items, st.table, clone=had_dev)
+        self._step_per_tensor(st, st.items, group=group)
         counts = {st.pstep[id(p)] for p, _, _, _ in st.items if p.requires_grad}        # (a frozen parameter never levels)
         if len(counts) == 1:              # everyone who steps is level again: back to the one-launch update
             lvl = counts.pop()
@@ -723,24 +744,37 @@ class Adam(torch.optim.Optimizer):
             raise GdnError("optimizer.step() with an accumulated, already all-reduced gradient pending: call "
                            "sync_gradients() after the last backward of an accumulation")
 
-    # ---- segmented: every param group of an arena in one launch -----------------------------------------
-    def _arenas_and_loose(self):
-        """([arena], {id(param): index of its param group}, [(group, loose param)]) over all param groups: arenas in
-        order of first appearance, every parameter of an intact arena under its group's index."""
-        arenas, owner, loose, intact = [], {}, [], {}
+    def _walk(self):
+        """One pass over the param groups, in the order step() updates: ([(group, [(arena, its parameters)], [loose
+        parameters])], {id(param): index of its param group} for the parameters of intact arenas, segmented only).
+        Unsegmented, one entry per group: its intact arenas in order of first appearance, each with the parameters THIS
+        group holds of it.  Segmented, an arena is listed once, where it first appears (its plan reaches every group), with
+        the parameters ANY group holds of it, and the loose parameters of all groups follow the arenas.  Either way an arena
+        is covered when it is listed with all of its parameters.  (Every step walks every parameter: written for speed.)"""
+        per_group, owner, intact, arenas, segmented = [], {}, {}, {}, self.segmented
         for gi, group in enumerate(self.param_groups):
+            listed, loose = [], []
+            if not segmented:
+                arenas = {}
             for p in group["params"]:
                 ar = getattr(p, "_gdn_arena", None)
-                if ar is not None and id(ar) not in intact:
-                    intact[id(ar)] = ar.intact()
-                    if intact[id(ar)]:
-                        arenas.append(ar)
-                if ar is not None and intact[id(ar)]:
-                    owner[id(p)] = gi
+                key = id(ar)
+                if ar is None or not (intact[key] if key in intact else intact.setdefault(key, ar.intact())):
+                    loose.append(p)
+                    continue
+                if key in arenas:
+                    arenas[key][1].append(p)
                 else:
-                    loose.append((group, p))
-        return arenas, owner, loose
+                    arenas[key] = (ar, [p])
+                    listed.append(arenas[key])
+                if segmented:
+                    owner[id(p)] = gi
+            per_group.append((group, listed, loose))
+        if segmented:
+            per_group = [(g, listed, []) for g, listed, _ in per_group] + [(g, [], loose) for g, _, loose in per_group]
+        return per_group, owner
 
+    # ---- segmented: every param group of an arena in one launch (DESIGN.md 3.8) -----------------------------------------
     def _plan_key(self, ar, owner):
         key = []
         for p, _, _, _ in ar.items:
@@ -757,27 +791,26 @@ class Adam(torch.optim.Optimizer):
         runs per tensor) when the live parameters' counts differ or per-parameter states exist already."""
         _no_capture("segmented Adam: the plan of an arena (chunk map, group table, step states) would be built inside a "
                     "graph capture; run one eager step with the same param groups and requires_grad flags first")
-        plan = _Plan(st.items, st.arena.numel, key, st.device)
+        plan = _Plan(st.items, st.arena.numel, key, self.param_groups, st.device)
         old, saved, st.seg_rec = st.plan, st.seg_rec, None
         memo = {}
         counts = {st.count(p, memo) for p, _, _, _ in st.items if id(p) in plan.k_of}
         if len(counts) == 1 and not st.pdev:
             t = counts.pop()
             if saved is not None and tuple(saved["key"]) == plan.key and saved["states"] is not None:
-                plan.states = saved["states"].to(device=st.device, copy=True)        # the device's own bytes, verbatim
+                plan.put(states=saved["states"].to(device=st.device, copy=True))     # the device's own bytes, verbatim
             else:
                 rows = []
                 for gi in plan.groups:
                     row = None
                     if old is not None and old.states is not None and gi in old.groups:
                         k0 = old.groups.index(gi)
-                        if _unpack(_STEP_FMT, old.state(k0))[2] == t:     # (a group nobody was left in keeps an older count)
+                        if _unpack(_STEP_FMT, old.row(k0).state)[2] == t:   # (a group nobody was left in keeps an older count)
                             row = old.states[_STATE_BYTES * k0:_STATE_BYTES * (k0 + 1)].clone()
                     if row is None:
-                        fresh = _step_state(self.param_groups[gi], t, st.device)
-                        row = torch.cat([fresh, torch.zeros(_STATE_BYTES - fresh.numel(), dtype=torch.uint8, device=st.device)])
+                        row = _state_row(_step_state(self.param_groups[gi], t, st.device))
                     rows.append(row)
-                plan.states = torch.cat(rows)
+                plan.put(states=torch.cat(rows))
         st.plan = plan
         return plan
 
@@ -794,61 +827,30 @@ class Adam(torch.optim.Optimizer):
         if st.pstep is None:          # a segmented store counts per parameter: a frozen one stays where it is
             st.pstep = {id(p): st.step for p, _, _, _ in st.items}
         plan = st.plan if st.plan is not None and st.plan.key == key else self._build_plan(st, key)
-        self._push_plan_hyper(plan)
+        self._push_hyper(plan)
         if plan.states is not None and not st.pdev and have == len(live):
             for p, _, _, _ in live:
                 st.pstep[id(p)] += 1
-            st.step = max(st.pstep.values())
             st.full_dev = True
-            self._launch(st.weights, ar.grad, st.m, st.v, plan.hyper, plan.states, st.ema, plan, base=plan.base_lr)
+            self._launch(st, ar.grad, plan, plan.states, plan.map)       # every group in one launch
         else:
-            self._step_partial_segmented(st, plan, live)
+            # each parameter's device step state a copy of its group's wherever the plan has states: they were made for, or
+            # driven to, the count its live parameters share
+            self._step_per_tensor(st, live, plan, clone=plan.states is not None)
+        st.step = max(st.pstep.values())
         st.touch()
 
-    def _step_partial_segmented(self, st, plan, live):
-        """_step_partial for a segmented store: per-tensor updates with each parameter's own group's row of the table,
-        each parameter's device step state a stream-ordered copy of its group's when the segmented launches drove it."""
-        ar = st.arena
-        for item in live:
-            p, o, n, _ = item
-            if p.grad is None:
-                continue
-            k = plan.k_of[id(p)]
-            gslice = ar.grad[o:o + n]
-            if p.grad.data_ptr() != gslice.data_ptr():
-                gslice = torch.empty_like(p, memory_format=torch.preserve_format).copy_(p.grad)
-            st.pstep[id(p)] += 1
-            if id(p) not in st.pdev:
-                if plan.states is not None:
-                    _no_capture("capturable Adam: a per-parameter step counter would be created inside a graph capture "
-                                "(every replay would reset it); run one eager step with this gradient coverage first")
-                    st.pdev[id(p)] = plan.state(k).clone()            # the group's device counter so far (no host read)
-                else:
-                    st.pdev[id(p)] = _step_state(self.param_groups[plan.groups[k]], st.pstep[id(p)] - 1, st.device)
-            self._launch(st.weights[o:o + n], gslice, st.m[o:o + n], st.v[o:o + n], plan.hyper[k], st.pdev[id(p)],
-                         None if st.ema is None else st.ema[o:o + n],
-                         base=None if plan.base_lr is None else plan.base_lr[k:k + 1])
-        st.step = max(st.pstep.values())
-
-    def _step_groups_segmented(self):
-        arenas, owner, loose = self._arenas_and_loose()
-        for ar in arenas:
-            self._refuse_pending_carry(ar)
-            self._step_arena_segmented(ar, owner)
-        for group, p in loose:
-            self._step_store(group, [(p, 0, p.numel(), None)])
-
     def _step_groups(self):
-        if self.segmented:
-            return self._step_groups_segmented()
-        for group in self.param_groups:
-            arenas, loose = self._arena_groups(group)
-            for ar, ps in arenas.values():
+        per_group, owner = self._walk()
+        for group, arenas, loose in per_group:
+            for ar, ps in arenas:
                 self._refuse_pending_carry(ar)
-                if len(ps) != len(ar.items):
-                    loose.extend(ps)      # partial coverage: fall back to per-tensor launches
-                else:
+                if self.segmented:
+                    self._step_arena_segmented(ar, owner)     # (a parameter of the arena that is in no group is refused there)
+                elif len(ps) == len(ar.items):
                     self._step_store(group, ar.items, ar)
+                else:
+                    loose = loose + ps    # partial coverage: per-tensor launches, as loose stores with moments of their own
             for p in loose:
                 self._step_store(group, [(p, 0, p.numel(), None)])
 
@@ -881,7 +883,10 @@ class Adam(torch.optim.Optimizer):
             if self.capturable:
                 self._ensure_dev(st, group, st.step - 1)      # (this update is counted already)
                 st.full_dev = True        # the store's device counter has taken every update so far: a valid thing to copy
-            self._update(st, group, grad)
+                row = st.table.row(0)
+                self._launch(st, grad, row, row.state)
+            else:
+                self._host_update(st, group, grad)
         else:
             # part of the model got no gradient this step (frozen sub-modules, an unused branch): torch.optim.Adam
             # skips those parameters -- the one-launch update would apply weight decay and stale moments to them.
@@ -913,19 +918,12 @@ class Adam(torch.optim.Optimizer):
         """Every store that holds the state of this optimizer's parameters as they are grouped and laid out now, parameters
         in param_groups order within a store."""
         out = []
-        if self.segmented:
-            arenas, owner, loose = self._arenas_and_loose()
-            for ar in arenas:
-                if id(ar) in self._stores and all(id(p) in owner for p, _, _, _ in ar.items):
-                    out.append(self._stores[id(ar)])
-            return out + [self._stores[id(p)] for _, p in loose if id(p) in self._stores]
-        for group in self.param_groups:
-            arenas, loose = self._arena_groups(group)
-            for ar, ps in arenas.values():
+        for _, arenas, loose in self._walk()[0]:
+            for ar, ps in arenas:
                 if id(ar) in self._stores and len(ps) == len(ar.items):
                     out.append(self._stores[id(ar)])
-                else:
-                    loose.extend(ps)
+                elif not self.segmented:
+                    loose = loose + ps
             out.extend(self._stores[id(p)] for p in loose if id(p) in self._stores)
         return out
 

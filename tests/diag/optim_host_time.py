@@ -4,9 +4,11 @@
 The work the GPU receives is pinned elsewhere (tests/test_optim_launch_order_cpu.py); what a change to optim.py can still
 cost is host time, so the launches are stubbed out (as in that test) and no queue back-pressure from 72 M-element kernels
 enters.  Needs no GPU: AutoEncoder_DtoD's parameters (one arena) live on the CPU, loose parameters do not occur.
-    forms      host path / capturable / guard + EMA (max_grad_norm, skip_nonfinite, ema_decay)
+    forms      host path / capturable / guard + EMA (max_grad_norm, skip_nonfinite, ema_decay) / schedule (cosine) /
+               segmented / seg + all (segmented with the guard, the average and the schedule)
     coverage   full: one launch per step;  frozen: res512_3 has no gradient -- the per-tensor path, one launch (and one
-               gathered tuple, one EMA launch) per remaining parameter, where the host cost is largest
+               gathered record, one EMA launch) per remaining parameter, where the host cost is largest; a segmented
+               optimizer stays on one launch there (res512_3 is requires_grad False: its chunks are skipped)
 A window is a fresh optimizer, 20 warm-up steps and time.perf_counter around `steps` calls of step().  With --parent-optim
 FILE that file is loaded as a second module and the two alternate, `rounds` windows each per form.
 Bar, per form: this tree's median <= the parent's median + (the parent's max - min over its rounds).  Exit status 1 if a
@@ -51,7 +53,8 @@ if opt.parent_optim:
 if not torch.cuda.is_available():
     torch.cuda.is_current_stream_capturing = lambda: False
 
-for name in ("adam_step", "adam_step_dev", "adam_step_dev_guarded", "grad_sumsq", "grad_guard_finalize", "ema_update", "swap_"):
+for name in ("adam_step", "adam_step_dev", "adam_step_dev_guarded", "grad_sumsq", "grad_guard_finalize", "ema_update", "swap_",
+             "adam_step_seg", "grad_sumsq_seg", "ema_update_seg", "lr_schedule"):
     setattr(ops, name, lambda *a, **k: None)
 ops.zeros = lambda shape, device: torch.zeros(shape, dtype=torch.float32, device=device)
 
@@ -62,8 +65,11 @@ model._gdn_param_arena = ar
 if opt.stub_intact:
     ar.intact = lambda: True
 frozen = {id(p) for p in model.res512_3.parameters()}
-FORMS = [("host path", {}), ("capturable", {"capturable": True}),
-         ("guard + EMA", {"max_grad_norm": 1.0, "skip_nonfinite": True, "ema_decay": 0.999})]
+GUARD_EMA = {"max_grad_norm": 1.0, "skip_nonfinite": True, "ema_decay": 0.999}
+SCHED = {"kind": "cosine", "warmup": 100, "total": 100000, "floor": 0.1}
+FORMS = [("host path", {}), ("capturable", {"capturable": True}), ("guard + EMA", GUARD_EMA),
+         ("schedule", {"schedule": SCHED}), ("segmented", {"segmented": True}),
+         ("seg + all", dict(GUARD_EMA, segmented=True, schedule=SCHED))]
 KW = dict(lr=2e-5, betas=[0.9, 0.999], eps=1e-8, weight_decay=5e-4)
 
 

@@ -253,8 +253,8 @@ def test_the_reference_decay_composes(gpu, form):
 def test_graphed_step_matches_eager_without_a_host_push(gpu, form, monkeypatch):
     """Three eager updates, then eight replays of a captured one that cross the end of the warm-up (W = 5) and of the run
     (total = 9): the same rates and bit-identical weights, moments and step states as eleven eager updates.  No host push
-    happens between replays: refresh_hyper() looks at the tables before every replay, and none of its _push_hyper /
-    _push_plan_hyper calls writes anything (the host copies they compare against stay what they were)."""
+    happens between replays: refresh_hyper() looks at the tables before every replay, and none of its _push_hyper
+    calls writes anything (the host copies they compare against stay what they were)."""
     from gdn_amd.graph import GraphedTrainStep
     from gdn_amd.optim import Adam
     seg = form == "segmented"
@@ -276,7 +276,7 @@ def test_graphed_step_matches_eager_without_a_host_push(gpu, form, monkeypatch):
         run = step_fn
         if mode == "graph":
             run = GraphedTrainStep(step_fn, (grads[2],), opt, prewarmed=True)
-            for name in ("_push_hyper", "_push_plan_hyper"):
+            for name in ("_push_hyper",):
                 def counted(target, *a, _f=getattr(Adam, name), _n=name):
                     host = lambda: (target.hyper_host, target.base_host)      # noqa: E731
                     before = host()

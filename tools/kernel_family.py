@@ -27,7 +27,8 @@ def family(n):
         return "pointwise (upsample/fold/add/cast/layout)"
     if re.search(r"berhu|sobel|smooth|sqdiff|finalize_sum|absdiff|zero_u32|depth_metrics", n):
         return "losses/metrics"
-    if "adam" in n or re.search(r"ema_update|swap_f32", n):       # (the weight average runs right after the update it follows)
+    # (the weight average runs right after the update it follows; stream2_kernel<VEC, EmaOp / SwapOp> since they share a skeleton)
+    if "adam" in n or re.search(r"ema_update|swap_f32|EmaOp|SwapOp", n):
         return "adam"
     if "at::native" in n or n.startswith("void at::"):
         return "torch (at::native)"
