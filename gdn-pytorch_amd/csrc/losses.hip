@@ -12,8 +12,10 @@ namespace {
 
 struct LossWs {
     unsigned* maxbits;
+    double* coef;      // [2] at byte 16 of the header: the SILog gradient coefficients a, b
     double* part;      // [LOSS_MAXBLK]
     double* part2;     // [LOSS_MAXBLK]
+    double* part3;     // [LOSS_MAXBLK]
     float* fa;         // [npix]
     float* fb;         // [npix]
 };
@@ -22,9 +24,11 @@ inline LossWs carve(void* ws, int64_t npix) {
     char* b = (char*)ws;
     LossWs w;
     w.maxbits = (unsigned*)b;
+    w.coef = (double*)(b + 16);
     w.part = (double*)(b + LOSS_HDR);
     w.part2 = w.part + LOSS_MAXBLK;
-    w.fa = (float*)(w.part2 + LOSS_MAXBLK);
+    w.part3 = w.part2 + LOSS_MAXBLK;
+    w.fa = (float*)(w.part3 + LOSS_MAXBLK);
     w.fb = w.fa + npix;
     return w;
 }
@@ -97,6 +101,97 @@ __global__ __launch_bounds__(256) void berhu_kernel(const float* __restrict__ ou
     }
     acc = block_sum_d256(acc, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// ------------------------------------------------------------------ SILog
+// Scale-invariant log loss (gdn_hip.h: gdn_silog_masked), float64 per pixel.  silog_pixel is the ONE place a pixel's validity and
+// d = log u(out) - log u(gt) are evaluated: the statistics pass and the gradient pass both call it, so the gradient is taken
+// from the bits the sums were taken from.  o1 = out + 1; live = the prediction is not clamped (a NaN is live: it must reach
+// the gradient).  out[i] is loaded for valid pixels only.
+__device__ __forceinline__ bool silog_pixel(const float* __restrict__ out, const float* __restrict__ gt,
+                                            const float* __restrict__ sparse, int Cs, int64_t HW, int W, int y1, int y2,
+                                            int x1, int x2, double fl, int64_t i, double& d, double& o1, bool& live) {
+    const double tg = ((double)gt[i] + 1.0) * 0.5;
+    if (!(tg > fl)) return false;
+    if (sparse) {
+        const int64_t b = i / HW, hw = i - b * HW;
+        const int y = (int)(hw / W), x = (int)(hw - (int64_t)y * W);
+        if (!(y >= y1 && y < y2 && x >= x1 && x < x2)) return false;
+        if (!(sparse[b * Cs * HW + hw] > -1.f)) return false;
+    }
+    o1 = (double)out[i] + 1.0;
+    const double to = o1 * 0.5;
+    live = !(to <= fl);
+    d = log(to < fl ? fl : to) - log(tg);      // (a NaN prediction stays a NaN: fmax would drop it)
+    return true;
+}
+
+__global__ __launch_bounds__(256) void silog_stats_kernel(const float* __restrict__ out, const float* __restrict__ gt,
+                                                          const float* __restrict__ sparse, int Cs, int B, int H, int W,
+                                                          int y1, int y2, int x1, int x2, double fl, double* pn, double* p1,
+                                                          double* p2) {
+    __shared__ double sh[4];
+    const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
+    double cn = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double d, o1;
+        bool live;
+        if (silog_pixel(out, gt, sparse, Cs, HW, W, y1, y2, x1, x2, fl, i, d, o1, live)) {
+            cn += 1.0;
+            s1 += d;
+            s2 += d * d;
+        }
+    }
+    cn = block_sum_d256(cn, sh);
+    s1 = block_sum_d256(s1, sh);
+    s2 = block_sum_d256(s2, sh);
+    if (threadIdx.x == 0) { pn[blockIdx.x] = cn; p1[blockIdx.x] = s1; p2[blockIdx.x] = s2; }
+}
+
+// one workgroup: n, m1, m2, D -> *loss, stats[4] (nullable), coef = {a = weight / (sqrt(D) * n), b = lambda * m1}; a = 0 when there
+// is no valid pixel or D <= 0 (a NaN D is neither: it goes through, into the loss and into a)
+__global__ __launch_bounds__(256) void silog_finalize_kernel(const double* __restrict__ pn, const double* __restrict__ p1,
+                                                             const double* __restrict__ p2, int nb, double lambda,
+                                                             double weight, float* loss, double* stats, double* coef) {
+    __shared__ double sh[4];
+    double cn = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) { cn += pn[i]; s1 += p1[i]; s2 += p2[i]; }
+    cn = block_sum_d256(cn, sh);
+    s1 = block_sum_d256(s1, sh);
+    s2 = block_sum_d256(s2, sh);
+    if (threadIdx.x == 0) {
+        double m1 = 0.0, m2 = 0.0, D = 0.0, l = 0.0, a = 0.0, b = 0.0;
+        if (cn > 0.0) {
+            m1 = s1 / cn;
+            m2 = s2 / cn;
+            D = m2 - lambda * m1 * m1;
+            if (!(D <= 0.0)) {
+                const double r = sqrt(D);
+                l = weight * r;
+                a = weight / (r * cn);
+                b = lambda * m1;
+            }
+        }
+        *loss = (float)l;
+        if (stats) { stats[0] = cn; stats[1] = m1; stats[2] = m2; stats[3] = D; }
+        coef[0] = a;
+        coef[1] = b;
+    }
+}
+
+__global__ __launch_bounds__(256) void silog_grad_kernel(const float* __restrict__ out, const float* __restrict__ gt,
+                                                         const float* __restrict__ sparse, int Cs, int B, int H, int W,
+                                                         int y1, int y2, int x1, int x2, double fl,
+                                                         const double* __restrict__ coef, float* __restrict__ dout) {
+    const double a = coef[0], b = coef[1];
+    if (a == 0.0) return;                      // degenerate: dout keeps its bits (adding 0.f would turn a -0.f into +0.f)
+    const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double d, o1;
+        bool live;
+        if (silog_pixel(out, gt, sparse, Cs, HW, W, y1, y2, x1, x2, fl, i, d, o1, live) && live)
+            dout[i] += (float)(a * (d - b) / o1);
+    }
 }
 
 // ------------------------------------------------------------------ Sobel L1
@@ -234,7 +329,7 @@ __global__ __launch_bounds__(256) void sqdiff_grad_kernel(const void* __restrict
 #define ST(s) ((hipStream_t)(s))
 
 extern "C" size_t gdn_loss_workspace_bytes(int64_t npix) {
-    return LOSS_HDR + 2 * LOSS_MAXBLK * sizeof(double) + 2 * (size_t)npix * sizeof(float);
+    return LOSS_HDR + 3 * LOSS_MAXBLK * sizeof(double) + 2 * (size_t)npix * sizeof(float);
 }
 
 // max |a - b| over n elements -> *max_out (device float).  A non-negative float's bit pattern orders like the float,
@@ -266,6 +361,30 @@ extern "C" int gdn_berhu_masked(const float* out, const float* gt, const float* 
                        ext_max ? (const unsigned*)ext_max : (const unsigned*)w.maxbits, w.part, dout);
     hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(256), 0, ST(stream), (const double*)w.part, nb,
                        3.0 / (double)n, 0, loss);
+    return gdn_launch_status();
+}
+
+extern "C" int gdn_silog_masked(const float* out, const float* gt, const float* sparse, int32_t Cs, int32_t B, int32_t H,
+                                int32_t W, const int32_t box[4], float lambda, float weight, float floor, float* loss,
+                                float* dout, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!out || !gt || !loss || B <= 0 || H <= 0 || W <= 0) return GDN_ERR_BAD_ARG;
+    if (!(lambda >= 0.f && lambda < 1.f) || !(floor > 0.f && floor < 1.f) || !(weight > 0.f)) return GDN_ERR_BAD_ARG;
+    if (sparse && (!box || Cs < 1)) return GDN_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * H * W;
+    if (!workspace || workspace_bytes < gdn_loss_workspace_bytes(n)) return GDN_ERR_WORKSPACE;
+    LossWs w = carve(workspace, n);
+    const int nb = loss_blocks(n);
+    int y1 = 0, y2 = H, x1 = 0, x2 = W;
+    if (box) { y1 = box[0]; y2 = box[1]; x1 = box[2]; x2 = box[3]; }
+    hipLaunchKernelGGL(silog_stats_kernel, dim3(nb), dim3(256), 0, ST(stream), out, gt, sparse, Cs, B, H, W, y1, y2, x1, x2,
+                       (double)floor, w.part, w.part2, w.part3);
+    hipLaunchKernelGGL(silog_finalize_kernel, dim3(1), dim3(256), 0, ST(stream), (const double*)w.part,
+                       (const double*)w.part2, (const double*)w.part3, nb, (double)lambda, (double)weight, loss, stats,
+                       w.coef);
+    if (dout)
+        hipLaunchKernelGGL(silog_grad_kernel, dim3(nb), dim3(256), 0, ST(stream), out, gt, sparse, Cs, B, H, W, y1, y2, x1,
+                           x2, (double)floor, (const double*)w.coef, dout);
     return gdn_launch_status();
 }
 

@@ -55,6 +55,14 @@ the device: one small launch in front of the fused Adam turns th
 cosine decay to ``F x lr`` at the run's last update (``epochs x ceil(epoch_size / accum_steps)``).  Nothing is written from the
 host per step, so ``--graph`` replays it; ``train_state.pt`` stores the schedule and a resumed run must repeat it.
 ``--lr_schedule reference`` without a warm-up is the run without these flags.
+``--loss silog`` trains on the scale-invariant log loss in the masked BerHu's place: ``--silog_weight`` x
+sqrt(mean(d^2) - ``--silog_lambda`` x mean(d)^2) with d = log depth(out) - log depth(gt), depths clamped from below at
+``--silog_floor`` of the range, over every pixel whose ground truth is above that floor (``--silog_mask dense``) or only
+over the pixels of the Garg box with a LiDAR return (``lidar``, KITTI).  One HIP entry point, three launches, float64 per
+pixel; the Sobel / smoothness / latent terms and the progress lines (``output_loss`` is the SILog value) are as ever, and
+``--graph``, ``--resume``, ``--accum_steps``, the gradient guard and bf16 run on it unchanged.  Each rank takes the statistics
+of its own shard; the flag is not stored in ``train_state.pt``: a resumed run repeats it.  ``--loss berhu`` is the run
+without the flag.
 """
 import contextlib
 import io
@@ -205,6 +213,36 @@ def _check_schedule(args):
         raise RuntimeError("--lr_floor %g is where a decay ends, and --lr_schedule %s has none (linear or cosine do)" % (floor, flag))
 
 
+def _check_loss(args, train_loader=None):
+    """--loss / --silog_*: the pixel term of a training run; checked before anything touches the GPU.  train_loader: the
+    loader run() was handed, if any -- one that declares `yields_sparse = False` cannot feed --silog_mask lidar."""
+    loss = getattr(args, "loss", None) or "berhu"
+    given = [k for k in option.SILOG_DEFAULTS if getattr(args, k, None) is not None]
+    if loss != "silog":
+        if given:
+            raise RuntimeError("%s set(s) the scale-invariant log loss, which --loss silog selects (add it, or drop the flag)"
+                               % ", ".join("--" + k for k in given))
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--loss silog is the pixel term of a training run; --mode %s trains nothing" % args.mode)
+    _, lam, weight, floor, lidar = option.pixel_spec(args)
+    if not 0.0 <= lam < 1.0:
+        raise RuntimeError("--silog_lambda %g is not in [0, 1)" % lam)
+    if not (weight > 0.0 and weight != float("inf")):
+        raise RuntimeError("--silog_weight %g is not a positive number" % weight)
+    if not 0.0 < floor < 1.0:
+        raise RuntimeError("--silog_floor %g is not in (0, 1)" % floor)
+    if lidar and args.dataset != "KITTI":
+        raise RuntimeError("--silog_mask lidar needs the sparse LiDAR map and the Garg box of KITTI; --dataset %s has neither "
+                           "(use --silog_mask dense)" % args.dataset)
+    if lidar and train_loader is not None and getattr(train_loader, "yields_sparse", True) is False:
+        raise RuntimeError("--silog_mask lidar: the training loader (%s) yields no sparse map (use --silog_mask dense)"
+                           % type(train_loader).__name__)
+    if getattr(args, "global_berhu", False):
+        raise RuntimeError("--global_berhu shares the BerHu threshold between ranks and --loss silog has none: every rank "
+                           "takes the statistics of its own shard (drop one of the two flags)")
+
+
 def _check_freeze_bn(args):
     """--freeze_bn trains on the stored running statistics; checked before anything touches the GPU."""
     if not getattr(args, "freeze_bn", False):
@@ -320,6 +358,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_graph(args)
     _check_accum(args)
     _check_schedule(args)
+    _check_loss(args, train_loader)
     _check_freeze_bn(args)
     _check_partial(args, args.height, args.width)
     rank, local_rank, world = D.env_rank()

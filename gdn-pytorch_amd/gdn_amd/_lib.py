@@ -109,6 +109,7 @@ _SIGS = {
     "gdn_loss_workspace_bytes": (_sz, [_i64]),
     "gdn_absdiff_max": (c_int32, [_P, _P, _i64, _P, _P]),
     "gdn_berhu_masked": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, POINTER(c_int32), _P, _P, _P, _P, _sz, _P]),
+    "gdn_silog_masked": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, POINTER(c_int32), _f, _f, _f, _P, _P, _P, _P, _sz, _P]),
     "gdn_sobel_l1": (c_int32, [_P, _P, _i32, _i32, _i32, _f, _P, _P, _P, _P, _P, _sz, _P]),
     "gdn_smoothness": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P, _sz, _P]),
     "gdn_mse": (c_int32, [_P, _P, _i64, _f, _i32, _P, _P, _sz, _i32, _P]),
@@ -155,7 +156,8 @@ EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --
 # a stale build would take the arguments apart differently.  (gdn_grad_accumulate joined revision 223 without a new number:
 # _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
-# and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam and gdn_lr_schedule, for the same reason.)
+# and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule and gdn_silog_masked, for the
+# same reason.)
 ABI_VERSION = 223
 
 

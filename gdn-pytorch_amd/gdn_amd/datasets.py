@@ -402,6 +402,7 @@ class GpuNYUAugmentLoader(GpuAugmentLoader):
     (rank / world / order_seed) and drop_last are GpuAugmentLoader's.  height x width <= 251 x 340."""
 
     bind_outputs = None      # this transform allocates its outputs: a captured step copies its batch
+    yields_sparse = False    # the third output is the ground truth again, not a LiDAR map (--silog_mask lidar is refused)
 
     def __init__(self, dataset, batch_size, device, height, width, mode="DtoD", seed=None, workers=0, drop_last=False,
                  rank=0, world=1, order_seed=None):

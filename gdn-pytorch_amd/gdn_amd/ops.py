@@ -968,6 +968,19 @@ def berhu_masked(out, gt, sparse, box, dout, loss, ext_max=None):
                          _p(ext_max), _p(loss), _p(dout), _p(ws), nb, stream())
 
 
+def silog_masked(out, gt, sparse, box, dout, loss, lam, weight, floor, stats=None):
+    """Scale-invariant log loss (gdn_silog_masked): out/gt [B,1,H,W]; sparse [B,Cs,H,W] with its box, or None = every pixel
+    whose ground truth is above the floor; adds the gradient into dout (None: value only); writes loss[()] and, when given,
+    stats = (n, m1, m2, D) into a float64 device tensor of 4."""
+    B, _, H, W = out.shape
+    ws, nb = _loss_ws(B * H * W, out.device)
+    cbox = (ctypes.c_int32 * 4)(*box) if box is not None else None
+    if stats is not None and (stats.dtype != torch.float64 or stats.numel() != 4 or not stats.is_contiguous()):
+        raise GdnError("silog_masked: stats must be a dense float64 tensor of 4")
+    lib.gdn_silog_masked(_p(out), _p(gt), _p(sparse), 0 if sparse is None else sparse.shape[1], B, H, W, cbox,
+                         float(lam), float(weight), float(floor), _p(loss), _p(dout), _p(stats), _p(ws), nb, stream())
+
+
 def sobel_l1(pred, gt, weight, dpred, loss, plus=None, total=None):
     """total (0-dim device tensor) = loss + plus: the step's loss sum comes out of the same kernel."""
     B, _, H, W = pred.shape

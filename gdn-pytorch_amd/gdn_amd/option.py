@@ -2,7 +2,7 @@
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
 --graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm, --warmup_steps, --lr_schedule,
---lr_floor).
+--lr_floor, --loss, --silog_lambda, --silog_weight, --silog_floor, --silog_mask).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -195,7 +195,35 @@ def build_parser():
                         'train_state.pt: a resumed run must repeat it')
     p.add_argument('--lr_floor', type=_unit_float, default=0.0, metavar='F',
                    help='with --lr_schedule linear / cosine: the share of --lr the decay ends at, in [0, 1]')
+    p.add_argument('--loss', default='berhu', choices=['berhu', 'silog'],
+                   help='training: the pixel term of the loss.  berhu: the reference\'s masked BerHu, as ever.  silog: the '
+                        'scale-invariant log loss weight x sqrt(mean(d^2) - lambda x mean(d)^2), d = log depth(out) - log '
+                        'depth(gt) over the valid pixels (DESIGN.md 3.10), in its place; the Sobel / smoothness / latent terms '
+                        'stay.  Every rank takes the statistics of its own shard.  Not stored in train_state.pt, a resumed run '
+                        'repeats it')
+    p.add_argument('--silog_lambda', type=float, default=None, metavar='L',
+                   help='with --loss silog: the variance-focus weight, in [0, 1) (when not given: 0.85)')
+    p.add_argument('--silog_weight', type=float, default=None, metavar='X',
+                   help='with --loss silog: the factor in front of the square root, > 0 (when not given: 10)')
+    p.add_argument('--silog_floor', type=float, default=None, metavar='F',
+                   help='with --loss silog: depths are clamped from below at F x the range before the logarithm and a pixel '
+                        'whose ground truth is not above it is left out, in (0, 1) (when not given: 0.0125, 1 m of 80 m)')
+    p.add_argument('--silog_mask', default=None, choices=['dense', 'lidar'],
+                   help='with --loss silog: dense = every pixel whose ground truth is above the floor; lidar = only pixels '
+                        'inside the Garg box that carry a LiDAR return (KITTI only) (when not given: dense)')
     return p
+
+
+SILOG_DEFAULTS = {'silog_lambda': 0.85, 'silog_weight': 10.0, 'silog_floor': 0.0125, 'silog_mask': 'dense'}
+
+
+def pixel_spec(args):
+    """None for --loss berhu; for --loss silog the spec utils.dtod_loss / rtod_pixel_loss take as `pixel`:
+    ('silog', lambda, weight, floor, use_sparse), flags not given at their defaults."""
+    if (getattr(args, 'loss', None) or 'berhu') != 'silog':
+        return None
+    v = {k: d if getattr(args, k, None) is None else getattr(args, k) for k, d in SILOG_DEFAULTS.items()}
+    return ('silog', float(v['silog_lambda']), float(v['silog_weight']), float(v['silog_floor']), v['silog_mask'] == 'lidar')
 
 
 RTOD_ARCH_DEFAULT = {'RtoD': 'unet', 'RtoD_single': 'unet', 'RtoD_test': 'legacy'}

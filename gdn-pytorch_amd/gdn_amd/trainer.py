@@ -20,6 +20,7 @@ import typing
 import torch
 
 from . import distributed as D
+from . import option
 from . import tracing
 from . import utils as U
 from .calculate_error import (ERROR_NAMES, ERROR_NAMES_MAKE3D, ERROR_NAMES_NYU, compute_errors_device,
@@ -585,11 +586,13 @@ def train_AE_DtoD(args, model, criterion_L2, criterion_L1, optimizer, dataset_lo
                   n_epochs, lr, logger, train_writer, progress=None):
     """Depth->depth auto-encoder training; loss = BerHu + 3*imgrad_loss (trainer.py:411-468).
     progress: what load_training_state() returned -- the loop goes on after that step."""
+    pixel = option.pixel_spec(args)     # None: BerHu, as ever; --loss silog: the spec of its pixel term (DESIGN.md 3.10)
+
     def fwd_bwd(depths, sparse, first=True):
         with tracing.span("gdn.forward"):
             outputs = model(depths, istrain=False)
         with tracing.span("gdn.losses"):
-            terms = U.dtod_loss(outputs, depths, sparse)
+            terms = U.dtod_loss(outputs, depths, sparse, pixel=pixel)
         if first:                       # (--accum_steps: the later backwards of a group accumulate)
             optimizer.zero_grad()
         with tracing.span("gdn.backward"):
@@ -657,6 +660,7 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
     drops the latent term."""
     single = args.mode == 'RtoD_single' or DtoD_model is None
     latent0 = torch.zeros((), device=_device_of(model))
+    pixel = option.pixel_spec(args)     # None: BerHu, as ever; --loss silog: the spec of its pixel term (DESIGN.md 3.10)
 
     def fwd_bwd(inputs, depths, sparse, first=True):
         latent = latent0
@@ -667,10 +671,10 @@ def train_AE_RtoD(args, model, DtoD_model, criterion_L2, criterion_L1, optimizer
             latent = guide_latent_loss(DtoD_model, depths, outputs, faithful=getattr(args, "faithful_guide", False),
                                        latent_grad=getattr(args, "latent_grad", False))
         if latent.requires_grad:            # --latent_grad: a differentiable term joins through autograd
-            pix, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse)
+            pix, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse, pixel=pixel)
             loss = pix + latent
         else:                               # value-only latent loss (F3): summed by the loss kernel itself
-            loss, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse, plus=latent)
+            loss, output_loss, smooth = U.rtod_pixel_loss(outputs, depths, inputs, sparse, plus=latent, pixel=pixel)
         tracing.pop()
         if first:                       # (--accum_steps: the later backwards of a group accumulate)
             optimizer.zero_grad()

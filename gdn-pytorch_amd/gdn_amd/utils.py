@@ -56,6 +56,30 @@ def _berhu(p, g, sparse, box, dp, loss):
     ops.berhu_masked(p, g, sparse, box, dp, loss, ext_max=ext)
 
 
+SILOG_DEFAULTS = (0.85, 10.0, 0.0125)         # lambda, weight, floor: 0.0125 is 1 m of the 80 m range
+
+
+def silog_spec(lam=SILOG_DEFAULTS[0], weight=SILOG_DEFAULTS[1], floor=SILOG_DEFAULTS[2], use_sparse=False):
+    """The `pixel=` spec of dtod_loss / rtod_pixel_loss that swaps the BerHu term for the scale-invariant log loss."""
+    return ("silog", float(lam), float(weight), float(floor), bool(use_sparse))
+
+
+def _pixel_term(pixel, p, g, sparse, box, dp, loss):
+    """The pixel term a spec names, in BerHu's place (pixel None never gets here: it keeps the branches it always took)."""
+    if len(pixel) != 5 or pixel[0] != "silog":
+        raise GdnError("pixel must be None or ('silog', lambda, weight, floor, use_sparse), got %r" % (pixel,))
+    _, lam, weight, floor, use_sparse = pixel
+    if use_sparse and sparse is None:
+        raise GdnError("the silog spec asks for the LiDAR mask, but the batch carries no sparse map")
+    _silog(p, g, _nchw(sparse, "sparse") if use_sparse else None, box if use_sparse else None, dp, loss, lam, weight, floor)
+
+
+def _silog(p, g, sparse, box, dp, loss, lam, weight, floor):
+    if sparse is not None and box is None:
+        box = crop_box_kitti(p.shape[2], p.shape[3])
+    ops.silog_masked(p, g, sparse, box, dp, loss, lam, weight, floor)
+
+
 class _PixelLoss(torch.autograd.Function):
     """loss = f(pred, *consts); the kernel that evaluates f also writes dloss/dpred."""
 
@@ -68,6 +92,9 @@ class _PixelLoss(torch.autograd.Function):
         if kind == "berhu":
             gt, sparse, box = args
             _berhu(p, _c1(gt, "gt"), None if sparse is None else _nchw(sparse, "sparse"), box, dp, loss)
+        elif kind == "silog":
+            gt, sparse, box, lam, weight, floor = args
+            _silog(p, _c1(gt, "gt"), None if sparse is None else _nchw(sparse, "sparse"), box, dp, loss, lam, weight, floor)
         elif kind == "sobel":
             gt, weight = args
             ops.sobel_l1(p, _c1(gt, "gt"), weight, dp, loss)
@@ -82,6 +109,15 @@ class _PixelLoss(torch.autograd.Function):
         elif kind == "rtod":          # BerHu + smoothness (+ a value-only extra term: the latent loss)
             gt, sparse, box, img, parts, extra = args
             _berhu(p, _c1(gt, "gt"), None if sparse is None else _nchw(sparse, "sparse"), box, dp, parts[0])
+            ops.smoothness(p, _nchw(img, "img"), dp, parts[1], plus=parts[0], plus2=extra, total=loss)
+        elif kind == "dtod_pixel":    # dtod with the pixel term a spec names (--loss silog) in BerHu's place
+            gt, sparse, box, parts, pixel = args
+            g = _c1(gt, "gt")
+            _pixel_term(pixel, p, g, sparse, box, dp, parts[0])
+            ops.sobel_l1(p, g, 3.0, dp, parts[1], plus=parts[0], total=loss)
+        elif kind == "rtod_pixel":    # rtod likewise
+            gt, sparse, box, img, parts, extra, pixel = args
+            _pixel_term(pixel, p, _c1(gt, "gt"), sparse, box, dp, parts[0])
             ops.smoothness(p, _nchw(img, "img"), dp, parts[1], plus=parts[0], plus2=extra, total=loss)
         else:
             raise ValueError(kind)
@@ -103,6 +139,16 @@ def berhu_masked_loss(outputs, depths, sparse_depths=None, box=None):
     return _PixelLoss.apply(outputs, "berhu", (depths, sparse_depths, box))
 
 
+def silog_loss(outputs, depths, sparse_depths=None, box=None, lam=SILOG_DEFAULTS[0], weight=SILOG_DEFAULTS[1],
+               floor=SILOG_DEFAULTS[2]):
+    """weight * sqrt(mean(d^2) - lam * mean(d)^2), d = log u(out) - log u(gt) with u(x) = max((x + 1) / 2, floor), over the
+    pixels whose ground truth is above the floor -- and, with sparse_depths, that lie inside the box and carry a LiDAR return
+    (DESIGN.md 3.10).  The scale-invariant log loss of Eigen et al. 2014 with the variance-focus weight lam."""
+    if sparse_depths is not None and box is None:
+        box = crop_box_kitti(outputs.shape[2], outputs.shape[3])
+    return _PixelLoss.apply(outputs, "silog", (depths, sparse_depths, box, float(lam), float(weight), float(floor)))
+
+
 def imgrad_loss(pred, gt):
     """mean|Sy*(p)-Sy*(g)| + mean|Sx*(p)-Sx*(g)| (3x3 Sobel, zero pad). utils.py:127-131."""
     return _PixelLoss.apply(pred, "sobel", (gt, 1.0))
@@ -113,26 +159,35 @@ def depth_smoothness_loss(depth, img):
     return _PixelLoss.apply(depth, "smooth", (img,))
 
 
-def dtod_loss(outputs, depths, sparse_depths=None, box=None):
-    """DtoD training loss, trainer.py:433-456: returns (loss, output_loss, gradient_loss)."""
+def dtod_loss(outputs, depths, sparse_depths=None, box=None, pixel=None):
+    """DtoD training loss, trainer.py:433-456: returns (loss, output_loss, gradient_loss).
+    pixel: None = the reference's BerHu term; silog_spec(...) = the scale-invariant log loss in its place (output_loss is
+    then its value; the Sobel term and the sum are as ever)."""
     if sparse_depths is not None and box is None:
         box = crop_box_kitti(outputs.shape[2], outputs.shape[3])
     parts = torch.empty(2, dtype=torch.float32, device=outputs.device)
-    loss = _PixelLoss.apply(outputs, "dtod", (depths, sparse_depths, box, (parts[0], parts[1])))
+    if pixel is None:
+        loss = _PixelLoss.apply(outputs, "dtod", (depths, sparse_depths, box, (parts[0], parts[1])))
+    else:
+        loss = _PixelLoss.apply(outputs, "dtod_pixel", (depths, sparse_depths, box, (parts[0], parts[1]), pixel))
     return loss, parts[0], parts[1]
 
 
-def rtod_pixel_loss(outputs, depths, rgb, sparse_depths=None, box=None, plus=None):
+def rtod_pixel_loss(outputs, depths, rgb, sparse_depths=None, box=None, plus=None, pixel=None):
     """BerHu + smoothness part of the RtoD loss, trainer.py:705-720,753-757.
     plus: a 0-dim device tensor WITHOUT autograd history (the value-only latent loss, F3) summed into the returned loss
-    by the same kernel: loss = (BerHu + smoothness) + plus, the association of trainer.py:757."""
+    by the same kernel: loss = (BerHu + smoothness) + plus, the association of trainer.py:757.
+    pixel: as for dtod_loss."""
     if sparse_depths is not None and box is None:
         box = crop_box_kitti(outputs.shape[2], outputs.shape[3])
     if plus is not None and (plus.requires_grad or plus.dim() != 0 or plus.dtype != torch.float32 or not plus.is_cuda):
         raise GdnError("rtod_pixel_loss: `plus` must be a detached 0-dim float32 device tensor (add a differentiable term "
                        "with torch's +)")
     parts = torch.empty(2, dtype=torch.float32, device=outputs.device)
-    loss = _PixelLoss.apply(outputs, "rtod", (depths, sparse_depths, box, rgb, (parts[0], parts[1]), plus))
+    if pixel is None:
+        loss = _PixelLoss.apply(outputs, "rtod", (depths, sparse_depths, box, rgb, (parts[0], parts[1]), plus))
+    else:
+        loss = _PixelLoss.apply(outputs, "rtod_pixel", (depths, sparse_depths, box, rgb, (parts[0], parts[1]), plus, pixel))
     return loss, parts[0], parts[1]
 
 

@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn); gdn_silog_masked (--loss silog; gdn_loss_workspace_bytes grows by a third partial array, which every caller queries).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 /* The GDN_HINT_* bits (below) this library acts on.  A binding that sets a bit that CHANGES WHAT IS COMPUTED (GDN_HINT_FLIP_TAPS)
@@ -558,6 +558,25 @@ int gdn_mse(const void* a, const void* b, int64_t n, float weight, int32_t accum
  * da = gscale * 2*weight/n * (a-b).  dtypes: bit0 a, bit1 b, bit2 da.  (--latent_grad) */
 int gdn_mse_grad(const void* a, const void* b, int64_t n, float weight, const float* gscale,
                  void* da, int32_t dtypes, void* stream);
+/* Scale-invariant log loss (Eigen et al. 2014, with the variance-focus weight lambda), --loss silog: replaces the BerHu
+ * term of trainer.py:433-448 == :705-720 where the user asks for it; the reference has no counterpart.  out / gt / sparse /
+ * box as for gdn_berhu_masked (a NULL box with a NULL sparse: every pixel).  With t(x) = (x + 1) / 2 and
+ * u(x) = max(t(x), floor):
+ *   a pixel is VALID iff t(gt) > floor and, when sparse is given, it lies inside box with sparse > -1;
+ *   d_i = log u(out_i) - log u(gt_i) over the n valid pixels, m1 = sum d / n, m2 = sum d^2 / n, D = m2 - lambda * m1^2;
+ *   *loss = weight * sqrt(D);  dout_i += weight / (sqrt(D) * n) * (d_i - lambda * m1) / (out_i + 1) at every valid pixel
+ *   whose prediction is not clamped (t(out_i) <= floor: no gradient).
+ * n == 0 or D <= 0: *loss = 0 and dout is not touched.  A NaN / +Inf prediction at a valid pixel makes *loss and the
+ * gradient of every valid pixel non-finite (the gradient guard's business); an invalid pixel's prediction is never read
+ * into the sums.  All per-pixel arithmetic and the sums are float64; *loss and each gradient term are rounded to float32
+ * once.  Three launches (two when dout is NULL): block partials in a fixed order, a one-workgroup finalize that leaves the
+ * two gradient coefficients in the workspace, the gradient pass -- no atomics, bitwise reproducible.
+ * stats (nullable, 4 device doubles): n, m1, m2, D.  lambda in [0, 1), floor in (0, 1), weight > 0 (GDN_ERR_BAD_ARG). */
+int gdn_silog_masked(const float* out, const float* gt, const float* sparse, int32_t Cs,
+                     int32_t B, int32_t H, int32_t W, const int32_t box[4],
+                     float lambda, float weight, float floor,
+                     float* loss, float* dout, double* stats,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Depth metrics, calculate_error.py:10-103: per image min-max -> x80, Godard
