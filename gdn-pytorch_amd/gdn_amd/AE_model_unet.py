@@ -41,7 +41,7 @@ def _norm_layer(norm, c):
     """nn.BatchNorm2d, or the reference's nn.InstanceNorm2d(c, affine=True, track_running_stats=True) (:73, :91, :147-155).
     With tracked running statistics an InstanceNorm in eval() normalises with the running mean/var exactly like an
     eval-mode BatchNorm, which is what the HIP path executes; in train mode the standalone ConvBlock / ConvTBlock use
-    per-instance statistics (engine._conv_instnorm_train: the BatchNorm kernels on one image at a time)."""
+    per-instance statistics (engine._instance_fwd: the BatchNorm kernels on one image at a time)."""
     if norm == 'Batch':
         return nn.BatchNorm2d(c, affine=True, track_running_stats=True)
     return nn.InstanceNorm2d(c, affine=True, track_running_stats=True)

@@ -82,6 +82,7 @@ class ParamArena:
             self.items.append((p, off, p.numel(), tr))
             off += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
         self.numel = off
+        self._slot = {id(p): (o, tr) for p, o, _, tr in self.items}      # (items keeps every parameter alive: the ids stay its own)
         self.device = device
         self.data = torch.zeros(off, dtype=torch.float32, device=device)
         self.grad = torch.zeros(off, dtype=torch.float32, device=device)
@@ -138,16 +139,16 @@ class ParamArena:
             self._key16 = key
         return self.data16
 
+    def _view_of(self, flat, p):
+        if id(p) not in self._slot:
+            raise KeyError("parameter not in arena")
+        o, tr = self._slot[id(p)]
+        return self._view(flat, o, p.shape, tr)
+
     def bf16_view(self, p):
         v = self._v16.get(id(p))
         if v is None:
-            for q, o, n, tr in self.items:
-                if q is p:
-                    v = self._view(self.bf16_data(), o, p.shape, tr)
-                    self._v16[id(p)] = v
-                    break
-            else:
-                raise KeyError("parameter not in arena")
+            v = self._v16[id(p)] = self._view_of(self.bf16_data(), p)
         return v
 
     def intact(self):
@@ -155,10 +156,7 @@ class ParamArena:
                    for p, o, _, _ in self.items)
 
     def grad_view(self, p):
-        for q, o, n, tr in self.items:
-            if q is p:
-                return self._view(self.grad, o, p.shape, tr)
-        raise KeyError("parameter not in arena")
+        return self._view_of(self.grad, p)
 
     def _exchange_ok(self):
         """An accumulating backward may make its sum in the second gradient arena: a GPU arena outside a stream capture
@@ -538,26 +536,17 @@ def _eval_key(bn):
             None if ar is None else ar.generation)
 
 
-def _eval_coeffs(bn):
-    """scale/shift of an eval-mode BatchNorm, cached until its tensors change."""
+def _stored_coeffs(bn, frozen):
+    """Coefficients of a norm layer that normalises by its running statistics, cached until its tensors change (the key follows
+    the arena generation, so a gamma / beta update by the fused Adam invalidates it): [scale, shift] of an eval-mode layer
+    (ops.bn_eval_coeffs), or with `frozen` the [scale, shift, mean, invstd] block of a train-mode layer for one that is being
+    trained on frozen statistics (ops.bn_frozen_coeffs)."""
+    attr, fn = ("_gdn_frozen_cache", ops.bn_frozen_coeffs) if frozen else ("_gdn_eval_cache", ops.bn_eval_coeffs)
     key = _eval_key(bn)
-    c = getattr(bn, "_gdn_eval_cache", None)
+    c = getattr(bn, attr, None)
     if c is None or c[0] != key:
-        co = ops.bn_eval_coeffs(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
-        c = (key, co)
-        bn._gdn_eval_cache = c
-    return c[1]
-
-
-def _frozen_coeffs(bn):
-    """[scale, shift, mean, invstd] of an eval-mode BatchNorm whose layer is being trained (ops.bn_frozen_coeffs), cached under
-    _eval_coeffs' key: it follows the arena generation, so a gamma / beta update by the fused Adam invalidates it."""
-    key = _eval_key(bn)
-    c = getattr(bn, "_gdn_frozen_cache", None)
-    if c is None or c[0] != key:
-        co = ops.bn_frozen_coeffs(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
-        c = (key, co)
-        bn._gdn_frozen_cache = c
+        c = (key, fn(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps))
+        setattr(bn, attr, c)
     return c[1]
 
 
@@ -571,70 +560,26 @@ def _frozen_stats(ctx, conv, bn):
                 and (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad))
 
 
-def _conv_instnorm_train(ctx, x, conv, inorm, relu, op, w, reflect, need_dx):
-    """Conv -> train-mode InstanceNorm2d(affine=True, track_running_stats=True) -> [ReLU]: the standalone
-    ConvBlock / ConvTBlock(norm='Instance') of the reference (AE_model_unet.py:70-75, :88-92; R and G never build one).
-    Per-instance statistics are batch statistics of a batch of one, so the BatchNorm kernels run once per image on that
-    image's slice: the convolution writes image b's output with its sum / sum-of-squares partials, finalize (momentum 1 into
-    scratch buffers) yields that image's coefficients, mean and unbiased variance, apply / backward use them; the running
-    statistics take the batch mean of the per-instance values (what F.instance_norm does).  A rarely used path: direct
-    kernels, B small launches."""
-    B, H, W, _ = x.shape
-    C = conv.out_channels
-    mom = 0.1 if inorm.momentum is None else inorm.momentum
-    ys, cos, outs = [], [], []
-    rm = torch.zeros((B, C), dtype=torch.float32, device=x.device)
-    rv = torch.ones((B, C), dtype=torch.float32, device=x.device)
-    for b in range(B):
-        yb, st = op.fwd(x[b:b + 1], w, stats=True)
-        co = ops.bn_finalize_train(st, yb.shape[1] * yb.shape[2], inorm.weight.data, inorm.bias.data, rm[b], rv[b], 1.0, inorm.eps)
-        ys.append(yb)
-        cos.append(co)
-        outs.append(ops.bn_apply(yb, co[0], co[1], relu, None, out_dtype=ctx.dtype))
-    if inorm.track_running_stats:
-        inorm.running_mean.mul_(1.0 - mom).add_(rm.mean(0), alpha=mom)
-        inorm.running_var.mul_(1.0 - mom).add_(rv.mean(0), alpha=mom)
-        # (torch's InstanceNorm2d leaves num_batches_tracked untouched: F.instance_norm does not take it)
-        inorm._gdn_stats_ver = getattr(inorm, "_gdn_stats_ver", 0) + 1
-    a = torch.cat(outs, 0)
-    if ctx.record:
-        in_hw = (H, W)
-        ctx.mark_live(a, (x,), (conv.weight, inorm.weight, inorm.bias))
-
-        def bwd():
-            da = ctx.pop_grad(a)
-            if da is None:
-                return
-            da = _dense(da)
-            frozen = not (conv.weight.requires_grad or inorm.weight.requires_grad or inorm.bias.requires_grad)
-            dg = torch.zeros(C, dtype=torch.float32, device=da.device)
-            db = torch.zeros(C, dtype=torch.float32, device=da.device)
-            dys = []
-            for b in range(B):
-                dgb, dbb = torch.empty_like(dg), torch.empty_like(db)
-                dys.append(ops.bn_bwd(da[b:b + 1], ys[b], inorm.weight.data, cos[b], relu, dgb, dbb))
-                dg += dgb
-                db += dbb
-            dy = torch.cat(dys, 0)
-            if not frozen:
-                inorm.weight.grad.copy_(dg)
-                inorm.bias.grad.copy_(db)
-                _wgrad_into(ctx, conv, x, dy)
-                ctx.grads_done(inorm.weight, inorm.bias, conv.weight)
-            if need_dx and ctx.wants_dx(x):
-                wt = ops.transpose_taps(_w_tap(conv)[0], dtype=torch.float32)
-                ctx.grads[id(x)] = (x, op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(x, torch.float32)))
-        ctx.tape.append(bwd)
-    return a
-
-
 # The kernels one conv_bn_act call runs (_conv_path).  fused_in: the loader applies a deferred train-mode BatchNorm
 # (in_affine / in_relu) or x2 upsampling (up2x); dyb: the backward applies this layer's BatchNorm backward while it transforms
 # dy; bnb_slots(): slots of the BatchNorm-backward partials of x's producer that the data gradient can emit; fwd(x, w, stats=,
-# [loader / epilogue keywords]) -> y or (y, stats[, saved state]); bwd(dy, w, in_hw, saved state, ...) -> dx (transform paths
-# only); c1_wgrad: the weight gradient runs on conv_c1_wgrad; up_fold: the direct data gradient may fold the producer's x2
-# upsampling (gdn_conv_dgrad dx_up2x); epilogue: the forward takes an eval-mode BatchNorm epilogue.
+# [loader / epilogue keywords]) -> (y, stats or None, saved state or None) (_fwd3); bwd(dy, w, in_hw, saved state, ...) -> dx
+# (transform paths only); c1_wgrad: the weight gradient runs on conv_c1_wgrad; up_fold: the direct data gradient may fold the
+# producer's x2 upsampling (gdn_conv_dgrad dx_up2x); epilogue: the forward takes an eval-mode BatchNorm epilogue.
 ConvPath = collections.namedtuple("ConvPath", "name fused_in dyb bnb_slots fwd bwd c1_wgrad up_fold epilogue")
+
+
+def _fwd3(fwd, **fixed):
+    """One return shape for every path's forward: ops.*_fwd return y alone, (y, stats), (y, state) or (y, stats, state),
+    depending on what was asked for; this returns (y, stats or None, state or None)."""
+    def run(x, w, stats=False, **kw):
+        r = fwd(x, w, stats=stats, **fixed, **kw)
+        if not isinstance(r, tuple):
+            return r, None, None
+        if stats:
+            return r[0], r[1], (r[2] if len(r) > 2 else None)
+        return r[0], None, r[1]
+    return run
 
 
 def _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect):
@@ -644,11 +589,12 @@ def _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect):
       wino2   Winograd F(3x3,2x2) (csrc/conv_wino2.hip): fp32, 4x4, stride 2, both channel counts >= _WINO2_MIN_C
       c1      1 <-> 64 channel 9x9 kernels (csrc/conv_c1.hip): fp32 1- or 3-channel image into a Conv2d
       direct  op.fwd / op.dgrad (the C library picks igemm / ring / ring2)
-    the transform paths and c1 only where the C library supports the geometry, never with a concatenated x2."""
+    the transform paths and c1 only where the C library supports the geometry, never with a concatenated x2, and never in front
+    of a train-mode InstanceNorm, which runs image by image on the direct kernels (_instance_fwd)."""
     k, s = conv.kernel_size[0], conv.stride[0]
     B, H, W = x.shape[0], x.shape[1], x.shape[2]
     lazy = isinstance(x, BnOut)
-    fp32 = ldt == torch.float32 and x2 is None
+    fp32 = ldt == torch.float32 and x2 is None and not (bn.training and isinstance(bn, torch.nn.InstanceNorm2d))
     # GDN_HINT_TRAIN: a layer whose weight is trained (forward + backward + weight gradient), on batch statistics or on frozen
     # ones -- the frequency-domain path then tiles for the sum of both passes (40-point tiles on the 9x9 layers); layers with a
     # fixed weight and inference keep the forward-optimal plan.  Only such a layer keeps the transform-domain state of its forward.
@@ -662,33 +608,55 @@ def _conv_path(ctx, x, conv, bn, op, ldt, x2, reflect):
             # the 3-channel input conv); this keeps it that way by construction (tools/check_no_mfma16_beside_fft.py checks traces).
             raise GdnError("internal: a bf16 model selected a frequency-domain layer")
         return path("fft", True, True, functools.partial(op.fft_bnb_slots, B, H, W, train=train),
-                    functools.partial(op.fft_fwd, spectrum=train, train=train), functools.partial(op.fft_bwd, train=train))
+                    _fwd3(op.fft_fwd, spectrum=train, train=train), functools.partial(op.fft_bwd, train=train))
     if fp32 and k == 3 and s == 1 and op.wino_ok(B, H, W):
-        return path("wino", True, False, functools.partial(op.wino_bnb_slots, B, H, W),
-                    functools.partial(op.wino_fwd, state=train), op.wino_bwd)
+        return path("wino", True, False, functools.partial(op.wino_bnb_slots, B, H, W), _fwd3(op.wino_fwd, state=train), op.wino_bwd)
     if (fp32 and k == 4 and s == 2 and not lazy and min(conv.in_channels, conv.out_channels) >= _WINO2_MIN_C
             and op.wino2_ok(B, H, W)):
-        return path("wino2", False, False, lambda: 0, functools.partial(op.wino2_fwd, state=train), op.wino2_bwd)
+        return path("wino2", False, False, lambda: 0, _fwd3(op.wino2_fwd, state=train), op.wino2_bwd)
     # (an Up2x input reaches c1 materialised: c1_ok reads dtype, channels and layout, which its source shares)
     if (fp32 and not lazy and conv.in_channels in (1, 3) and not isinstance(conv, torch.nn.ConvTranspose2d)
             and ops.c1_ok(x.src if isinstance(x, Up2x) else x, conv.out_channels, k, s, reflect or conv.padding[0], rgb=True)):
-        return path("c1", False, False, None, functools.partial(ops.conv_c1_fwd, reflect=bool(reflect)), None,
-                    c1_wgrad=conv.in_channels == 1)
-    return path("direct", False, False, None, functools.partial(op.fwd, x2=x2), None,
+        return path("c1", False, False, None, _fwd3(ops.conv_c1_fwd, reflect=bool(reflect)), None, c1_wgrad=conv.in_channels == 1)
+    return path("direct", False, False, None, _fwd3(op.fwd, x2=x2), None,
                 up_fold=bool(reflect and not lazy and x2 is None and conv.in_channels % 4 == 0 and H % 2 == 0 and W % 2 == 0))
 
 
-def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_dx=True, defer=False, up_out=None):
-    """[relu](BN(conv(cat(x, x2)))) (+ residual): ConvBlock / ResidualBlock halves / ConvTBlock.
+# ----------------------------------------------------------------------------
+# conv_bn_act: one layer call = a layer record (_layer_call), a norm record (_norm_call) and the helpers below
+# ----------------------------------------------------------------------------
+# What the norm layer does in one conv_bn_act call, decided once in the forward:
+BATCH, FROZEN, FOLDED, EVAL, INSTANCE = "batch", "frozen", "folded", "eval", "instance"
+#   BATCH     train-mode BatchNorm: batch statistics from the conv epilogue, running statistics updated
+#   FROZEN    eval-mode norm layer of a module being trained (_frozen_stats): running statistics, raw conv output kept
+#   FOLDED    eval-mode norm layer folded into the conv epilogue: conv + scale / shift + ReLU (+ residual) in one pass
+#   EVAL      eval-mode norm layer applied by a pass of its own (the epilogue cannot take it)
+#   INSTANCE  train-mode InstanceNorm2d: per-image statistics, the BatchNorm kernels on one image at a time
 
-    up_out (None, or the align_corners flag): the caller also wants F.interpolate(output, scale_factor=2, mode='bilinear') and
-    gets (output, upsampled) back -- on the bf16 path the BatchNorm-apply pass writes both (one kernel), on the fp32 path the
-    upsampled one is the deferred Up2x of upsample().
 
-    x may be a BnOut (the deferred activation of the previous layer) or an Up2x (a deferred upsampling): the fft / wino loaders
-    apply its scale / shift / ReLU or interpolate while loading; any other path materialises it first.  defer=True (the
-    caller guarantees a single consumer) returns this layer's output as a BnOut instead of running the BatchNorm-apply pass,
-    when the layer is a train-mode fp32 one without a residual."""
+class NormCall:
+    """The norm layer of one conv_bn_act call.  The forward fills it: `mode`; `co`, the coefficient block ([scale, shift] for
+    FOLDED / EVAL, [scale, shift, mean, invstd] for BATCH / FROZEN, one such block per image for INSTANCE); `y`, the raw conv
+    output (per image for INSTANCE); `out`, the BnOut of a BATCH / FROZEN layer (it carries the backward's partial sums).
+    dyb: the layer's path applies the last pass of the BatchNorm backward while it transforms dy; ldt: the dtype of dy."""
+    __slots__ = ("mode", "bn", "relu", "dyb", "ldt", "co", "y", "out")
+
+    def __init__(self, mode, bn, relu, dyb, ldt):
+        self.mode, self.bn, self.relu, self.dyb, self.ldt = mode, bn, relu, dyb, ldt
+        self.co = self.y = self.out = None
+
+
+class LayerCall:
+    """What _layer_call resolved for one conv_bn_act call and what its backward needs: conv, bn, op, path, ldt, w, reflect;
+    x (an Up2x only while `up` is set), x2, xin (ConvPath / Ctx.claim), up (the Up2x whose interpolation the loader applies);
+    residual, need_dx; xt (the tensor the conv kernels read), state (what a trained transform-domain layer's forward keeps),
+    up_in (the low-resolution source of an upsampled x and its mode, where the data gradient may fold the upsampling)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _layer_call(ctx, x, conv, bn, x2, reflect):
     op = _conv_op(conv, reflect)
     ldt = _layer_dtype(ctx, conv)
     if x.dtype != ldt:
@@ -708,181 +676,268 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
         else:
             x = x.dense(ctx)
     xin = ctx.claim(x)                   # BnOut of the train-mode BatchNorm that produced x, if we are its first consumer
-    lazy = isinstance(x, BnOut)
     if x2 is not None:
         ctx.claim(x2)
     w, _ = _w_for(ctx, conv, ldt)
-    if bn.training and isinstance(bn, torch.nn.InstanceNorm2d):
-        if lazy or up is not None or x2 is not None or residual is not None or ldt != torch.float32:
-            raise GdnError("train-mode InstanceNorm is implemented for the standalone fp32 ConvBlock / ConvTBlock only")
-        a = _conv_instnorm_train(ctx, x, conv, bn, relu, op, w, reflect, need_dx)
-        return a if up_out is None else (a, upsample(ctx, a, bool(up_out)))
-    xt, kw = x, {}                       # the tensor the conv kernels read, and the forward's loader / epilogue arguments
-    if up is not None:
-        xt, kw = up.src, dict(up2x=up.mode)
-    elif lazy and path.fused_in and _FUSE_TRAIN_BN:
-        xt, kw = x.y, dict(in_affine=(x.co[0], x.co[1]), in_relu=x.relu)
-    elif lazy:
-        xt = x.dense(ctx.dtype)          # (the other loaders go straight to LDS: materialise)
-    # frozen-statistics trained layer: the running statistics normalise, nothing updates them, and the raw conv output is kept
-    # (no epilogue fold) with a train-mode layer's coefficient block, so everything downstream of a train-mode layer -- deferred
-    # activation, apply passes, the consumers' BatchNorm-backward partials -- works on it unchanged
-    frozen_stats = not bn.training and _frozen_stats(ctx, conv, bn)
-    co = None if bn.training else (_frozen_coeffs(bn) if frozen_stats else _eval_coeffs(bn))
-    # eval-mode BN folded into the conv epilogue: conv + scale/shift + ReLU (+ residual) in one pass
-    fused = (not bn.training and not frozen_stats and path.epilogue and ldt == ctx.dtype
-             and not (relu and residual is not None) and (residual is None or residual.dtype == ldt))
-    if fused:
-        kw.update(affine=(co[0], co[1]), act=ops.ACT_RELU if relu else ops.ACT_NONE, addsrc=residual)
-    r = path.fwd(xt, w, stats=bn.training, **kw)
-    y, state, out_info = r, None, None   # state: what a trained transform-domain layer's forward keeps for its backward
-    if frozen_stats:
-        if isinstance(r, tuple):
-            y, state = r[0], (r[1] if len(r) > 1 else None)
-        out_info = BnOut(y, co, relu)
-    if bn.training:
-        y, st, state = r[0], r[1], (r[2] if len(r) > 2 else None)
-        count = y.shape[0] * y.shape[1] * y.shape[2]
-        mom = 0.1 if bn.momentum is None else bn.momentum
-        co = ops.bn_finalize_train(st, count, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, mom, bn.eps,
-                                   num_batches_tracked=bn.num_batches_tracked)
-        bn._gdn_stats_ver = getattr(bn, "_gdn_stats_ver", 0) + 1
-        out_info = BnOut(y, co, relu)
-    a_up = None
-    if fused:
-        a = y
-    elif (defer and out_info is not None and residual is None and _FUSE_TRAIN_BN and ldt == torch.float32
-            and ctx.dtype == torch.float32):
-        a = out_info                                      # scale / shift / ReLU happen in the consumer's loader
-    else:
-        if (up_out is not None and _FUSE_UP2X_BF16 and ctx.dtype == torch.bfloat16 and y.is_contiguous()
-                and (residual is None or residual.is_contiguous()) and y.shape[0] * 2 * y.shape[1] <= 65535
-                and y.shape[3] % 4 == 0):             # (the fused kernel's channel-vector width; other shapes take the two-pass form)
-            a, a_up = ops.bn_apply_up2x(y, co[0], co[1], relu, residual, align_corners=bool(up_out), out_dtype=ctx.dtype)
-        else:
-            a = ops.bn_apply(y, co[0], co[1], relu, residual, out_dtype=ctx.dtype)
-        if out_info is not None and ctx.record and _FUSE_TRAIN_BN:
-            ctx.bn_src[id(a)] = out_info
-    # the layer's input is an upsampled tensor whose producer kept the low-resolution source (up_out above): a reflection-padded
-    # layer's fold pass can write dL/d(source) directly
-    up_in = ctx.up_src.get(id(x)) if path.up_fold else None
-    if ctx.record:
-        in_hw = (x.shape[1], x.shape[2])
-        bn_training = bn.training
-        ctx.mark_live(a, (x, x2, residual), (conv.weight, bn.weight, bn.bias))
+    return LayerCall(conv=conv, bn=bn, op=op, path=path, ldt=ldt, w=w, reflect=reflect, x=x, x2=x2, xin=xin, up=up, state=None)
 
-        def bwd():
-            da = ctx.pop_grad(a)
-            if da is None:
-                return
-            frozen = not (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)
-            if not bn_training and not frozen and not frozen_stats:
-                raise GdnError("backward through an eval-mode BatchNorm of a module in eval() is only implemented for layers "
-                               "with nothing to train (requires_grad False on the conv and BN parameters: the guide network of "
-                               "--latent_grad); to train on frozen statistics keep the module in train() and its norm layers in "
-                               "eval() (freeze_bn())")
-            if residual is not None and ctx.is_live(residual):
-                ctx.add_grad(residual, da)
-            extra = {}
-            wtrain, written = not frozen, None   # (written None: all three parameters, as a train-mode layer always wrote them)
-            if frozen_stats:
-                # a frozen-statistics layer writes only the gradients that are asked for (NULL pointers for the rest)
-                dgam = bn.weight.grad if bn.weight.requires_grad else None
-                dbet = bn.bias.grad if bn.bias.requires_grad else None
-                wtrain = conv.weight.requires_grad
-                written = tuple(p for p in (bn.weight, bn.bias, conv.weight) if p.requires_grad)
-            if frozen_stats and path.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32:
-                # frequency-domain layer: the sums only; pass 3 of the BatchNorm backward with k1 = k2 = 0 IS scale * dz, so the
-                # dy transform applies scale and mask while loading and dy is never written
-                ops.bn_frozen_bwd(da, y, co, relu, dgam, dbet, partial=out_info.partial, need_dy=False)
-                out_info.partial = None
-                dy, extra["dyb"] = da, (y, co, ops.zeros((2, y.shape[3]), y.device), relu)
-            elif frozen_stats:
-                dy = ops.bn_frozen_bwd(da, y, co, relu, dgam, dbet, out_dtype=ldt, partial=out_info.partial)
-                out_info.partial = None
-            elif bn_training and path.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32:
-                # frequency-domain layer: dy has one reader (the dy transform), which applies pass 3 of the BatchNorm
-                # backward while loading -- dy is never written
-                kk = ops.bn_bwd_coeffs(da, y, co, relu, bn.weight.grad if not frozen else None,
-                                       bn.bias.grad if not frozen else None, partial=out_info.partial)
-                out_info.partial = None
-                dy, extra["dyb"] = da, (y, co, kk, relu)
-            elif bn_training:
-                dy = ops.bn_bwd(da, y, bn.weight.data, co, relu, bn.weight.grad if not frozen else None,
-                                bn.bias.grad if not frozen else None, out_dtype=ldt, partial=out_info.partial)
-                out_info.partial = None
-            else:
-                dy = ops.bn_eval_bwd(da, y, co, (2 if fused else 1) if relu else 0, out_dtype=ldt)
-            want_dx = need_dx and (ctx.wants_dx(x) or (x2 is not None and ctx.wants_dx(x2)))
-            if path.bwd is not None:
-                # one transform of dy feeds both gradients; the forward's transformed input is reused for dw
-                gv = _grad_tap(conv) if wtrain else None
-                if gv is not None or want_dx:
-                    bnb = None
-                    if xin is not None and want_dx and xin.y.dtype == torch.float32:
-                        # x = [relu](BN_train(xin.y)) and this data gradient is its final gradient: emit the producer's
-                        # BatchNorm-backward partial sums from the epilogue that writes dx
-                        slots = path.bnb_slots()
-                        if slots > 0:
-                            part = torch.empty((slots, 2, conv.in_channels), dtype=torch.float32, device=dy.device)
-                            bnb = (xin.y, xin.co, xin.relu, part)
-                    gx = x                                  # the tensor whose gradient this layer's dx is
-                    if up is not None:
-                        extra["up2x"] = up.mode             # ... the low-resolution source of the deferred upsampling
-                        gx = up.src
-                    dx = path.bwd(dy, w, in_hw, state, dw_tap=gv, need_dx=want_dx,
-                                  addsrc=ctx.pop_grad_as(gx, ldt) if want_dx else None, bnb=bnb, **extra)
-                    if want_dx:
-                        ctx.grads[id(gx)] = (gx, dx)
-                        if bnb is not None:
-                            xin.partial = bnb[3]
-                if not frozen:
-                    ctx.grads_done(*(written or (bn.weight, bn.bias, conv.weight)))
-                return
-            if not frozen:
-                if not wtrain:
-                    pass
-                elif path.c1_wgrad and dy.is_contiguous():
-                    ops.conv_c1_wgrad(xt, dy, tap_view(conv.weight.grad, False), reflect=bool(reflect))
-                else:
-                    _wgrad_into(ctx, conv, xt, dy, x2)
-                ctx.grads_done(*(written or (bn.weight, bn.bias, conv.weight)))
-            if want_dx:
-                wt = ops.transpose_taps(_w_tap(conv)[0], dtype=ldt)
-                if x2 is None:
-                    bnb = None
-                    if (xin is not None and ldt == torch.bfloat16 and xin.y.dtype == ldt and _FUSE_TRAIN_BN
-                            and xin.y.is_contiguous()):
-                        # x = [relu](BN_train(xin.y)) and this data gradient is its final gradient (we are its first consumer;
-                        # the other consumers' gradients arrive as addsrc): the LDS-DMA ring kernel's epilogue emits the
-                        # producer's BatchNorm-backward partial sums, as the Winograd path does for the fp32 layers
-                        slots = op.dgrad_bnb_slots(x.shape[0], x.shape[1], x.shape[2], ldt)
-                        if slots > 0:
-                            part = torch.empty((slots, 2, conv.in_channels), dtype=torch.float32, device=dy.device)
-                            bnb = (xin.y, xin.co, xin.relu, part)
-                    if up_in is not None and bnb is None and id(x) not in ctx.grads:
-                        lo, mode = up_in
-                        ctx.grads[id(lo)] = (lo, op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(lo, ldt), up2x=mode))
-                        return
-                    dx = op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(x, ldt), bnb=bnb)
-                    ctx.grads[id(x)] = (x, dx)
-                    if bnb is not None:
-                        xin.partial = bnb[3]
-                else:
-                    dcat = op.dgrad(dy, wt, in_hw)
-                    c1 = x.shape[3]
-                    if ctx.is_live(x):
-                        ctx.add_grad(x, dcat[..., :c1])
-                    if ctx.is_live(x2):       # (the skip connection of a frozen encoder is not)
-                        ctx.add_grad(x2, dcat[..., c1:])
-        ctx.tape.append(bwd)
-    if up_out is None:
-        return a
+
+def _norm_call(ctx, L, relu):
+    """The NormCall of layer call L with its mode: the one place that reads bn.training and, through _frozen_stats, the
+    requires_grad flags the forward goes by."""
+    bn, residual = L.bn, L.residual
+    if bn.training:
+        mode = INSTANCE if isinstance(bn, torch.nn.InstanceNorm2d) else BATCH
+    elif _frozen_stats(ctx, L.conv, bn):
+        # the running statistics normalise, nothing updates them, and the raw conv output is kept (no epilogue fold) with a
+        # train-mode layer's coefficient block, so everything downstream of a train-mode layer -- deferred activation, apply
+        # passes, the consumers' BatchNorm-backward partials -- works on it unchanged
+        mode = FROZEN
+    elif (L.path.epilogue and L.ldt == ctx.dtype and not (relu and residual is not None)
+            and (residual is None or residual.dtype == L.ldt)):
+        mode = FOLDED
+    else:
+        mode = EVAL
+    if mode == INSTANCE and (L.x2 is not None or residual is not None or L.ldt != torch.float32):
+        raise GdnError("train-mode InstanceNorm is implemented for the standalone fp32 ConvBlock / ConvTBlock only")
+    return NormCall(mode, bn, relu, L.path.dyb, L.ldt)
+
+
+def _loader_input(ctx, L):
+    """(the tensor the conv kernels read, the forward's loader keywords): a deferred upsampling or BatchNorm is applied by the
+    loader where the path has one (fft / wino); the other loaders go straight to LDS, so a deferred activation is written."""
+    x = L.x
+    if L.up is not None:
+        return L.up.src, dict(up2x=L.up.mode)
+    if not isinstance(x, BnOut):
+        return x, {}
+    if L.path.fused_in and _FUSE_TRAIN_BN:
+        return x.y, dict(in_affine=(x.co[0], x.co[1]), in_relu=x.relu)
+    return x.dense(ctx.dtype), {}
+
+
+def _conv_fwd(L, norm, kw):
+    """The convolution with what the norm mode asks of it: statistics (BATCH) or the folded epilogue (FOLDED).  Fills
+    norm.co / y / out and L.state."""
+    bn, mode = norm.bn, norm.mode
+    if mode != BATCH:
+        co = norm.co = _stored_coeffs(bn, mode == FROZEN)
+    if mode == FOLDED:
+        kw.update(affine=(co[0], co[1]), act=ops.ACT_RELU if norm.relu else ops.ACT_NONE, addsrc=L.residual)
+    y, st, L.state = L.path.fwd(L.xt, L.w, stats=mode == BATCH, **kw)
+    if mode == BATCH:
+        mom = 0.1 if bn.momentum is None else bn.momentum
+        norm.co = ops.bn_finalize_train(st, y.shape[0] * y.shape[1] * y.shape[2], bn.weight.data, bn.bias.data, bn.running_mean,
+                                        bn.running_var, mom, bn.eps, num_batches_tracked=bn.num_batches_tracked)
+        bn._gdn_stats_ver = getattr(bn, "_gdn_stats_ver", 0) + 1
+    norm.y = y
+    if mode in (BATCH, FROZEN):
+        norm.out = BnOut(y, norm.co, norm.relu)
+
+
+def _norm_apply(ctx, L, norm, defer, up_out):
+    """The layer's output from the raw conv output: (a, a upsampled x2 or None).  a is y itself (FOLDED), the BnOut (a deferred
+    train-mode fp32 layer without a residual: scale / shift / ReLU happen in the consumer's loader) or what the apply pass
+    writes -- on the bf16 path together with the upsampled tensor the caller asked for (up_out), in one kernel."""
+    y, co, residual, a_up = norm.y, norm.co, L.residual, None
+    if norm.mode == FOLDED:
+        return y, None
+    if (defer and norm.out is not None and residual is None and _FUSE_TRAIN_BN and L.ldt == torch.float32
+            and ctx.dtype == torch.float32):
+        return norm.out, None
+    if (up_out is not None and _FUSE_UP2X_BF16 and ctx.dtype == torch.bfloat16 and y.is_contiguous()
+            and (residual is None or residual.is_contiguous()) and y.shape[0] * 2 * y.shape[1] <= 65535
+            and y.shape[3] % 4 == 0):             # (the fused kernel's channel-vector width; other shapes take the two-pass form)
+        a, a_up = ops.bn_apply_up2x(y, co[0], co[1], norm.relu, residual, align_corners=bool(up_out), out_dtype=ctx.dtype)
+    else:
+        a = ops.bn_apply(y, co[0], co[1], norm.relu, residual, out_dtype=ctx.dtype)
+    if norm.out is not None and ctx.record and _FUSE_TRAIN_BN:
+        ctx.bn_src[id(a)] = norm.out
+    return a, a_up
+
+
+def _instance_fwd(ctx, L, norm):
+    """Conv -> train-mode InstanceNorm2d(affine=True, track_running_stats=True) -> [ReLU]: the standalone
+    ConvBlock / ConvTBlock(norm='Instance') of the reference (AE_model_unet.py:70-75, :88-92; R and G never build one).
+    Per-instance statistics are batch statistics of a batch of one, so the BatchNorm kernels run once per image on that
+    image's slice: the convolution writes image b's output with its sum / sum-of-squares partials, finalize (momentum 1 into
+    scratch buffers) yields that image's coefficients, mean and unbiased variance, apply / backward (_instance_bwd) use them;
+    the running statistics take the batch mean of the per-instance values (what F.instance_norm does).  A rarely used path:
+    direct kernels, B small launches."""
+    x, inorm = L.xt, norm.bn
+    B, C = x.shape[0], L.conv.out_channels
+    mom = 0.1 if inorm.momentum is None else inorm.momentum
+    norm.y, norm.co, outs = [], [], []
+    rm = torch.zeros((B, C), dtype=torch.float32, device=x.device)
+    rv = torch.ones((B, C), dtype=torch.float32, device=x.device)
+    for b in range(B):
+        yb, st, _ = L.path.fwd(x[b:b + 1], L.w, stats=True)
+        co = ops.bn_finalize_train(st, yb.shape[1] * yb.shape[2], inorm.weight.data, inorm.bias.data, rm[b], rv[b], 1.0, inorm.eps)
+        norm.y.append(yb)
+        norm.co.append(co)
+        outs.append(ops.bn_apply(yb, co[0], co[1], norm.relu, None, out_dtype=ctx.dtype))
+    if inorm.track_running_stats:
+        inorm.running_mean.mul_(1.0 - mom).add_(rm.mean(0), alpha=mom)
+        inorm.running_var.mul_(1.0 - mom).add_(rv.mean(0), alpha=mom)
+        # (torch's InstanceNorm2d leaves num_batches_tracked untouched: F.instance_norm does not take it)
+        inorm._gdn_stats_ver = getattr(inorm, "_gdn_stats_ver", 0) + 1
+    return torch.cat(outs, 0)
+
+
+def _instance_bwd(norm, da, dgamma, dbeta):
+    da = _dense(da)
+    dg = torch.zeros(da.shape[3], dtype=torch.float32, device=da.device)
+    db = torch.zeros_like(dg)
+    dys = []
+    for b, (yb, co) in enumerate(zip(norm.y, norm.co)):
+        dgb, dbb = torch.empty_like(dg), torch.empty_like(db)
+        dys.append(ops.bn_bwd(da[b:b + 1], yb, norm.bn.weight.data, co, norm.relu, dgb, dbb))
+        dg += dgb
+        db += dbb
+    if dgamma is not None:
+        dgamma.copy_(dg)
+        dbeta.copy_(db)
+    return torch.cat(dys, 0)
+
+
+def _trained(L, norm):
+    """(dgamma, dbeta, whether the conv weight gets a gradient, the parameters to report to ctx.grads_done) of a layer's
+    backward: the one place that decides which parameter gradients the layer writes.
+
+    When requires_grad is read.  The FORWARD reads it twice: _frozen_stats (is this eval-mode layer being trained: the norm
+    mode) and _conv_path's GDN_HINT_TRAIN (does the layer keep transform-domain state).  Everything here is read when the TAPE
+    REPLAYS, so a flag changed between forward and backward acts on the gradients written but not on the mode.  A FROZEN layer
+    writes exactly the gradients that are asked for (NULL pointers for the rest); every other layer with anything trainable
+    writes all three, as a train-mode layer always did, and one with nothing trainable writes none."""
+    params = (norm.bn.weight, norm.bn.bias, L.conv.weight)
+    rg = [p.requires_grad for p in params]
+    if norm.mode != FROZEN:
+        rg = [any(rg)] * 3
+    if rg[0] and norm.mode in (FOLDED, EVAL):
+        raise GdnError("backward through an eval-mode BatchNorm of a module in eval() is only implemented for layers "
+                       "with nothing to train (requires_grad False on the conv and BN parameters: the guide network of "
+                       "--latent_grad); to train on frozen statistics keep the module in train() and its norm layers in "
+                       "eval() (freeze_bn())")
+    return (params[0].grad if rg[0] else None, params[1].grad if rg[1] else None, rg[2],
+            tuple(p for p, r in zip(params, rg) if r))
+
+
+def _norm_bwd(norm, da, dgamma, dbeta):
+    """da -> (dy, extra keywords for the path's backward), by norm mode; dgamma / dbeta (or None) receive their gradients."""
+    mode, y, co, relu = norm.mode, norm.y, norm.co, norm.relu
+    if mode == INSTANCE:
+        return _instance_bwd(norm, da, dgamma, dbeta), {}
+    if mode in (FOLDED, EVAL):
+        return ops.bn_eval_bwd(da, y, co, (2 if mode == FOLDED else 1) if relu else 0, out_dtype=norm.ldt), {}
+    partial, norm.out.partial = norm.out.partial, None
+    # frequency-domain layer: dy has one reader (the dy transform), which applies the last pass of the BatchNorm backward
+    # while loading -- dy is never written
+    on_load = norm.dyb and _FUSE_TRAIN_BN and da.is_contiguous() and da.dtype == torch.float32
+    if mode == FROZEN and on_load:
+        # the sums only; pass 3 of the BatchNorm backward with k1 = k2 = 0 IS scale * dz: the transform applies scale and mask
+        ops.bn_frozen_bwd(da, y, co, relu, dgamma, dbeta, partial=partial, need_dy=False)
+        return da, dict(dyb=(y, co, ops.zeros((2, y.shape[3]), y.device), relu))
+    if mode == FROZEN:
+        return ops.bn_frozen_bwd(da, y, co, relu, dgamma, dbeta, out_dtype=norm.ldt, partial=partial), {}
+    if on_load:
+        return da, dict(dyb=(y, co, ops.bn_bwd_coeffs(da, y, co, relu, dgamma, dbeta, partial=partial), relu))
+    return ops.bn_bwd(da, y, norm.bn.weight.data, co, relu, dgamma, dbeta, out_dtype=norm.ldt, partial=partial), {}
+
+
+def _bnb(xin, slots, device):
+    """The `bnb` argument of a data gradient that is the final gradient of x = [relu](BN_train(xin.y)): (y, co, relu, partial),
+    with the [slots, 2, C] buffer the kernel's epilogue fills with the producer's BatchNorm-backward partial sums; None
+    where the kernel has no such epilogue (slots 0).  The caller stores bnb[3] as xin.partial once the kernel has run."""
+    if slots <= 0:
+        return None
+    return (xin.y, xin.co, xin.relu, torch.empty((slots, 2, xin.y.shape[3]), dtype=torch.float32, device=device))
+
+
+def _dgrad_into(ctx, op, dy, wt, x, x2=None, **kw):
+    """Direct data gradient of a convolution of x (or of cat(x, x2)) into ctx.grads.  A single input's pending gradient rides
+    along as addsrc and the result replaces it; the halves of a concatenated one are added to their inputs' gradients, each
+    only where it is live (the skip connection of a frozen encoder is not).  kw: in_hw (default: x's), bnb, up2x of op.dgrad."""
+    in_hw = kw.pop("in_hw", (x.shape[1], x.shape[2]))
+    if x2 is None:
+        ctx.grads[id(x)] = (x, op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(x, dy.dtype), **kw))
+        return
+    dcat = op.dgrad(dy, wt, in_hw)
+    c1 = x.shape[3]
+    if ctx.is_live(x):
+        ctx.add_grad(x, dcat[..., :c1])
+    if ctx.is_live(x2):
+        ctx.add_grad(x2, dcat[..., c1:])
+
+
+def _want_dx(ctx, L):
+    return L.need_dx and (ctx.wants_dx(L.x) or (L.x2 is not None and ctx.wants_dx(L.x2)))
+
+
+def _transform_grads(ctx, L, dy, extra, wtrain):
+    """Transform-domain backward: one transform of dy feeds both gradients; the forward's transformed input is reused for dw."""
+    gv = _grad_tap(L.conv) if wtrain else None
+    want_dx = _want_dx(ctx, L)
+    if gv is None and not want_dx:
+        return
+    xin, bnb, gx = L.xin, None, L.x                      # gx: the tensor whose gradient this layer's dx is
+    if xin is not None and want_dx and xin.y.dtype == torch.float32:
+        # this data gradient is the final gradient of x: emit the producer's BatchNorm-backward partial sums from the epilogue
+        bnb = _bnb(xin, L.path.bnb_slots(), dy.device)
+    if L.up is not None:
+        extra["up2x"] = L.up.mode                        # ... the low-resolution source of the deferred upsampling
+        gx = L.up.src
+    dx = L.path.bwd(dy, L.w, (L.x.shape[1], L.x.shape[2]), L.state, dw_tap=gv, need_dx=want_dx,
+                    addsrc=ctx.pop_grad_as(gx, L.ldt) if want_dx else None, bnb=bnb, **extra)
+    if want_dx:
+        ctx.grads[id(gx)] = (gx, dx)
+        if bnb is not None:
+            xin.partial = bnb[3]
+
+
+def _direct_dgrad(ctx, L, dy):
+    """Data gradient on the direct kernels.  bf16: the LDS-DMA ring kernel's epilogue emits the BatchNorm-backward partial sums
+    of x's producer when this is x's final gradient (we are its first consumer; the other consumers' gradients arrive as
+    addsrc), as the transform paths do for the fp32 layers.  up_in: x is an upsampled tensor whose producer kept the
+    low-resolution source -- a reflection-padded layer's fold pass writes dL/d(source) directly."""
+    op, x, xin, ldt = L.op, L.x, L.xin, L.ldt
+    wt = ops.transpose_taps(_w_tap(L.conv)[0], dtype=ldt)
+    if L.x2 is not None:
+        return _dgrad_into(ctx, op, dy, wt, x, L.x2)
+    bnb = None
+    if xin is not None and ldt == torch.bfloat16 and xin.y.dtype == ldt and _FUSE_TRAIN_BN and xin.y.is_contiguous():
+        bnb = _bnb(xin, op.dgrad_bnb_slots(x.shape[0], x.shape[1], x.shape[2], ldt), dy.device)
+    if L.up_in is not None and bnb is None and id(x) not in ctx.grads:
+        lo, mode = L.up_in
+        return _dgrad_into(ctx, op, dy, wt, lo, in_hw=(x.shape[1], x.shape[2]), up2x=mode)
+    _dgrad_into(ctx, op, dy, wt, x, bnb=bnb)
+    if bnb is not None:
+        xin.partial = bnb[3]
+
+
+def _layer_bwd(ctx, L, norm, da):
+    """The tape entry of one conv_bn_act call: norm backward, then both gradients of the convolution."""
+    dgamma, dbeta, wtrain, done = _trained(L, norm)
+    if L.residual is not None and ctx.is_live(L.residual):
+        ctx.add_grad(L.residual, da)
+    dy, extra = _norm_bwd(norm, da, dgamma, dbeta)
+    if L.path.bwd is not None:
+        _transform_grads(ctx, L, dy, extra, wtrain)
+    elif wtrain and L.path.c1_wgrad and dy.is_contiguous():
+        ops.conv_c1_wgrad(L.xt, dy, tap_view(L.conv.weight.grad, False), reflect=bool(L.reflect))
+    elif wtrain:
+        _wgrad_into(ctx, L.conv, L.xt, dy, L.x2)
+    if done:
+        ctx.grads_done(*done)
+    if L.path.bwd is None and _want_dx(ctx, L):
+        _direct_dgrad(ctx, L, dy)
+
+
+def _also_upsampled(ctx, a, a_up, align):
+    """(a, its x2 upsampling) for conv_bn_act(up_out=): a_up from the fused bf16 apply pass, with its tape entry, or upsample()."""
     if a_up is None:
-        return a, upsample(ctx, a, bool(up_out))
+        return a, upsample(ctx, a, align)
     ctx.claim(a)                         # (as upsample() does: the interpolation is this activation's first consumer)
     if ctx.record:
-        align = bool(up_out)
         ctx.up_src[id(a_up)] = (a, 2 if align else 1)
         ctx.mark_live(a_up, (a,))
 
@@ -894,6 +949,39 @@ def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_
     return a, a_up
 
 
+def conv_bn_act(ctx, x, conv, bn, relu, residual=None, x2=None, reflect=0, need_dx=True, defer=False, up_out=None):
+    """[relu](BN(conv(cat(x, x2)))) (+ residual): ConvBlock / ResidualBlock halves / ConvTBlock.
+
+    up_out (None, or the align_corners flag): the caller also wants F.interpolate(output, scale_factor=2, mode='bilinear') and
+    gets (output, upsampled) back -- on the bf16 path the BatchNorm-apply pass writes both (one kernel), on the fp32 path the
+    upsampled one is the deferred Up2x of upsample().
+
+    x may be a BnOut (the deferred activation of the previous layer) or an Up2x (a deferred upsampling): the fft / wino loaders
+    apply its scale / shift / ReLU or interpolate while loading; any other path materialises it first.  defer=True (the
+    caller guarantees a single consumer) returns this layer's output as a BnOut instead of running the BatchNorm-apply pass,
+    when the layer is a train-mode fp32 one without a residual."""
+    L = _layer_call(ctx, x, conv, bn, x2, reflect)
+    L.residual, L.need_dx = residual, need_dx
+    norm = _norm_call(ctx, L, relu)
+    L.xt, kw = _loader_input(ctx, L)
+    if norm.mode == INSTANCE:
+        a, a_up = _instance_fwd(ctx, L, norm), None
+    else:
+        _conv_fwd(L, norm, kw)
+        a, a_up = _norm_apply(ctx, L, norm, defer, up_out)
+    # the layer's input is an upsampled tensor whose producer kept the low-resolution source (up_out of that call)
+    L.up_in = ctx.up_src.get(id(L.x)) if L.path.up_fold else None
+    if ctx.record:
+        ctx.mark_live(a, (L.x, x2, residual), (conv.weight, bn.weight, bn.bias))
+
+        def bwd():
+            da = ctx.pop_grad(a)
+            if da is not None:
+                _layer_bwd(ctx, L, norm, da)
+        ctx.tape.append(bwd)
+    return a if up_out is None else _also_upsampled(ctx, a, a_up, bool(up_out))
+
+
 def conv_head_tanh(ctx, x, conv):
     """Final 9x9 (transposed) conv to one channel + tanh (AE_model_unet.py:362-363, :570-571).
     On the bf16 path only x is bf16: weights, the depth map and this layer's backward results are fp32 (the 1 <-> 64 channel
@@ -903,7 +991,6 @@ def conv_head_tanh(ctx, x, conv):
     w, tr = _w_tap(conv)
     out = op.fwd(x, w, act=ops.ACT_TANH)
     if ctx.record:
-        in_hw = (x.shape[1], x.shape[2])
         ctx.mark_live(out, (x,), (conv.weight,))
 
         def bwd():
@@ -924,11 +1011,9 @@ def conv_head_tanh(ctx, x, conv):
             if not ctx.is_live(x):
                 return                   # only the head trains: nothing below it needs a gradient
             if c1:
-                dx = ops.conv_c1_fwd(dpre, w, flip=not tr, addsrc=ctx.pop_grad(x))      # fp32, like the generic path's
-            else:
-                wt = ops.transpose_taps(w)
-                dx = op.dgrad(dpre, wt, in_hw, addsrc=ctx.pop_grad_as(x, torch.float32))
-            ctx.grads[id(x)] = (x, dx)
+                ctx.grads[id(x)] = (x, ops.conv_c1_fwd(dpre, w, flip=not tr, addsrc=ctx.pop_grad(x)))
+            else:                        # (fp32 like dpre, also for a bf16 x)
+                _dgrad_into(ctx, op, dpre, ops.transpose_taps(w), x)
         ctx.tape.append(bwd)
     return out
 
@@ -943,7 +1028,6 @@ def conv_plain(ctx, x, conv, x2=None):
     w, tr = _w_for(ctx, conv, ldt)
     y = op.fwd(x, w, x2=x2)
     if ctx.record:
-        in_hw = (x.shape[1], x.shape[2])
         ctx.mark_live(y, (x, x2), (conv.weight,))
 
         def bwd():
@@ -957,16 +1041,8 @@ def conv_plain(ctx, x, conv, x2=None):
                 _wgrad_into(ctx, conv, x, dy, x2)
                 ctx.grads_done(conv.weight)
             wt = ops.transpose_taps(_w_tap(conv)[0], dtype=ldt)
-            if x2 is None:
-                if ctx.wants_dx(x):
-                    ctx.grads[id(x)] = (x, op.dgrad(dy, wt, in_hw, addsrc=ctx.pop_grad_as(x, ldt)))
-            elif ctx.is_live(x) or ctx.is_live(x2):
-                dcat = op.dgrad(dy, wt, in_hw)
-                c1 = x.shape[3]
-                if ctx.is_live(x):
-                    ctx.add_grad(x, dcat[..., :c1])
-                if ctx.is_live(x2):
-                    ctx.add_grad(x2, dcat[..., c1:])
+            if ctx.wants_dx(x) if x2 is None else (ctx.is_live(x) or ctx.is_live(x2)):
+                _dgrad_into(ctx, op, dy, wt, x, x2)
         ctx.tape.append(bwd)
     return y
 

@@ -16,17 +16,16 @@ form bn_bwd_reduce / _apply, bn_finalize_train).
 
 usage: freeze_bn_time.py [steps per window = 30] [rounds = 3] [--dtype fp32|bf16|both] [--only batch-stat|frozen] [--batch 20]
                          [--out FILE]"""
-import collections
 import json
 import pathlib
 import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent.parent
-sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "gdn-pytorch_amd"))
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "gdn-pytorch_amd")); sys.path.insert(0, str(ROOT / "tests"))
 import torch
 import gdn_amd.AE_model_unet as M
-from gdn_amd import _lib
+from libcalls import count_library_calls
 from gdn_amd import utils as U
 from gdn_amd.optim import Adam
 from gdn_amd.synthetic import SyntheticLoader
@@ -53,26 +52,6 @@ dev = torch.device("cuda:0")
 FORMS = [f for f in ("batch-stat", "frozen") if only in (None, f)]
 BN_CALLS = ("gdn_bn_finalize_train", "gdn_bn_apply", "gdn_bn_apply_up2x", "gdn_bn_bwd", "gdn_bn_bwd_coeffs", "gdn_bn_eval_coeffs",
             "gdn_bn_eval_bwd", "gdn_bn_frozen_coeffs", "gdn_bn_frozen_bwd")
-
-
-def count_library_calls(fn):
-    """Calls into the C ABI (status-returning entry points: the ones that launch) while fn() runs, by name."""
-    n = collections.Counter()
-    saved = {}
-    for name in _lib._STATUS_FUNCS - {"gdn_conv_out_dims", "gdn_fftconv_cgemm_shape"}:      # (these two launch nothing)
-        f = getattr(_lib.lib, name)
-        saved[name] = f
-
-        def counted(*a, _f=f, _n=name):
-            n[_n] += 1
-            return _f(*a)
-        setattr(_lib.lib, name, counted)
-    try:
-        fn()
-    finally:
-        for name, f in saved.items():
-            setattr(_lib.lib, name, f)
-    return n
 
 
 def build(dtype, frozen, sd):
@@ -133,7 +112,7 @@ for dtype in (("fp32", "bf16") if dtypes == "both" else (dtypes,)):
             times[f].append(window(runs[f], steps))
     rec = {}
     for f in FORMS:
-        calls = count_library_calls(runs[f])
+        calls, _ = count_library_calls(runs[f])
         torch.cuda.synchronize()
         rec[f] = {"median_ms": round(statistics.median(times[f]), 3), "min_ms": round(min(times[f]), 3),
                   "max_ms": round(max(times[f]), 3), "library_calls_per_step": sum(calls.values()),

@@ -2,7 +2,6 @@
 per-tensor launches it replaces and against torch.optim.Adam, its launch count, the pruned backward against the unpruned one,
 what stays bit for bit where it was under --freeze / --lr_mult 0, and the flags end to end through GDN_main.run with --graph
 and --resume."""
-import collections
 import copy
 import os
 
@@ -10,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from libcalls import count_library_calls
 from oracle import gdn_oracle as O
 from test_hip_kernels import close
 
@@ -19,28 +19,6 @@ H, W = 16, 32
 NETS = ["AutoEncoder_DtoD", "AutoEncoder_2"]
 OPT_CALLS = ("gdn_adam_step", "gdn_adam_step_dev", "gdn_adam_step_dev_guarded", "gdn_grad_sumsq", "gdn_grad_guard_finalize",
              "gdn_ema_update", "gdn_adam_step_seg", "gdn_grad_sumsq_seg", "gdn_ema_update_seg")
-
-
-def count_library_calls(fn):
-    """Calls into the C ABI (status-returning entry points: the ones that launch) while fn() runs: (Counter by name, the
-    names in call order).  The counter of tests/diag/freeze_bn_time.py."""
-    from gdn_amd import _lib
-    n, order, saved = collections.Counter(), [], {}
-    for name in _lib._STATUS_FUNCS - {"gdn_conv_out_dims", "gdn_fftconv_cgemm_shape"}:      # (these two launch nothing)
-        f = getattr(_lib.lib, name)
-        saved[name] = f
-
-        def counted(*a, _f=f, _n=name):
-            n[_n] += 1
-            order.append(_n)
-            return _f(*a)
-        setattr(_lib.lib, name, counted)
-    try:
-        fn()
-    finally:
-        for name, f in saved.items():
-            setattr(_lib.lib, name, f)
-    return n, order
 
 
 @pytest.fixture(scope="module")
