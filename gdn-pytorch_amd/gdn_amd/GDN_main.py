@@ -63,6 +63,12 @@ pixel; the Sobel / smoothness / latent terms and the progress lines (``output_lo
 ``--graph``, ``--resume``, ``--accum_steps``, the gradient guard and bf16 run on it unchanged.  Each rank takes the statistics
 of its own shard; the flag is not stored in ``train_state.pt``: a resumed run repeats it.  ``--loss berhu`` is the run
 without the flag.
+``--eval_protocol standard`` evaluates KITTI under the Eigen-split protocol of the literature in the
+reference protocol's place, in the test modes and in the per-epoch validation: metric depth (``--depth_scale`` metres at +1),
+the ``--min_depth`` / ``--max_depth`` cap, the ``--eval_crop {garg,eigen,none}`` box, optional ``--median_scaling`` and
+``--flip_test``, nine metrics averaged per image.  ``--eval_gt_list FILE`` (test modes with ``--real_test``) takes the ground
+truth from 16-bit KITTI depth maps at their native size; the prediction is resampled to each map inside the metrics kernel.
+The result line states the protocol's parameters.  ``--eval_protocol reference`` is the run without the flag.
 """
 import contextlib
 import io
@@ -78,7 +84,7 @@ from .AE_model_unet import AutoEncoder, AutoEncoder_2, AutoEncoder_DtoD
 from .optim import Adam
 from .synthetic import SyntheticLoader
 from .trainer import (load_checkpoint, load_training_state, lr_schedule_of, read_training_state, train_AE_DtoD, train_AE_RtoD,
-                      validate, validate_NYU)
+                      validate, validate_NYU, validate_std)
 
 TEST_MODES = ('DtoD_test', 'RtoD_test')
 
@@ -243,6 +249,33 @@ def _check_loss(args, train_loader=None):
                            "takes the statistics of its own shard (drop one of the two flags)")
 
 
+def _check_eval(args):
+    """--eval_protocol standard and its flags; checked before anything touches the GPU."""
+    spec = option.eval_spec(args)
+    if not spec["standard"]:
+        given = option.eval_flags_given(args)
+        if given:
+            raise RuntimeError("%s set(s) the Eigen-split evaluation, which --eval_protocol standard selects (add it, or drop "
+                               "the flag)" % ", ".join("--" + k for k in given))
+        return
+    if args.dataset != "KITTI":
+        raise RuntimeError("--eval_protocol standard is the KITTI Eigen-split protocol; --dataset %s keeps its own metrics "
+                           "(drop the flag)" % args.dataset)
+    if not (spec["min_depth"] > 0.0 and spec["max_depth"] > spec["min_depth"] and spec["max_depth"] != float("inf")):
+        raise RuntimeError("--min_depth %g / --max_depth %g: the cap needs 0 < min_depth < max_depth" % (spec["min_depth"],
+                                                                                                       spec["max_depth"]))
+    if not (spec["depth_scale"] > 0.0 and spec["depth_scale"] != float("inf")):
+        raise RuntimeError("--depth_scale %g is not a positive number" % spec["depth_scale"])
+    if spec["gt_list"]:
+        if args.mode not in TEST_MODES:
+            raise RuntimeError("--eval_gt_list is the ground truth of a test run; --mode %s validates on the loader's "
+                               "(use --mode DtoD_test / RtoD_test)" % args.mode)
+        if not args.real_test:
+            raise RuntimeError("--eval_gt_list lists the ground truth of the Eigen test split: add --real_test")
+        if not os.path.isfile(spec["gt_list"]):
+            raise FileNotFoundError("--eval_gt_list %r: no such file" % (spec["gt_list"],))
+
+
 def _check_freeze_bn(args):
     """--freeze_bn trains on the stored running statistics; checked before anything touches the GPU."""
     if not getattr(args, "freeze_bn", False):
@@ -360,6 +393,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_schedule(args)
     _check_loss(args, train_loader)
     _check_freeze_bn(args)
+    _check_eval(args)
     _check_partial(args, args.height, args.width)
     rank, local_rank, world = D.env_rank()
     if world == 1 and "HIP_VISIBLE_DEVICES" not in os.environ and not torch.cuda.is_initialized():
@@ -473,6 +507,18 @@ def run(args, train_loader=None, val_loader=None):
             load_checkpoint(model, ckpt)
         model.eval()
         saver = ImageSaver(args.result_dir) if args.img_save and rank == 0 else None
+        spec = option.eval_spec(args)
+        if spec["standard"]:
+            # the Eigen-split protocol; --eval_gt_list: the 16-bit maps at their native size
+            gt16 = None
+            if spec["gt_list"]:
+                from .datasets import EigenGt16
+                gt16 = EigenGt16(spec["gt_list"], args.data)
+            errors, left_out, names = validate_std(args, val_loader, model, 0, logger, args.mode, on_batch=saver, gt16=gt16)
+            if rank == 0:
+                print("Results: " + ", ".join("%s %.4f" % (n, e) for n, e in zip(names, errors)) +
+                      " [standard: %s; %d image(s) left out]" % (option.eval_describe(spec), left_out))
+            return errors
         evaluate = validate_NYU if args.dataset == "NYU" else validate
         errors, min_errors, names = evaluate(args, val_loader, model, 0, logger, args.mode, on_batch=saver)
         if rank == 0:

@@ -124,6 +124,10 @@ _SIGS = {
     "gdn_depth_metrics_nyu": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _P, _P, _sz, _P]),
     "gdn_depth_metrics_make3d_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "gdn_depth_metrics_make3d": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _P, _P, _sz, _P]),
+    "gdn_depth_metrics_std_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "gdn_depth_metrics_std": (c_int32, [_P, _i32, _i32, _i32, _P, _P, _i32, _i32, _i32, _f, _f, _f, _i32, _P, _P, _sz, _P]),
+    "gdn_flip_w": (c_int32, [_P, _i64, _i32, _P, _P]),
+    "gdn_flip_mean": (c_int32, [_P, _P, _i64, _i32, _P, _P]),
     "gdn_crop_normalize": (c_int32, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "gdn_bytescale_u8": (c_int32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
     "gdn_nyu_augment_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
@@ -156,8 +160,8 @@ EXPORTS = tuple(_SIGS)
 # The C ABI revision these signatures (and ConvGeom's layout) describe: gdn_version() of the library must match exactly --
 # a stale build would take the arguments apart differently.  (gdn_grad_accumulate joined revision 223 without a new number:
 # _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
-# and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule and gdn_silog_masked, for the
-# same reason.)
+# and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule, gdn_silog_masked and the
+# evaluation entry points gdn_depth_metrics_std*, gdn_flip_w and gdn_flip_mean, for the same reason.)
 ABI_VERSION = 223
 
 

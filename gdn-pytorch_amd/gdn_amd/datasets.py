@@ -122,6 +122,52 @@ class TestFolder:
         return len(self.samples)
 
 
+class EigenGt16:
+    """--eval_gt_list: the ground truth of the Eigen split at its native size.  list_file names one 16-bit single-channel
+    depth PNG per test sample (first token of every line; taken as written if that path exists, else relative to root), in
+    the order of the test lists.  A sample is the [h, w] uint16 array as stored, WITHOUT conversion: metres x 256, 0 where
+    the LiDAR has no return (the official KITTI format)."""
+
+    def __init__(self, list_file, root=None):
+        self.root = pathlib.Path(root) if root is not None else pathlib.Path(list_file).resolve().parent
+        with open(list_file) as f:
+            toks = [line.split()[0] for line in f if line.split()]
+        self.samples = [pathlib.Path(t) if pathlib.Path(t).exists() else self.root / t for t in toks]
+
+    def __getitem__(self, index):
+        from PIL import Image
+        path = self.samples[index]
+        try:
+            with Image.open(path) as im:
+                mode = im.mode
+                a = np.asarray(im) if mode.startswith("I;16") else None
+        except Exception as e:
+            raise GdnError("cannot decode %s: %s" % (path, e)) from e
+        if a is None or a.ndim != 2:
+            raise GdnError("%s is not a single-channel 16-bit image (mode %s): --eval_gt_list takes KITTI depth maps, "
+                           "uint16 = metres x 256" % (path, mode))
+        return np.ascontiguousarray(a, dtype=np.uint16)
+
+    def __len__(self):
+        return len(self.samples)
+
+
+def assemble_gt16(maps, device):
+    """B uint16 maps of any sizes -> ([B,Hmax,Wmax] uint16 on `device`, image b in the top-left corner, zero padding;
+    [(h, w), ...]): one pinned staging buffer, one host-to-device copy."""
+    sizes = [tuple(int(v) for v in m.shape) for m in maps]
+    if not sizes or any(m.dtype != np.uint16 or m.ndim != 2 for m in maps):
+        raise GdnError("assemble_gt16: a non-empty list of [h, w] uint16 arrays")
+    device = torch.device(device)
+    pool = torch.zeros((len(maps), max(h for h, _ in sizes), max(w for _, w in sizes)), dtype=torch.uint16)
+    if device.type == "cuda":
+        pool = pool.pin_memory()
+    view = pool.numpy()
+    for b, m in enumerate(maps):
+        view[b, :m.shape[0], :m.shape[1]] = m
+    return (pool.to(device, non_blocking=True) if device.type == "cuda" else pool), sizes
+
+
 class NYUdataset:
     """NYU Depth v2 (datasets_list.py:366-444).  train=False: root/test/test_depths/*.png (16-bit depth) paired in sorted
     order with root/test/test_colors/*.png, in that order (the reference shuffles unless --img_test).  train=True:

@@ -1038,6 +1038,61 @@ def depth_metrics_make3d(gt_np, gt, pred):
     return err
 
 
+GT_METRES, GT_U16, GT_UNIT = 0, 1, 2        # gt_kind of gdn_depth_metrics_std
+
+
+def depth_metrics_std(gt, gt_kind, boxes, pred, depth_scale=80.0, min_depth=1e-3, max_depth=80.0, median_scaling=False):
+    """gdn_depth_metrics_std: gt [B,Hmax,Wmax] (float32 for kind 0 / 2, uint16 for kind 1), boxes int32 [B,6] =
+    (h0, w0, y1, y2, x1, x2) and pred [B,1,H,W] float32, all dense and on the GPU -> device float64 [B,12] =
+    (n, ratio, abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, log10, silog, 0) per image.  No sync."""
+    want = torch.uint16 if gt_kind == GT_U16 else torch.float32
+    if gt_kind not in (GT_METRES, GT_U16, GT_UNIT):
+        raise GdnError("depth_metrics_std: gt_kind %r is not 0 (metres), 1 (uint16 / 256) or 2 ([-1, 1])" % (gt_kind,))
+    if not (gt.is_cuda and gt.dim() == 3 and gt.dtype == want and gt.is_contiguous()):
+        raise GdnError("depth_metrics_std: gt of kind %d must be a dense [B,Hmax,Wmax] %s tensor on the GPU" % (gt_kind, want))
+    if not (pred.is_cuda and pred.dim() == 4 and pred.shape[1] == 1 and pred.dtype == torch.float32 and pred.is_contiguous()):
+        raise GdnError("depth_metrics_std: pred must be a dense [B,1,H,W] float32 tensor on the GPU")
+    B, _, H, W = pred.shape
+    if gt.shape[0] != B or not (boxes.is_cuda and boxes.dtype == torch.int32 and tuple(boxes.shape) == (B, 6) and
+                                boxes.is_contiguous()):
+        raise GdnError("depth_metrics_std: gt and boxes (int32 [B,6] on the GPU) must hold pred's %d images" % B)
+    Hmax, Wmax = gt.shape[1], gt.shape[2]
+    nb = int(lib.gdn_depth_metrics_std_workspace_bytes(B, Hmax, Wmax))
+    ws = workspace(nb, pred.device, "metrics_std")
+    rows = torch.empty((B, 12), dtype=torch.float64, device=pred.device)
+    lib.gdn_depth_metrics_std(_p(gt), int(gt_kind), Hmax, Wmax, _p(boxes), _p(pred), B, H, W, float(depth_scale),
+                              float(min_depth), float(max_depth), 1 if median_scaling else 0, _p(rows), _p(ws), nb, stream())
+    return rows
+
+
+def _flip_rows(what, *ts):
+    a = ts[0]
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() >= 1 and t.shape == a.shape):
+            raise GdnError("%s: dense float32 tensors of one shape on the GPU" % what)
+    W = a.shape[-1]
+    return a.numel() // W, W
+
+
+def flip_w(src):
+    """src[..., ::-1] of a dense float32 device tensor (gdn_flip_w), as a new tensor."""
+    rows, W = _flip_rows("flip_w", src)
+    dst = torch.empty_like(src)
+    lib.gdn_flip_w(_p(src), rows, W, _p(dst), stream())
+    return dst
+
+
+def flip_mean(a, b, out=None):
+    """(a + b.flip(-1)) * 0.5 bitwise (gdn_flip_mean): the merge of the flip test-time augmentation.  out: a new tensor, or
+    a itself."""
+    out = torch.empty_like(a) if out is None else out
+    rows, W = _flip_rows("flip_mean", a, b, out)
+    if out.data_ptr() == b.data_ptr():
+        raise GdnError("flip_mean: out may be a, not b")
+    lib.gdn_flip_mean(_p(a), _p(b), rows, W, _p(out), stream())
+    return out
+
+
 def center_crop_offsets(in_h, in_w, out_h, out_w):
     """CenterCrop.get_params (transform_list.py:260-261): Python's round, i.e. half to even."""
     return int(round((in_h - out_h) / 2.)), int(round((in_w - out_w) / 2.))

@@ -2,7 +2,8 @@
 plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global_berhu, --resident, --rtod_arch,
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
 --graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm, --warmup_steps, --lr_schedule,
---lr_floor, --loss, --silog_lambda, --silog_weight, --silog_floor, --silog_mask).
+--lr_floor, --loss, --silog_lambda, --silog_weight, --silog_floor, --silog_mask, --eval_protocol, --eval_crop, --min_depth,
+--max_depth, --depth_scale, --median_scaling, --flip_test, --eval_gt_list).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -211,7 +212,62 @@ def build_parser():
     p.add_argument('--silog_mask', default=None, choices=['dense', 'lidar'],
                    help='with --loss silog: dense = every pixel whose ground truth is above the floor; lidar = only pixels '
                         'inside the Garg box that carry a LiDAR return (KITTI only) (when not given: dense)')
+    p.add_argument('--eval_protocol', default='reference', choices=['reference', 'standard'],
+                   help='how KITTI is evaluated (test modes and the per-epoch validation).  reference: the reference\'s '
+                        'compute_errors, as ever.  standard: the Eigen-split protocol of the literature (DESIGN.md 3.12) -- '
+                        'metric depth, the --min_depth / --max_depth cap, the --eval_crop box, evaluated at the ground '
+                        'truth\'s own resolution, nine metrics averaged per image')
+    # (the flags below default to None so that one given without --eval_protocol standard can be refused; eval_spec()
+    # resolves them: garg, 1e-3, 80, 80)
+    p.add_argument('--eval_crop', default=None, choices=['garg', 'eigen', 'none'],
+                   help='with --eval_protocol standard: the evaluation crop (when not given: garg)')
+    p.add_argument('--min_depth', type=float, default=None, metavar='M',
+                   help='with --eval_protocol standard: ground truth at or below M metres is left out and the prediction is '
+                        'clamped to it, > 0 (when not given: 1e-3)')
+    p.add_argument('--max_depth', type=float, default=None, metavar='M',
+                   help='with --eval_protocol standard: the cap, likewise (when not given: 80)')
+    p.add_argument('--depth_scale', type=float, default=None, metavar='M',
+                   help='with --eval_protocol standard: the depth in metres that the network\'s +1 stands for (when not '
+                        'given: 80)')
+    p.add_argument('--median_scaling', action='store_true',
+                   help='with --eval_protocol standard: scale each prediction by median(gt) / median(prediction) over its '
+                        'valid pixels before the metrics')
+    p.add_argument('--flip_test', action='store_true',
+                   help='with --eval_protocol standard: evaluate the mean of the prediction and the mirrored prediction of '
+                        'the mirrored input (two forwards per batch); --img_save then writes the merged map')
+    p.add_argument('--eval_gt_list', type=str, default=None, metavar='FILE',
+                   help='with --eval_protocol standard, a test mode and --real_test: one 16-bit KITTI depth PNG (metres x '
+                        '256) per test sample, at its native size, as the ground truth; the network\'s inputs stay what '
+                        'the test lists feed it')
     return p
+
+
+EVAL_DEFAULTS = {'eval_crop': 'garg', 'min_depth': 1e-3, 'max_depth': 80.0, 'depth_scale': 80.0}
+EVAL_SWITCHES = ('median_scaling', 'flip_test', 'eval_gt_list')
+
+
+def eval_spec(args):
+    """The evaluation protocol as a dict: 'standard' (False: the reference's compute_errors, as ever) and, flags not given
+    at their defaults, 'crop', 'min_depth', 'max_depth', 'depth_scale', 'median_scaling', 'flip_test', 'gt_list'."""
+    v = {k: d if getattr(args, k, None) is None else getattr(args, k) for k, d in EVAL_DEFAULTS.items()}
+    return {'standard': (getattr(args, 'eval_protocol', None) or 'reference') == 'standard', 'crop': v['eval_crop'],
+            'min_depth': float(v['min_depth']), 'max_depth': float(v['max_depth']), 'depth_scale': float(v['depth_scale']),
+            'median_scaling': bool(getattr(args, 'median_scaling', False)), 'flip_test': bool(getattr(args, 'flip_test', False)),
+            'gt_list': getattr(args, 'eval_gt_list', None)}
+
+
+def eval_flags_given(args):
+    """The names of the --eval_protocol standard flags the command line sets."""
+    return [k for k in EVAL_DEFAULTS if getattr(args, k, None) is not None] + \
+           [k for k in EVAL_SWITCHES if getattr(args, k, None)]
+
+
+def eval_describe(spec):
+    """What a result line of the standard protocol says about itself."""
+    return "crop %s, cap %g-%g m, depth_scale %g m, median scaling %s, flip %s, gt %s" % (
+        spec['crop'], spec['min_depth'], spec['max_depth'], spec['depth_scale'], 'on' if spec['median_scaling'] else 'off',
+        'on' if spec['flip_test'] else 'off',
+        '16-bit maps at native size (%s)' % spec['gt_list'] if spec['gt_list'] else "the loader's, at the network's size")
 
 
 SILOG_DEFAULTS = {'silog_lambda': 0.85, 'silog_weight': 10.0, 'silog_floor': 0.0125, 'silog_mask': 'dense'}

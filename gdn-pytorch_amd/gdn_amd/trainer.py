@@ -23,8 +23,9 @@ from . import distributed as D
 from . import option
 from . import tracing
 from . import utils as U
-from .calculate_error import (ERROR_NAMES, ERROR_NAMES_MAKE3D, ERROR_NAMES_NYU, compute_errors_device,
-                              compute_errors_Make3D_device, compute_errors_NYU_device)
+from .calculate_error import (ERROR_NAMES, ERROR_NAMES_MAKE3D, ERROR_NAMES_NYU, ERROR_NAMES_STD, compute_errors_device,
+                              compute_errors_Make3D_device, compute_errors_NYU_device, compute_errors_std_device,
+                              mean_errors_std)
 
 
 def _is_main():
@@ -53,11 +54,12 @@ def _save_checkpoint(model, path, optimizer=None):
 
 def _validate_epoch(args, val_loader, model, optimizer, epoch, logger):
     """The per-epoch validation of both training loops; on the averaged weights where the optimizer keeps them."""
+    evaluate = validate_std if option.eval_spec(args)["standard"] else validate       # --eval_protocol standard
     if _averaging(optimizer):
         with optimizer.averaged_weights():
-            errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
+            errors, _, names = evaluate(args, val_loader, model, epoch, logger, args.mode)
     else:
-        errors, _, names = validate(args, val_loader, model, epoch, logger, args.mode)
+        errors, _, names = evaluate(args, val_loader, model, epoch, logger, args.mode)
     if _is_main():
         print(('(averaged weights)' if _averaging(optimizer) else '') + ' * Avg ' +
               ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
@@ -712,6 +714,48 @@ def validate(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None)
     """KITTI: compute_errors (Godard crop) per batch, trainer.py:17-87."""
     return _evaluate(val_loader, model, mode, lambda s, g, o: compute_errors_device(s, g, o, crop=True), ERROR_NAMES,
                      on_batch)
+
+
+def validate_std(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None, gt16=None):
+    """KITTI under the Eigen-split protocol (--eval_protocol standard): metric depth, the --min_depth /
+    --max_depth cap, the --eval_crop box at the ground truth's own resolution, optional --median_scaling and --flip_test.
+    The ground truth is the loader's third tensor (in [-1, 1], at the network's size) or, with gt16 (datasets.EigenGt16,
+    one map per sample in loader order), the 16-bit maps at their native size.  The per-image rows stay on the device; one
+    D2H copy at the end.  Returns (the nine metrics as the float64 mean over ALL images with a valid pixel -- not the mean
+    of batch means --, the number of images left out, names); rank 0 prints that number whenever it is not 0."""
+    from . import ops
+    from .datasets import assemble_gt16
+    dev = _device_of(model)
+    opt = option.eval_spec(args)
+    rows, k = [], 0
+    if gt16 is not None and len(gt16) != len(val_loader.ds):
+        raise U.GdnError("--eval_gt_list names %d maps, the test split has %d samples" % (len(gt16), len(val_loader.ds)))
+    for depth, img, depth_np in val_loader:
+        depth, img, depth_np = _to_dev(depth, dev), _to_dev(img, dev), _to_dev(depth_np, dev)
+        x = img if mode in ('RtoD', 'RtoD_test', 'RtoD_single') else depth
+        with torch.no_grad():
+            out = model(x, istrain=False)
+            if opt["flip_test"]:
+                out = out.detach().float().contiguous()
+                mirrored = model(ops.flip_w(x.float().contiguous()), istrain=False).detach().float().contiguous()
+                out = ops.flip_mean(out, mirrored, out=out)
+        B = out.shape[0]
+        if gt16 is None:
+            gt, sizes = depth_np, None
+        else:
+            gt, sizes = assemble_gt16([gt16[k + i] for i in range(B)], dev)
+        k += B
+        rows.append(compute_errors_std_device(gt, sizes, out, crop=opt["crop"], min_depth=opt["min_depth"],
+                                              max_depth=opt["max_depth"], depth_scale=opt["depth_scale"],
+                                              median_scaling=opt["median_scaling"]))
+        if on_batch is not None:
+            on_batch(depth, img, depth_np, out)
+    if not rows:
+        return [float('nan')] * len(ERROR_NAMES_STD), 0, ERROR_NAMES_STD
+    errors, left_out = mean_errors_std(torch.cat(rows).cpu())
+    if left_out and _is_main():
+        print("=> standard protocol: %d of %d images have no valid pixel and are left out of the mean" % (left_out, k))
+    return errors, left_out, ERROR_NAMES_STD
 
 
 def validate_NYU(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None):

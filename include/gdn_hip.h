@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn); gdn_silog_masked (--loss silog; gdn_loss_workspace_bytes grows by a third partial array, which every caller queries).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn); gdn_silog_masked (--loss silog; gdn_loss_workspace_bytes grows by a third partial array, which every caller queries); gdn_depth_metrics_std*, gdn_flip_w, gdn_flip_mean (--eval_protocol standard, --flip_test).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 /* The GDN_HINT_* bits (below) this library acts on.  A binding that sets a bit that CHANGES WHAT IS COMPUTED (GDN_HINT_FLIP_TAPS)
@@ -612,6 +612,47 @@ int gdn_depth_metrics_nyu(const float* gt, const float* pred, int32_t B, int32_t
 size_t gdn_depth_metrics_make3d_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int gdn_depth_metrics_make3d(const float* gt_np, const float* gt, const float* pred, int32_t B, int32_t H, int32_t W,
                              float* errors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Metric KITTI evaluation under the Eigen-split protocol (--eval_protocol standard).  No counterpart in
+ * the reference, whose compute_errors (gdn_depth_metrics above) stretches both maps to their own min / max; its intent is
+ * the commented-out block of calculate_error.py:59-76.
+ *   gt     [B][Hmax][Wmax]; image b is the top-left h0 x w0 corner, the padding is never read.  gt_kind 0: float32 metres;
+ *          1: uint16, metres = v / 256 (the official KITTI PNG, 0 = no return); 2: float32 in [-1, 1] as the loaders
+ *          yield it, metres = (float)(((double)v + 1) / 2 * depth_scale)
+ *   boxes  device int32 [B][6] = {h0, w0, y1, y2, x1, x2}: size and crop box of each image, from the host, taken as
+ *          given (0 <= y1 <= y2 <= h0, likewise in x); h0 / w0 beyond the pool are held to Hmax / Wmax
+ *   pred   [B][1][H][W] float32 in [-1, 1]
+ * Per pixel (y, x) of the h0 x w0 image, float64 without FMA contraction unless stated: g = ground truth in metres (a
+ * float32 value, widened); valid iff g > min_depth, g < max_depth, y1 <= y < y2, x1 <= x < x2.  The prediction at the
+ * ground truth's resolution is bilinear with half-pixel centres and edge clamping -- per axis
+ * s = max((i + 0.5) * ((double)n_in / n_out) - 0.5, 0), i0 = min(floor(s), n_in - 1), i1 = min(i0 + 1, n_in - 1),
+ * w = s - i0; t = (top0 * (1 - wx) + top1 * wx) * (1 - wy) + (bot0 * (1 - wx) + bot1 * wx) * wy over ((double)pred + 1) / 2
+ * of the four neighbours -- then p = max((float)(t * depth_scale), 0), rounded to float32 once (NaN propagates; the
+ * identity when h0 x w0 == H x W).  median_scaling: ratio = median(valid g) / median(valid p) with numpy's median (the mean
+ * of the two middle values of an even count; an exact selection over the float32 bit patterns), else ratio = 1;
+ * p <- min(max(p * ratio, min_depth), max_depth), NaN stays NaN.  Over the n valid pixels: abs_rel = mean(|g-p|/g),
+ * sq_rel = mean((g-p)^2/g), rmse = sqrt(mean((g-p)^2)), rmse_log = sqrt(mean((ln g - ln p)^2)),
+ * a_k = count(max(g/p, p/g) < 1.25^k) / n, log10 = mean(|log10 g - log10 p|),
+ * silog = 100 sqrt(max(mean(e^2) - mean(e)^2, 0)) with e = ln p - ln g.
+ *   per_image  device [B][12] doubles = {n, ratio, abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, log10, silog, 0};
+ *              n == 0: {0, NaN x 10, 0}
+ * An image is split over several workgroups; partial sums are float64 and combined in a fixed order, the select's
+ * histograms are summed with integer atomics, there is no floating-point atomic: two calls on the same inputs give the same
+ * 96 B bytes.  One memset node and 3 kernel launches, 6 with median scaling.  min_depth > 0, max_depth > min_depth,
+ * depth_scale > 0, all finite, gt_kind in 0..2, Hmax x Wmax and H x W below 2^31, B <= 65535 (GDN_ERR_BAD_ARG).
+ * ---------------------------------------------------------------------- */
+size_t gdn_depth_metrics_std_workspace_bytes(int32_t B, int32_t Hmax, int32_t Wmax);
+int gdn_depth_metrics_std(const void* gt, int32_t gt_kind, int32_t Hmax, int32_t Wmax,
+                          const int32_t* boxes, const float* pred, int32_t B, int32_t H, int32_t W,
+                          float depth_scale, float min_depth, float max_depth, int32_t median_scaling,
+                          double* per_image, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Flip test-time augmentation (--flip_test), float32 rows of W elements, rows = B * C * H:
+ * gdn_flip_w: dst[r][x] = src[r][W-1-x] (dst must not be src);
+ * gdn_flip_mean: out[r][x] = 0.5f * (a[r][x] + b[r][W-1-x]), bitwise (a + b.flip(-1)) * 0.5; out may be a, not b. */
+int gdn_flip_w(const float* src, int64_t rows, int32_t W, float* dst, void* stream);
+int gdn_flip_mean(const float* a, const float* b, int64_t rows, int32_t W, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
  * NYU validation transform (GDN_main.py:41-47: CenterCrop, ArrayToTensor,
