@@ -807,6 +807,76 @@ __global__ __launch_bounds__(256) void adam_seg_kernel(f32x4* __restrict__ p, co
         p[i] = f32x4{pe[0], pe[1], pe[2], pe[3]};
     }
 }
+// ---- decoupled weight decay (AdamW; include/gdn_hip.h).  The gradient carries no decay term, so the moments
+// never see it; the decay dec * p, dec = float(lr * wd) with the product in double, is added to the Adam term q and the sum is
+// subtracted from the weight ONCE: p (1 - lr wd) in float32 loses the decay altogether at this project's rates (1 - 1e-8
+// rounds to 1).  One element, every product, sum, quotient and root rounded on its own but the one fma: all four adamw kernels
+// go through it, so their bits agree, and with dec = 0 it is adam_update1 at wd = 0.
+// dec = (float)((double)lr * (double)wd): the double product of two floats is exact (48 bits), so its one rounding to float IS
+// the IEEE float product -- written as that, which keeps double-rate instructions out of a loop that streams at HBM speed.
+__device__ __forceinline__ float adamw_dec(float lr, float wd) { return lr * wd; }
+__device__ __forceinline__ void adamw_update1(float& p, float g, float& m, float& v, float step, float b1, float b2, float eps,
+                                              float dec, float bc2s, float gscale) {
+#pragma clang fp contract(off)
+    const float pi = p;
+    const float gi = g * gscale;
+    const float mi = b1 * m + (1.f - b1) * gi;
+    const float vi = b2 * v + (1.f - b2) * gi * gi;
+    m = mi; v = vi;
+    const float q = step * mi / (sqrtf(vi) / bc2s + eps);
+    p = pi - fmaf(dec, pi, q);
+}
+// adam_update's loop (a scalar grid-stride loop over any start and n) with the decoupled element
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, int64_t n, float step, float b1, float b2, float eps,
+                                             float dec, float bc2s, float gscale) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_update1(pi, g[i], mi, vi, step, b1, b2, eps, dec, bc2s, gscale);
+        m[i] = mi; v[i] = vi;
+        p[i] = pi;
+    }
+}
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                                                    float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                                                    float gscale) {
+    adamw_update(p, g, m, v, n, lr / bc1, b1, b2, eps, adamw_dec(lr, wd), bc2s, gscale);
+}
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                        const float* __restrict__ hyper, const AdamDevState* st,
+                                                        const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;    // p, m, v are neither read nor written: a skipped step does not decay
+    adamw_update(p, g, m, v, n, hyper[0] / st->bc1, hyper[1], hyper[2], hyper[3], adamw_dec(hyper[0], hyper[4]), st->bc2s,
+                 guard != nullptr ? hyper[5] * guard->coef : hyper[5]);
+}
+// adam_seg_kernel with the decoupled element: the same grid, the same map reads, the same 16 bytes per lane
+__global__ __launch_bounds__(256) void adamw_seg_kernel(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
+                                                        f32x4* __restrict__ v, int64_t nvec, const uint8_t* __restrict__ map,
+                                                        const float* __restrict__ hyper, const AdamDevState* __restrict__ states,
+                                                        const AdamGuard* guard) {
+    if (guard != nullptr && guard->skip != 0) return;    // p, m, v are neither read nor written
+    const int64_t T = (int64_t)gridDim.x * 256;
+    for (int64_t i0 = blockIdx.x * 256ll; i0 < nvec; i0 += T) {      // (block-uniform bound: every lane reaches the shuffle)
+        const int64_t i = i0 + threadIdx.x;
+        const int k = seg_group(map, i, i < nvec);
+        if (k == SEG_SKIP) continue;
+        const float* __restrict__ h = hyper + 6 * k;
+        const AdamDevState* st = states + k;
+        const float gscale = guard != nullptr ? h[5] * guard->coef : h[5];
+        const float step = h[0] / st->bc1, b1 = h[1], b2 = h[2], eps = h[3], dec = adamw_dec(h[0], h[4]), bc2s = st->bc2s;
+        const f32x4 gi = g[i];
+        const f32x4 p4 = p[i], m4 = m[i], v4 = v[i];
+        float pe[4] = {p4.x, p4.y, p4.z, p4.w}, me[4] = {m4.x, m4.y, m4.z, m4.w}, ve[4] = {v4.x, v4.y, v4.z, v4.w};
+        const float ge[4] = {gi.x, gi.y, gi.z, gi.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) adamw_update1(pe[e], ge[e], me[e], ve[e], step, b1, b2, eps, dec, bc2s, gscale);
+        m[i] = f32x4{me[0], me[1], me[2], me[3]};
+        v[i] = f32x4{ve[0], ve[1], ve[2], ve[3]};
+        p[i] = f32x4{pe[0], pe[1], pe[2], pe[3]};
+    }
+}
 // stage 1 of gdn_grad_sumsq_seg: adam_gradnorm_partial_kernel over the chunks that are not skipped (a skipped chunk is not
 // read, so a NaN there stays out of the sum); the same grid, the same per-lane partials and the same block reduction.
 __global__ __launch_bounds__(256) void adam_gradnorm_seg_partial_kernel(const f32x4* __restrict__ gv, int64_t nvec,
@@ -1466,6 +1536,51 @@ extern "C" int gdn_ema_update_seg(float* ema, const float* p, int64_t n, const u
     if (((uintptr_t)states & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
     hipLaunchKernelGGL(ema_update_seg_kernel, dim3(stream_rw_blocks(n, true)), dim3(256), 0, ST(stream), (f32x4*)ema, (const f32x4*)p,
                        n / 4, map, decay, (const AdamDevState*)states, (const AdamGuard*)guard);
+    return gdn_launch_status();
+}
+
+// ---- decoupled weight decay: the four update entry points again, argument lists, checks and launch geometry of their coupled
+// counterparts, the prep launch shared with them
+extern "C" int gdn_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                              float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !g || !m || !v || n <= 0 || step < 1) return GDN_ERR_BAD_ARG;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(adamw_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n, lr,
+                       beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
+    return gdn_launch_status();
+}
+static void adamw_dev_launch(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, void* state,
+                             const void* guard, void* stream) {
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), adam_prep_block(1), 0, ST(stream), (AdamDevState*)state, hyper, 1,
+                       (const AdamGuard*)guard);
+    hipLaunchKernelGGL(adamw_dev_kernel, dim3(stream_blocks(n, 256, 4096)), dim3(256), 0, ST(stream), p, g, m, v, n, hyper,
+                       (const AdamDevState*)state, (const AdamGuard*)guard);
+}
+extern "C" int gdn_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, void* state,
+                                  void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !g || !m || !v || n <= 0 || !hyper || !state) return GDN_ERR_BAD_ARG;
+    adamw_dev_launch(p, g, m, v, n, hyper, state, nullptr, stream);
+    return gdn_launch_status();
+}
+extern "C" int gdn_adamw_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                                          void* state, const void* guard, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !g || !m || !v || n <= 0 || !hyper || !state || !guard) return GDN_ERR_BAD_ARG;
+    adamw_dev_launch(p, g, m, v, n, hyper, state, guard, stream);
+    return gdn_launch_status();
+}
+extern "C" int gdn_adamw_step_seg(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* map, int32_t G,
+                                  const float* hyper, void* states, const void* guard, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !g || !m || !v || !hyper || !states || G < 1 || G > 254 || seg_bad_range(n, map, p, g, m, v)) return GDN_ERR_BAD_ARG;
+    if (((uintptr_t)hyper & 3) || ((uintptr_t)states & 7) || ((uintptr_t)guard & 7)) return GDN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), adam_prep_block(G), 0, ST(stream), (AdamDevState*)states, hyper, (int)G,
+                       (const AdamGuard*)guard);
+    hipLaunchKernelGGL(adamw_seg_kernel, dim3(stream_rw_blocks(n, true)), dim3(256), 0, ST(stream), (f32x4*)p, (const f32x4*)g,
+                       (f32x4*)m, (f32x4*)v, n / 4, map, hyper, (const AdamDevState*)states, (const AdamGuard*)guard);
     return gdn_launch_status();
 }
 

@@ -69,6 +69,13 @@ the ``--min_depth`` / ``--max_depth`` cap, the ``--eval_crop {garg,eigen,none}``
 ``--flip_test``, nine metrics averaged per image.  ``--eval_gt_list FILE`` (test modes with ``--real_test``) takes the ground
 truth from 16-bit KITTI depth maps at their native size; the prediction is resampled to each map inside the metrics kernel.
 The result line states the protocol's parameters.  ``--eval_protocol reference`` is the run without the flag.
+``--optimizer adamw`` trains with decoupled weight decay: ``--decoupled_wd W`` (1e-2 when not given) takes
+the place of the reference's 5e-4, stays out of the gradient and the moments and shrinks each weight by ``rate x W x weight``
+inside the fused update's own launches, ``rate`` being the update's (after ``--lr_mult`` and the schedule); ``--no_decay_norm``
+takes it off gamma / beta.  It runs with ``--graph``, ``--resume``, ``--accum_steps``, the gradient guard, ``--ema_decay``,
+``--freeze`` / ``--lr_mult``, the schedules, ``--loss silog`` and bf16; the optimizer state in ``train_state.pt`` says which
+rule wrote it and a resumed run must repeat the flag.  ``--weight-decay`` stays accepted and ignored.  ``--optimizer adam`` is
+the run without the flag.
 """
 import contextlib
 import io
@@ -109,6 +116,10 @@ def _make_optimizer(model, args):
     schedule = lr_schedule_of(args, getattr(args, "epochs", 0), getattr(args, "epoch_size", 0))
     if schedule is not None:
         guard["schedule"] = schedule
+    # --optimizer adamw: --decoupled_wd in the place of the reference's L2 term, decoupled from the gradient
+    decay = option.decoupled_wd(args)
+    if decay is not None:
+        return Adam(params, args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=decay, decoupled=True, **guard)
     return Adam(params, args.lr, [args.momentum, args.beta], eps=1e-08, weight_decay=5e-4, **guard)
 
 
@@ -217,6 +228,23 @@ def _check_schedule(args):
                            "trains nothing" % args.mode)
     if floor != 0.0 and flag not in ("linear", "cosine"):
         raise RuntimeError("--lr_floor %g is where a decay ends, and --lr_schedule %s has none (linear or cosine do)" % (floor, flag))
+
+
+def _check_optimizer(args):
+    """--optimizer / --decoupled_wd pick the update rule of a training run; checked before anything touches the GPU."""
+    adamw = (getattr(args, "optimizer", None) or "adam") == "adamw"
+    if getattr(args, "decoupled_wd", None) is not None and not adamw:
+        raise RuntimeError("--decoupled_wd sets the decoupled weight decay, which --optimizer adamw selects (add it, or drop "
+                           "the flag)")
+    if adamw and args.mode in TEST_MODES:
+        raise RuntimeError("--optimizer adamw is the update rule of a training run; --mode %s trains nothing" % args.mode)
+
+
+def _announce_optimizer(args, rank):
+    decay = option.decoupled_wd(args)
+    if decay is not None and rank == 0:
+        print("=> optimizer: AdamW, decoupled weight decay %g%s" %
+              (decay, " (0 on the 1-D parameters)" if getattr(args, "no_decay_norm", False) else ""))
 
 
 def _check_loss(args, train_loader=None):
@@ -391,6 +419,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_graph(args)
     _check_accum(args)
     _check_schedule(args)
+    _check_optimizer(args)
     _check_loss(args, train_loader)
     _check_freeze_bn(args)
     _check_eval(args)
@@ -472,6 +501,7 @@ def run(args, train_loader=None, val_loader=None):
         _freeze(G, args, rank)
         D.broadcast_parameters(G)             # rank 0's weights / BN buffers everywhere (identical seeds make this a no-op)
         opt = _make_optimizer(G, args)
+        _announce_optimizer(args, rank)
         loss = train_AE_DtoD(args, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
                              args.lr, logger, None, progress=_resume(args, G, opt, train_loader, rank))
         if rank == 0 and loss is not None:
@@ -494,6 +524,7 @@ def run(args, train_loader=None, val_loader=None):
         _freeze(R, args, rank)
         D.broadcast_parameters(R)
         opt = _make_optimizer(R, args)
+        _announce_optimizer(args, rank)
         return train_AE_RtoD(args, R, G, None, None, opt, train_loader, val_loader, args.batch_size, args.epochs,
                              args.lr, logger, None, progress=_resume(args, R, opt, train_loader, rank))
     if args.mode in ('DtoD_test', 'RtoD_test'):

@@ -150,6 +150,10 @@ _SIGS = {
     "gdn_grad_sumsq_seg": (c_int32, [_P, _i64, _P, _P, _i32, _P, _sz, _P]),
     "gdn_ema_update_seg": (c_int32, [_P, _P, _i64, _P, c_double, _P, _P, _P]),
     "gdn_lr_schedule": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, c_double, _P]),
+    "gdn_adamw_step": (c_int32, [_P, _P, _P, _P, _i64, _f, _f, _f, _f, _f, _i32, _f, _P]),
+    "gdn_adamw_step_dev": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P]),
+    "gdn_adamw_step_dev_guarded": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P, _P]),
+    "gdn_adamw_step_seg": (c_int32, [_P, _P, _P, _P, _i64, _P, _i32, _P, _P, _P, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),
@@ -161,7 +165,8 @@ EXPORTS = tuple(_SIGS)
 # a stale build would take the arguments apart differently.  (gdn_grad_accumulate joined revision 223 without a new number:
 # _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
 # and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule, gdn_silog_masked and the
-# evaluation entry points gdn_depth_metrics_std*, gdn_flip_w and gdn_flip_mean, for the same reason.)
+# evaluation entry points gdn_depth_metrics_std*, gdn_flip_w and gdn_flip_mean, and the four gdn_adamw_step* entry points of
+# the decoupled weight decay, for the same reason.)
 ABI_VERSION = 223
 
 

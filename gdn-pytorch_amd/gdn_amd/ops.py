@@ -1436,6 +1436,31 @@ def ema_update_seg(ema, p, chunk_map, decay, states, guard=None):
     lib.gdn_ema_update_seg(_p(ema), _p(p), n, _p(chunk_map), float(decay), _p(states), _p(guard), stream())
 
 
+# Decoupled weight decay (AdamW): the four updates again, the arguments and the checks of their siblings, with
+# weight_decay / hyper[4] the decoupled rate -- p -= fma(float32(lr * wd), p, adam term), the moments never see the decay.
+def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+    lib.gdn_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, int(step),
+                       float(grad_scale), stream())
+
+
+def adamw_step_dev(p, g, m, v, hyper, state):
+    """adam_step_dev with decoupled weight decay (gdn_adamw_step_dev)."""
+    lib.gdn_adamw_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), stream())
+
+
+def adamw_step_dev_guarded(p, g, m, v, hyper, state, guard):
+    """adam_step_dev_guarded with decoupled weight decay: a skipped step does not decay (gdn_adamw_step_dev_guarded)."""
+    lib.gdn_adamw_step_dev_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(state), _p(guard), stream())
+
+
+def adamw_step_seg(p, g, m, v, chunk_map, hyper, states, guard=None):
+    """adam_step_seg with decoupled weight decay, each chunk at its own group's rate and decay; a skipped chunk does not decay
+    (gdn_adamw_step_seg)."""
+    n = p.numel()
+    G = _seg_groups(n, chunk_map, hyper, states)
+    lib.gdn_adamw_step_seg(_p(p), _p(g), _p(m), _p(v), n, _p(chunk_map), G, _p(hyper), _p(states), _p(guard), stream())
+
+
 LR_SCHEDULE_KINDS = ("constant", "linear", "cosine")        # the `kind` argument of gdn_lr_schedule: 0, 1, 2
 
 

@@ -23,6 +23,10 @@ kernels read a map from 64-float chunks of the arena to groups and skip what is 
 Learning-rate schedule (``schedule``): warm-up and a constant / linear / cosine decay evaluated on the device from the
 device's own update count, one small launch per arena in front of the update -- no host write per step, capturable
 (DESIGN.md 3.9).
+
+Decoupled weight decay (``decoupled``, ``AdamW``): the groups' ``weight_decay`` leaves the gradient and decays the weight
+directly, at the update's own rate, inside the same launches -- the gdn_adamw_step* entry points in their siblings' places
+(DESIGN.md 3.13).
 """
 import collections
 import contextlib
@@ -434,10 +438,19 @@ class Adam(torch.optim.Optimizer):
     pushes nothing per step, so captured graphs replay it.  Implies capturable=True.  A skipped step does not advance u.
     Code that writes group['lr'] (the reference's decay) still works: the base rate is pushed when it changes, outside a
     capture.  current_lr() reads the rates the last update used.  state_dict()['gdn']['schedule'] carries the four values
-    and load_state_dict() refuses another schedule."""
+    and load_state_dict() refuses another schedule.
+
+    decoupled (optimizer-wide): the groups' weight_decay is torch.optim.AdamW's -- it stays out of the gradient
+    and the moments, and the weight loses float32(rate * weight_decay) * p with the Adam term in one subtraction, `rate` being
+    the update's own (after lr_mult and the schedule).  Every update path calls the gdn_adamw_step* entry point in its
+    sibling's place: the same launches, the same records.  A parameter without a gradient, a frozen chunk and a step the
+    guard skips are not decayed.  It does not imply capturable.  state_dict()['gdn'] carries 'decoupled': True only when it
+    is on, and load_state_dict() refuses a 'gdn' state of the other kind: the groups' weight_decay comes from the checkpoint
+    and would silently change its meaning.  A dict without a 'gdn' key (torch.optim.Adam, torch.optim.AdamW) loads as ever."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, segmented=False, schedule=None):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, segmented=False, schedule=None,
+                 decoupled=False):
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be positive (None: no clipping), got %r" % (max_grad_norm,))
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
@@ -455,6 +468,7 @@ class Adam(torch.optim.Optimizer):
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.segmented = bool(segmented)
         self.schedule = check_schedule(schedule)
+        self.decoupled = bool(decoupled)
         self.capturable = bool(capturable) or self.guarded or self.ema_decay is not None or self.segmented or \
             self.schedule is not None
         for g in self.param_groups:
@@ -523,8 +537,12 @@ class Adam(torch.optim.Optimizer):
         """One update of the host path, launched now: the whole store with its count, or `item` with that parameter's own."""
         w, m, v, _ = st.ranges(item)
         b1, b2 = group["betas"]
-        ops.adam_step(w, grad, m, v, _lr(group), b1, b2, group["eps"], group["weight_decay"],
-                      st.step if item is None else st.pstep[id(item[0])], self._scale())
+        self._update("")(w, grad, m, v, _lr(group), b1, b2, group["eps"], group["weight_decay"],
+                         st.step if item is None else st.pstep[id(item[0])], self._scale())
+
+    def _update(self, form):
+        """ops.adam_step<form>, or with decoupled weight decay its sibling ops.adamw_step<form> (looked up per call)."""
+        return getattr(ops, ("adamw_step" if self.decoupled else "adam_step") + form)
 
     def _launch(self, st, grad, row, state, cmap=None, item=None):
         """One capturable update of store `st` (all of it, or `item`) with `grad` in the weights' physical layout, and the
@@ -544,14 +562,14 @@ class Adam(torch.optim.Optimizer):
             s = self.schedule
             ops.lr_schedule(job.hyper, job.base_lr, job.state, s["kind"], s["warmup"], s["total"], s["floor"])
         if job.map is not None:
-            ops.adam_step_seg(job.w, job.grad, job.m, job.v, job.map, job.hyper, job.state, guard)
+            self._update("_seg")(job.w, job.grad, job.m, job.v, job.map, job.hyper, job.state, guard)
             if job.ema is not None:
                 ops.ema_update_seg(job.ema, job.w, job.map, self.ema_decay, job.state, guard)
             return
         if guard is None:
-            ops.adam_step_dev(job.w, job.grad, job.m, job.v, job.hyper, job.state)
+            self._update("_dev")(job.w, job.grad, job.m, job.v, job.hyper, job.state)
         else:
-            ops.adam_step_dev_guarded(job.w, job.grad, job.m, job.v, job.hyper, job.state, guard)
+            self._update("_dev_guarded")(job.w, job.grad, job.m, job.v, job.hyper, job.state, guard)
         if job.ema is not None:
             ops.ema_update(job.ema, job.w, self.ema_decay, job.state, guard)      # the same skip decision
 
@@ -969,6 +987,8 @@ class Adam(torch.optim.Optimizer):
                              "steps": gs["steps"], "clipped": gs["clipped"], "skipped": gs["skipped"]}
         if self.schedule is not None:
             priv["schedule"] = dict(self.schedule)
+        if self.decoupled:
+            priv["decoupled"] = True
         if self.ema_decay is not None:
             # every parameter, so the averaged model can be put together from this key alone (no update yet: avg_0 = p_0)
             views = self._ema_views()
@@ -992,6 +1012,12 @@ class Adam(torch.optim.Optimizer):
             if theirs != self.schedule:
                 raise GdnError("optimizer state written under the learning-rate schedule %r loaded into an optimizer with the "
                                "schedule %r: the update counts it carries would mean other rates" % (theirs, self.schedule))
+            theirs = bool((state_dict["gdn"] or {}).get("decoupled", False))
+            if theirs != self.decoupled:
+                kinds = ("coupled (Adam, L2)", "decoupled (AdamW)")
+                raise GdnError("optimizer state written under %s weight decay loaded into an optimizer with %s weight decay: "
+                               "the weight_decay its param groups carry would mean another update" %
+                               (kinds[theirs], kinds[self.decoupled]))
         groups = state_dict["param_groups"]
         mine = [len(g["params"]) for g in self.param_groups]
         theirs = [len(g["params"]) for g in groups]
@@ -1056,3 +1082,12 @@ class Adam(torch.optim.Optimizer):
             ar = getattr(p, "_gdn_arena", None)
             if ar is not None:
                 ar.touch()
+
+
+class AdamW(Adam):
+    """Adam(..., decoupled=True) with torch.optim.AdamW's defaults: weight_decay 1e-2, decoupled from the gradient."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        if not kw.pop("decoupled", True):
+            raise ValueError("AdamW is the decoupled optimizer; Adam(decoupled=False) is the coupled one")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=True, **kw)

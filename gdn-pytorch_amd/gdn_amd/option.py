@@ -3,7 +3,7 @@ plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
 --graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm, --warmup_steps, --lr_schedule,
 --lr_floor, --loss, --silog_lambda, --silog_weight, --silog_floor, --silog_mask, --eval_protocol, --eval_crop, --min_depth,
---max_depth, --depth_scale, --median_scaling, --flip_test, --eval_gt_list).
+--max_depth, --depth_scale, --median_scaling, --flip_test, --eval_gt_list, --optimizer, --decoupled_wd).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -183,7 +183,8 @@ def build_parser():
                         'stay.  Not stored in train_state.pt, a resumed run repeats it')
     p.add_argument('--no_decay_norm', action='store_true',
                    help='training: every 1-D parameter (BatchNorm / InstanceNorm gamma, beta) takes weight decay 0 instead of '
-                        'the 5e-4 the reference applies to it too.  Not stored in train_state.pt, a resumed run repeats it')
+                        'the 5e-4 the reference applies to it too (with --optimizer adamw: instead of --decoupled_wd, the '
+                        'usual AdamW practice).  Not stored in train_state.pt, a resumed run repeats it')
     p.add_argument('--warmup_steps', type=_non_negative_int, default=0, metavar='W',
                    help='training: the first W Adam updates run at (u + 1) / W of the learning rate (u = 0, 1, ... counts '
                         'APPLIED updates: a step --skip_nonfinite drops does not advance it), every --lr_mult group at its own '
@@ -239,7 +240,27 @@ def build_parser():
                    help='with --eval_protocol standard, a test mode and --real_test: one 16-bit KITTI depth PNG (metres x '
                         '256) per test sample, at its native size, as the ground truth; the network\'s inputs stay what '
                         'the test lists feed it')
+    p.add_argument('--optimizer', default='adam', choices=['adam', 'adamw'],
+                   help='training: the update rule of the fused optimizer.  adam: the reference\'s Adam with its L2 term of '
+                        '5e-4 folded into the gradient, as ever.  adamw: decoupled weight decay (DESIGN.md 3.13) -- the decay '
+                        'stays out of the gradient and the moments and shrinks the weight at the update\'s own rate, inside '
+                        'the same launches.  Stored with the optimizer state in train_state.pt: a resumed run must repeat it')
+    # (None so that the flag given without --optimizer adamw can be refused; decoupled_wd() resolves it)
+    p.add_argument('--decoupled_wd', type=_non_negative_float, default=None, metavar='W',
+                   help='with --optimizer adamw: the decoupled weight decay, >= 0 (when not given: 1e-2, torch.optim.AdamW\'s '
+                        'default, a common choice that is not tuned here); --no_decay_norm takes it off the 1-D parameters')
     return p
+
+
+DECOUPLED_WD_DEFAULT = 1e-2
+
+
+def decoupled_wd(args):
+    """None for --optimizer adam; for --optimizer adamw the decoupled weight decay, the flag not given at its default."""
+    if (getattr(args, 'optimizer', None) or 'adam') != 'adamw':
+        return None
+    w = getattr(args, 'decoupled_wd', None)
+    return DECOUPLED_WD_DEFAULT if w is None else float(w)
 
 
 EVAL_DEFAULTS = {'eval_crop': 'garg', 'min_depth': 1e-3, 'max_depth': 80.0, 'depth_scale': 80.0}

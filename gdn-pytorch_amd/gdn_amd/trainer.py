@@ -134,6 +134,13 @@ def load_training_state(state, model, optimizer, loader):
         raise U.GdnError("the training state was written under the learning-rate schedule %r, this run has %r "
                          "(--lr_schedule / --warmup_steps / --lr_floor / the run's length): the update counts it carries would "
                          "mean other rates" % (theirs, mine))
+    # --optimizer: the optimizer state says which update rule wrote it ('decoupled', only when it is on); refused here, before
+    # the weights are overwritten, as optim.Adam.load_state_dict() would refuse it after
+    theirs = bool((state["optimizer"].get("gdn") or {}).get("decoupled", False))
+    if theirs != bool(getattr(optimizer, "decoupled", False)):
+        names = ("--optimizer adam", "--optimizer adamw")
+        raise U.GdnError("the training state was written under %s, this run has %s: the weight decay its optimizer state "
+                         "carries would mean another update" % (names[theirs], names[not theirs]))
     model.load_state_dict(state["model"])
     ar = getattr(model, "_gdn_param_arena", None)
     if ar is not None:

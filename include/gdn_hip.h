@@ -883,6 +883,34 @@ int gdn_ema_update_seg(float* ema, const float* p, int64_t n, const uint8_t* map
 int gdn_lr_schedule(float* hyper, const double* base_lr, const void* states, int32_t G, int32_t kind, int32_t warmup,
                     int32_t total, double floor, void* stream);
 
+/* Decoupled weight decay (AdamW; no reference counterpart): the four update entry points once more, each with
+ * the argument list, the return codes, the checks, the records (hyper row of 6 floats, step state, guard, chunk map), the prep
+ * launch and the launch geometry of the entry point it is named after -- only the element differs.  weight_decay / hyper[4]
+ * is the DECOUPLED rate: it does not enter the gradient, so the moments never see it.  With lr = this update's rate (the
+ * launch argument, hyper[0] after a gdn_lr_schedule), step = lr / bc1 and gscale as in the coupled update, in float32:
+ *     dec = (float)((double)lr * (double)wd)           computed by the update kernel from the row it reads (the double product of
+ *                                                      two floats is exact: this is the float32 product, rounded once)
+ *     gi  = g * gscale
+ *     mi  = b1 * m + (1 - b1) * gi
+ *     vi  = b2 * v + (1 - b2) * gi * gi
+ *     q   = step * mi / (sqrtf(vi) / bc2s + eps)
+ *     p   = pi - fmaf(dec, pi, q)
+ *   every product, sum, quotient and root rounded on its own, the one fmaf the only fused operation, in all four entry points:
+ *   on the same slice with the same records they give the same bits, and with wd = 0 the bits of the coupled entry point at
+ *   wd = 0.  (The decay is ADDED to the Adam term and subtracted once: p * (1 - lr * wd) loses it in float32 as soon as
+ *   lr * wd < 2^-25.)  Mathematically torch.optim.AdamW.  A step the guard skips touches neither p, m, v nor the step state:
+ *   it does not decay.  A skipped chunk (0xFF) of gdn_adamw_step_seg is neither read nor written.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+int gdn_adamw_step(float* p, const float* g, float* m, float* v, int64_t n,
+                   float lr, float beta1, float beta2, float eps, float weight_decay,
+                   int32_t step, float grad_scale, void* stream);
+int gdn_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
+                       const float* hyper, void* state, void* stream);
+int gdn_adamw_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n,
+                               const float* hyper, void* state, const void* guard, void* stream);
+int gdn_adamw_step_seg(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* map, int32_t G,
+                       const float* hyper, void* states, const void* guard, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
