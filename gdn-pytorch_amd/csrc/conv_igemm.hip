@@ -911,6 +911,7 @@ __global__ __launch_bounds__(256, 3) void conv_rowpatch_bf16(const IgemmParams p
     }
 }
 
+#include "ring_common.h"
 #include "conv_ring.h"
 #include "conv_ring2.h"
 
@@ -1046,7 +1047,7 @@ bool rowpatch_ok(const IgemmParams& P) {
 
 // LDS-DMA ring kernel eligibility (geometry only): as the row-patch kernel, with an odd window of 3..9 taps per row (the
 // instantiated schedules), whole BN-channel tiles, and the touched rows' halos within the 64 spare positions of the patch.
-int ring_kw(const IgemmParams& P, int bm = RG_BM) {
+int ring_kw(const IgemmParams& P, int cfg = 10) {
     if (P.nphase != 1 || P.stride != 1 || (P.Cred % 64)) return 0;
     const IgemmPhase& ph = P.ph[0];
     const int ntap = ph.tap_end - ph.tap_begin;
@@ -1061,43 +1062,38 @@ int ring_kw(const IgemmParams& P, int bm = RG_BM) {
             const int i = ph.tap_begin + r * kw + t, i0 = ph.tap_begin + r * kw;
             if (P.tdy[i] != P.tdy[i0] || P.tdx[i] != P.tdx[ph.tap_begin] + dir * t || P.twi[i] != P.twi[i0] + t) return 0;
         }
-    const int nrows_max = (bm - 1 + ph.Wo - 1) / ph.Wo + 1;
-    if (nrows_max > (bm == RG_BM ? RG_NRMAX : RG2_NRMAX) || bm + nrows_max * (kw - 1) > (bm == RG_BM ? RG_APOS : RG2_APOS)) return 0;
-    return kw;
+    const RingFormV f = ring_form(cfg);
+    const int nrows_max = (f.bm - 1 + ph.Wo - 1) / ph.Wo + 1;
+    return nrows_max > f.nrmax || f.bm + nrows_max * (kw - 1) > f.apos ? 0 : kw;
 }
-bool ring_ok(const IgemmParams& P, int bn, int bm = RG_BM) { return ring_kw(P, bm) != 0 && P.N % bn == 0 && !P.x2; }
 
 // How the persistent workgroups of conv_ring_bf16 cover the (M-tile, N-tile) units: G workgroups (one per CU), `main` units in
 // full rounds, and -- when the last round would be a small fraction of one (B = 20: 65/64 of a power of two tiles at every
 // level) -- its `tail` units cut into `parts` stage ranges of `sp` stages, one per workgroup, summed by splitk_combine_kernel.
-struct RingPlan { int G, grid_m, grid_n, main_units, tail_units, parts, sp, slabs, main_mtiles; int64_t tail_px; };
+struct RingPlan { int G, grid_m, grid_n, main_units, tail_units, parts, sp, slabs, main_mtiles, kw; int64_t tail_px; };
 RingPlan ring_plan(const IgemmParams& P, int cfg) {
     RingPlan r{};
-    const int bm = kCfg[cfg].bm, bn = kCfg[cfg].bn;
+    const RingFormV f = ring_form(cfg);
     const IgemmPhase& ph = P.ph[0];
     const int64_t M = (int64_t)P.B * ph.Ho * ph.Wo;
-    r.grid_m = (int)cdiv64(M, bm); r.grid_n = P.N / bn;
+    r.grid_m = (int)cdiv64(M, f.bm); r.grid_n = P.N / kCfg[cfg].bn;
     const int units = r.grid_m * r.grid_n, units_xcd = cdiv(r.grid_m, 8) * r.grid_n, cus_xcd = P.plan_cus / 8 > 0 ? P.plan_cus / 8 : 32;
     r.G = 8 * (units_xcd < cus_xcd ? units_xcd : cus_xcd);
-    const int kw = ring_kw(P, bm), nstage = kw ? (ph.tap_end - ph.tap_begin) / kw * (P.Cred / (bm == RG_BM ? 64 : 32)) : 0;
+    const int kw = r.kw = ring_kw(P, cfg), nstage = kw ? (ph.tap_end - ph.tap_begin) / kw * (P.Cred / f.slab) : 0;
     const int rounds = units / r.G, tail = units % r.G;
     r.main_units = units; r.parts = 1; r.sp = nstage; r.slabs = 0; r.main_mtiles = r.grid_m; r.tail_px = 0;
     if (P.ring_notail) return r;                                       // (tile_cfg & 0x800: every unit whole)
     if (rounds >= 1 && tail > 0 && 4 * tail <= r.G && nstage >= 2 && r.G % r.grid_n == 0) {
         int parts = r.G / tail < nstage ? r.G / tail : nstage;
         if (parts > 8) parts = 8;                 // (each range is one fp32 slab -- two with the 256 x 64 form -- that the combine pass reads back)
-        r.sp = cdiv(nstage, parts);
-        r.parts = cdiv(nstage, r.sp);
-        r.main_units = rounds * r.G; r.tail_units = tail;
-        r.main_mtiles = r.main_units / r.grid_n;
-        r.tail_px = M - (int64_t)r.main_mtiles * bm;
-        r.slabs = r.parts * (cfg == 10 ? 2 : 1);
+        r.sp = cdiv(nstage, parts); r.parts = cdiv(nstage, r.sp);
+        r.main_units = rounds * r.G; r.tail_units = tail; r.main_mtiles = r.main_units / r.grid_n;
+        r.tail_px = M - (int64_t)r.main_mtiles * f.bm; r.slabs = r.parts * f.tail_slabs;
     }
     return r;
 }
 size_t ring_ws_bytes(const IgemmParams& P, int cfg) {
-    if (cfg < 10) return 0;
-    const RingPlan r = ring_plan(P, cfg);
+    const RingPlan r = cfg >= 10 ? ring_plan(P, cfg) : RingPlan{};
     return r.parts > 1 ? (size_t)r.slabs * r.tail_px * P.N * sizeof(float) : 0;
 }
 
@@ -1106,9 +1102,7 @@ int pick_cfg_bf16(const IgemmParams& P, int64_t M, int N, int forced) {
     const bool rp = rowpatch_ok(P);
     if (forced >= 1 && forced <= 3) return forced;
     if ((forced == 8 || forced == 9) && rp) return forced;
-    if (forced == 10 && ring_ok(P, 64)) return 10;
-    if (forced == 11 && ring_ok(P, 128)) return 11;
-    if (forced == 12 && ring_ok(P, 64, RG2_BM)) return 12;
+    if (forced >= 10 && forced <= 12 && ring_kw(P, forced) != 0 && P.N % kCfg[forced].bn == 0 && !P.x2) return forced;
     // round 4 (tests/diag/ring_check.py, ring_probe.py at B = 20): the LDS-DMA ring kernel (conv_ring.h) beats both round-1
     // kernels on every stride-1 layer with a 3..9 window -- 9x9 / 64 ch 1070 vs 930, 7x7 / 128 ch 1045 vs 886, 5x5 / 256 ch 885
     // vs 725, 3x3 / 512 ch at 8x26 418 vs 266 TFLOP/s, level with them at 16x52 (603) -- and its data gradients with a residual
@@ -1117,11 +1111,11 @@ int pick_cfg_bf16(const IgemmParams& P, int64_t M, int N, int forced) {
     if (forced == 0 && ring_kw(P) != 0 && !P.x2 && N % 64 == 0) {
         // 256 x 128 tiles (0.75 fragment reads per MFMA instead of 1, no exchange of reduction halves) wherever they give every
         // CU at least one unit; else 256 x 64 (8x26 level: 68 units of 256 x 128 for 256 CUs)
-        if (N % 128 == 0 && cdiv64(M, RG_BM) * (N / 128) >= P.plan_cus) return 11;
+        if (N % 128 == 0 && cdiv64(M, kCfg[11].bm) * (N / 128) >= P.plan_cus) return 11;
         // round 5: 512 x 64 tiles on 32-channel slabs (conv_ring2.h) for the 64-output-channel layers with wide windows -- half
         // the per-tile set-up and epilogue barriers per pixel, 2/3 of the LDS-DMA bytes (tests/diag/ring2_check.py at B = 20:
         // 9x9 / 64 ch 1104 vs 1070 TFLOP/s, reflect 7x7 128 -> 64 1101 vs 1048; N >= 128 layers lose 4-8 %)
-        if (N == 64 && ring_kw(P, RG2_BM) >= 7 && cdiv64(M, RG2_BM) >= 2 * P.plan_cus) return 12;
+        if (N == 64 && ring_kw(P, 12) >= 7 && cdiv64(M, kCfg[12].bm) >= 2 * P.plan_cus) return 12;
         return 10;
     }
     if (rp && N <= 128 && cdiv64(M, RP_BM) * cdiv(N, 64) >= 448) return 9;
@@ -1249,6 +1243,19 @@ size_t ksplit_bytes(const IgemmParams& P, int ksplit) {
     return ksplit > 1 ? (size_t)ksplit * P.B * P.Hy * P.Wy * P.N * sizeof(float) : 0;
 }
 
+// launch_ring_kernel: one launch of a form's kernel (BM = 256: conv_ring_bf16, 512: conv_ring2_bf16); launch_ring: that of kw taps per row, false: none
+template <int BM, int BN, int KW, bool BNB>
+void launch_ring_kernel(dim3 g, hipStream_t st, const IgemmParams& P) {
+    if constexpr (BM == 512) hipLaunchKernelGGL((conv_ring2_bf16<BN, KW, BNB>), g, dim3(512), 0, st, P);
+    else hipLaunchKernelGGL((conv_ring_bf16<BN, KW, BNB>), g, dim3(512), 0, st, P);
+}
+template <int BM, int BN, int KW = 9>
+bool launch_ring(int kw, dim3 g, hipStream_t st, const IgemmParams& P) {
+    if (kw != KW) { if constexpr (KW > 3) return launch_ring<BM, BN, KW - 2>(kw, g, st, P); else return false; }
+    P.bnb_y ? launch_ring_kernel<BM, BN, KW, true>(g, st, P) : launch_ring_kernel<BM, BN, KW, false>(g, st, P);
+    return true;
+}
+
 // Launches the kernel; with ksplit > 1 the partials go to `split_ws` and the combine kernel writes
 // y / stats (P.y, P.ldy, P.addsrc, P.act, P.stats keep their single-stage meaning).
 int launch_igemm(IgemmParams& P, int cfg, hipStream_t st, int ksplit = 1, void* split_ws = nullptr) {
@@ -1271,20 +1278,13 @@ int launch_igemm(IgemmParams& P, int cfg, hipStream_t st, int ksplit = 1, void* 
             case 10: case 11: case 12: case 13: {
                 // persistent workgroups, one per CU: every XCD (workgroups b, b + 8, ...) walks its band of tiles
                 const RingPlan rp = ring_plan(P, cfg);
-                const dim3 g1(rp.G), b1(512);
                 P.ksplit = rp.parts; P.ring_main = rp.main_units; P.ring_sp = rp.sp;
                 if (rp.parts > 1 && !split_ws) return GDN_ERR_WORKSPACE;
-#define GDN_RING(BNV, KWV) do { if (P.bnb_y) hipLaunchKernelGGL((conv_ring_bf16<BNV, KWV, 0, true>), g1, b1, 0, st, P); \
-                                else hipLaunchKernelGGL((conv_ring_bf16<BNV, KWV>), g1, b1, 0, st, P); } while (0)
-#define GDN_RING2(BNV, KWV) do { if (P.bnb_y) hipLaunchKernelGGL((conv_ring2_bf16<BNV, KWV, 0, true>), g1, b1, 0, st, P); \
-                                 else hipLaunchKernelGGL((conv_ring2_bf16<BNV, KWV>), g1, b1, 0, st, P); } while (0)
-                const int kw = ring_kw(P, tc.bm);
-                if (cfg == 12) { if (kw == 3) GDN_RING2(64, 3); else if (kw == 5) GDN_RING2(64, 5); else if (kw == 7) GDN_RING2(64, 7); else if (kw == 9) GDN_RING2(64, 9); else return GDN_ERR_UNSUPPORTED; }
-                else if (cfg == 13) return GDN_ERR_UNSUPPORTED;    // (512 x 128: 128 accumulator registers per lane of 256 -- spills)
-                else if (cfg == 10) { if (kw == 3) GDN_RING(64, 3); else if (kw == 5) GDN_RING(64, 5); else if (kw == 7) GDN_RING(64, 7); else if (kw == 9) GDN_RING(64, 9); else return GDN_ERR_UNSUPPORTED; }
-                else { if (kw == 3) GDN_RING(128, 3); else if (kw == 5) GDN_RING(128, 5); else if (kw == 7) GDN_RING(128, 7); else if (kw == 9) GDN_RING(128, 9); else return GDN_ERR_UNSUPPORTED; }
-#undef GDN_RING
-#undef GDN_RING2
+                bool launched = false;                              // (stays false for 13, 512 x 128: 128 accumulator registers per lane spill)
+                if (cfg == 10) launched = launch_ring<256, 64>(rp.kw, rp.G, st, P);
+                else if (cfg == 11) launched = launch_ring<256, 128>(rp.kw, rp.G, st, P);
+                else if (cfg == 12) launched = launch_ring<512, 64>(rp.kw, rp.G, st, P);
+                if (!launched) return GDN_ERR_UNSUPPORTED;
                 if (rp.parts > 1) {
                     // the tail ranges' slabs -> y / stats for the pixels [main_mtiles * 256, M) (a dense pixel range: ring layers have
                     // one phase and unit stride, so output pixel index == m)
