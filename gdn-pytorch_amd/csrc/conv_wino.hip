@@ -370,15 +370,46 @@ constexpr float W4_P = W4_A2 * W4_B2, W4_S = W4_A2 + W4_B2;                     
 constexpr float W4_I0 = (float)(1.0 / ((double)W4_A2 * W4_B2));                                  // 1 / N_0
 constexpr float W4_IA = (float)(1.0 / (2.0 * W4_A2 * ((double)W4_A2 - W4_B2)));                  // 1 / N_a = 1 / N_-a
 constexpr float W4_IB = (float)(1.0 / (2.0 * W4_B2 * ((double)W4_B2 - W4_A2)));                  // 1 / N_b = 1 / N_-b
-__device__ __forceinline__ void w4_bt(const float (&d)[6], float (&o)[6]) {
-    const float ea = d[4] - W4_B2 * d[2], oa = W4_A * (d[3] - W4_B2 * d[1]);
-    const float eb = d[4] - W4_A2 * d[2], ob = W4_B * (d[3] - W4_A2 * d[1]);
-    o[0] = W4_P * d[0] - W4_S * d[2] + d[4];
-    o[1] = ea + oa;
-    o[2] = ea - oa;
-    o[3] = eb + ob;
-    o[4] = eb - ob;
-    o[5] = W4_P * d[1] - W4_S * d[3] + d[5];
+// B^T (6x6) and A^T (4x6) are PINNED: no contraction by the compiler, a fused multiply-add exactly where it is written.  Left to
+// the compiler, which products fuse depends on the code around the call (a select next to a load is enough to move one), and
+// every rescheduling of a transform kernel would change what training computes.  The forms below are the ones the compiler
+// had chosen for the input / output transforms when they were pinned (recovered by matching candidate forms against the
+// kernels' output bits) -- they were not the same in every instance, hence the switches:
+//   W4_FP / W4_FS / W4_F0   rows 0 and 5,  P x - S y + z :  fma(P, x, -(S y)) + z  /  fma(-S, y, P x) + z  /  (P x - S y) + z
+//   fodd                    rows 1..4,  e +- k i :  fma(+-k, i, e)  or  e +- (k i)        (e and i are always fused)
+// w4_g, w4_gw and w4_awt (weight and weight-gradient transforms) are still the compiler's choice, each in its own kernel(s).
+enum { W4_FP = 0, W4_FS = 1, W4_F0 = 2 };
+__device__ __forceinline__ float w4_bt_edge(int f, float x, float y, float z) {
+#pragma clang fp contract(off)
+    if (f == W4_FP) return __builtin_fmaf(W4_P, x, -(W4_S * y)) + z;
+    if (f == W4_FS) return __builtin_fmaf(-W4_S, y, W4_P * x) + z;
+    return (W4_P * x - W4_S * y) + z;
+}
+// (f0, fodd, f5 are constants at every call once the loops around it are unrolled)
+__device__ __forceinline__ void w4_bt(const float (&d)[6], float (&o)[6], int f0, bool fodd, int f5) {
+#pragma clang fp contract(off)
+    const float ea = __builtin_fmaf(-W4_B2, d[2], d[4]), ia = __builtin_fmaf(-W4_B2, d[1], d[3]);      // d4 - b^2 d2,  d3 - b^2 d1
+    const float eb = __builtin_fmaf(-W4_A2, d[2], d[4]), ib = __builtin_fmaf(-W4_A2, d[1], d[3]);
+    o[0] = w4_bt_edge(f0, d[0], d[2], d[4]);
+    if (fodd) {
+        o[1] = __builtin_fmaf(W4_A, ia, ea);
+        o[2] = __builtin_fmaf(-W4_A, ia, ea);
+        o[3] = __builtin_fmaf(W4_B, ib, eb);
+        o[4] = __builtin_fmaf(-W4_B, ib, eb);
+    } else {
+        const float oa = W4_A * ia, ob = W4_B * ib;
+        o[1] = ea + oa;
+        o[2] = ea - oa;
+        o[3] = eb + ob;
+        o[4] = eb - ob;
+    }
+    o[5] = w4_bt_edge(f5, d[1], d[3], d[5]);
+}
+// the two passes of V = B^T d B as the input transform runs them: along the rows of patch column j, then along the columns of
+// row i of the result
+__device__ __forceinline__ void w4_bt_rows(int j, const float (&d)[6], float (&o)[6]) { w4_bt(d, o, W4_FP, j != 5, W4_FP); }
+__device__ __forceinline__ void w4_bt_cols(int i, const float (&r)[6], float (&o)[6]) {
+    w4_bt(r, o, W4_F0, true, (i == 0 || i == 5) ? W4_FP : W4_FS);
 }
 __device__ __forceinline__ void w4_g(const float (&g)[3], float (&o)[6]) {        // G (6x3)
     const float ea = W4_IA * (g[0] + W4_A2 * g[2]), oa = (W4_IA * W4_A) * g[1];
@@ -401,11 +432,17 @@ __device__ __forceinline__ void w4_gw(const float (&y)[4], float (&o)[6]) {     
     o[5] = y[3];
 }
 __device__ __forceinline__ void w4_at(const float (&m)[6], float (&o)[4]) {       // A^T (4x6)
+#pragma clang fp contract(off)
     const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
     o[0] = m[0] + s12 + s34;
-    o[1] = W4_A * d12 + W4_B * d34;
-    o[2] = W4_A2 * s12 + W4_B2 * s34;
-    o[3] = W4_A3 * d12 + W4_B3 * d34 + m[5];
+    o[1] = __builtin_fmaf(W4_A, d12, W4_B * d34);
+    o[2] = __builtin_fmaf(W4_A2, s12, W4_B2 * s34);
+    o[3] = __builtin_fmaf(W4_A3, d12, W4_B3 * d34) + m[5];
+}
+// a product that is rounded on its own, never contracted into the sum it feeds (the partial sums of wino4_output_kernel)
+__device__ __forceinline__ float w4_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
 }
 __device__ __forceinline__ void w4_awt(const float (&p)[6], float (&o)[3]) {      // A_w^T (3x6)
     const float s12 = p[1] + p[2], d12 = p[1] - p[2], s34 = p[3] + p[4], d34 = p[3] - p[4];
@@ -414,17 +451,79 @@ __device__ __forceinline__ void w4_awt(const float (&p)[6], float (&o)[3]) {    
     o[2] = W4_A2 * s12 + W4_B2 * s34 + p[5];
 }
 
-// V = B^T d B of the 6x6 patch whose top-left corner is (4a - pad_off, 4b - pad_off); in_scale / up2x as wino_input_kernel
-// (zero padding only: reflection-padded layers stay on F(2x2,3x3))
+// A wave of the transform kernels is one tile (wino_decode: 64 channels of tile t), so everything derived from t -- the tile's
+// image and position, which patch rows / columns lie in the image, the row bases -- is uniform over the wave.  Computed from
+// threadIdx the compiler keeps it in vector registers; WINO_UNI moves t to a scalar register once, which makes the bounds
+// logic scalar arithmetic and every access a scalar base + the lane's channel.
+#define WINO_UNI(v) __builtin_amdgcn_readfirstlane(v)
+
+// V = B^T d B of the 6x6 patch whose top-left corner is (4a - pad_off, 4b - pad_off); in_scale as wino_input_kernel, a
+// compile-time switch here (zero padding only: reflection-padded layers stay on F(2x2,3x3)).
+// Branch-free loader: a patch element outside the image is read from the nearest pixel inside it (clamped row / column: 6 + 6
+// predicates and bases per wave, not 36 pairs) and replaced by zero with one select, so all 36 loads of a thread are in flight
+// before the first use -- per-element `if (ok)` regions made them 36 memory round trips one after another.
+template <bool INSC>
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ x, int ldx, float* __restrict__ V, WinoGeom g,
                                                           const float* __restrict__ in_scale, const float* __restrict__ in_shift,
-                                                          int in_relu, int up2x) {
-    int t, c;
-    if (!wino_decode(g.M, g.cq_shift, t, c)) return;
-    const float is = in_scale ? in_scale[c] : 1.f, it = in_scale ? in_shift[c] : 0.f;
+                                                          int in_relu) {
+    int tv, c;
+    if (!wino_decode(g.M, g.cq_shift, tv, c)) return;
+    const int t = WINO_UNI(tv);
+    float is = 1.f, it = 0.f;
+    if (INSC) { is = in_scale[c]; it = in_shift[c]; }
     const float lo = in_relu ? 0.f : -3.402823466e38f;
     const int b2 = t % g.tiles_x, a2 = (t / g.tiles_x) % g.tiles_y, img = t / (g.tiles_x * g.tiles_y);
+    const float* rowp[6];                    // patch row i (clamped into the image), column 0, channel 0
+    size_t colo[6];                          // patch column j (clamped): element offset within a row
+    bool row_ok[6], col_ok[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int iy = 4 * a2 - g.pad_off + k, ix = 4 * b2 - g.pad_off + k;
+        row_ok[k] = iy >= 0 && iy < g.H;
+        col_ok[k] = ix >= 0 && ix < g.W;
+        const int iyc = iy < 0 ? 0 : (iy < g.H ? iy : g.H - 1), ixc = ix < 0 ? 0 : (ix < g.W ? ix : g.W - 1);
+        rowp[k] = x + ((size_t)(img * g.H + iyc) * g.W) * ldx;
+        colo[k] = (size_t)ixc * ldx;
+    }
+    float d[6][6];                           // d[j][i]: patch column j, row i
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) d[j][i] = (rowp[i] + colo[j])[(unsigned)c];
     float r[6][6];                           // B^T along rows, one patch column at a time
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            float v = d[j][i];
+            if (INSC) v = fmaxf(v * is + it, lo);
+            d[j][i] = (row_ok[i] && col_ok[j]) ? v : 0.f;
+        }
+        float o[6];
+        w4_bt_rows(j, d[j], o);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) r[i][j] = o[i];
+    }
+    float* dst = V + (size_t)t * g.C + c;
+    const size_t bs = (size_t)g.M * g.C;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {            // ... and along columns
+        float o[6];
+        w4_bt_cols(i, r[i], o);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) { dst[0] = o[j]; dst += bs; GDN_KEEP(dst); }
+    }
+}
+
+// The same on a LOW-resolution x [B][H/2][W/2][ldx]: the x2 bilinear upsampling happens on load (up2x.h; up2x - 1 =
+// align_corners).  Only the legacy network's flipped-tap layer runs it, so it keeps the per-element loader; no BatchNorm-on-load
+// here (gdn_winoconv_fwd refuses the combination).
+__global__ __launch_bounds__(256) void wino4_input_up2x_kernel(const float* __restrict__ x, int ldx, float* __restrict__ V, WinoGeom g,
+                                                               int up2x) {
+    int t, c;
+    if (!wino_decode(g.M, g.cq_shift, t, c)) return;
+    const int b2 = t % g.tiles_x, a2 = (t / g.tiles_x) % g.tiles_y, img = t / (g.tiles_x * g.tiles_y);
+    float r[6][6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         const int ix = 4 * b2 - g.pad_off + j;
@@ -436,31 +535,25 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
             const bool ok = col_ok && iy >= 0 && iy < g.H;
             float v = 0.f;
             if (ok) {
-                if (up2x) {
-                    // x is the LOW-resolution tensor [B][H/2][W/2][ldx]: the x2 bilinear upsampling happens here (up2x.h)
-                    const int Hl = g.H >> 1, Wl = g.W >> 1;
-                    float ly, lx; int y0, y1, x0, x1;
-                    up_src(iy, Hl, up2x - 1, ly, y0, y1);
-                    up_src(ix, Wl, up2x - 1, lx, x0, x1);
-                    v = up2x_at(x + ((size_t)(img * Hl + y0) * Wl) * ldx + c, x + ((size_t)(img * Hl + y1) * Wl) * ldx + c, ldx, ly, x0, x1, lx);
-                } else {
-                    v = x[((size_t)(img * g.H + iy) * g.W + ix) * ldx + c];
-                    if (in_scale) v = fmaxf(v * is + it, lo);
-                }
+                const int Hl = g.H >> 1, Wl = g.W >> 1;
+                float ly, lx; int y0, y1, x0, x1;
+                up_src(iy, Hl, up2x - 1, ly, y0, y1);
+                up_src(ix, Wl, up2x - 1, lx, x0, x1);
+                v = up2x_at(x + ((size_t)(img * Hl + y0) * Wl) * ldx + c, x + ((size_t)(img * Hl + y1) * Wl) * ldx + c, ldx, ly, x0, x1, lx);
             }
             d[i] = v;
         }
         float o[6];
-        w4_bt(d, o);
+        w4_bt_rows(j, d, o);
 #pragma unroll
         for (int i = 0; i < 6; ++i) r[i][j] = o[i];
     }
     float* dst = V + (size_t)t * g.C + c;
     const size_t bs = (size_t)g.M * g.C;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {            // ... and along columns
+    for (int i = 0; i < 6; ++i) {
         float o[6];
-        w4_bt(r[i], o);
+        w4_bt_cols(i, r[i], o);
 #pragma unroll
         for (int j = 0; j < 6; ++j) { dst[0] = o[j]; dst += bs; GDN_KEEP(dst); }
     }
@@ -557,7 +650,11 @@ __global__ __launch_bounds__(256) void wino4_weights_x3_kernel(const float* __re
 }
 
 // y = A^T m A (4x4 outputs per tile); epilogue, BatchNorm partials and the data gradient's BatchNorm-backward partials exactly as
-// wino_output_kernel (stats slot = group of 4 tiles)
+// wino_output_kernel (stats slot = group of 4 tiles).  ADD / BNB: addsrc / bnb_y given, as compile-time switches, so that the
+// tile's 16 addsrc and 16 bnb_y values are loaded next to the 36 bins (pixels outside the image from the nearest one inside it,
+// never used) and all of them are in flight together; the 16 outputs are computed, then stored under the tile's 4 + 4 row /
+// column predicates, which are scalar (WINO_UNI).
+template <bool ADD, bool BNB>
 __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restrict__ Mo, float* __restrict__ y, int ldy,
                                                            const float* __restrict__ addsrc, int ld_add,
                                                            float* __restrict__ stats, const float* __restrict__ ep_scale,
@@ -565,11 +662,38 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
                                                            int q_shift, const float* __restrict__ bnb_y, int ld_bnb,
                                                            const float* __restrict__ bnb_co, int bnb_relu) {
     __shared__ float red[256 * 2];
-    int t, n;
-    const bool live = wino_decode(g.M, q_shift, t, n);
+    int tv, n;
+    const bool live = wino_decode(g.M, q_shift, tv, n);
     float s1 = 0.f, s2 = 0.f;
     if (live) {
+        const int t = WINO_UNI(tv);
         const int b2 = t % g.tiles_x, a2 = (t / g.tiles_x) % g.tiles_y, img = t / (g.tiles_x * g.tiles_y);
+        size_t rowpx[4];                     // first pixel of output row i (clamped into the image)
+        int colpx[4];
+        bool row_ok[4], col_ok[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int oy = 4 * a2 + k, ox = 4 * b2 + k;
+            row_ok[k] = oy < g.Ho;
+            col_ok[k] = ox < g.Wo;
+            rowpx[k] = (size_t)(img * g.Ho + (oy < g.Ho ? oy : g.Ho - 1)) * g.Wo;
+            colpx[k] = ox < g.Wo ? ox : g.Wo - 1;
+        }
+        float av[4][4], yv[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t px = rowpx[i] + colpx[j];
+                av[i][j] = ADD ? (addsrc + px * ld_add)[(unsigned)n] : 0.f;
+                yv[i][j] = BNB ? (bnb_y + px * ld_bnb)[(unsigned)n] : 0.f;
+            }
+        // (no branch around these two loads either -- the join would wait for everything issued above: without an affine they
+        // read Mo[n], which exists, and the value is dropped)
+        const float esl = (ep_scale ? ep_scale : Mo)[(unsigned)n], etl = (ep_shift ? ep_shift : Mo)[(unsigned)n];
+        const float es = ep_scale ? esl : 1.f, et = ep_shift ? etl : 0.f;
+        float bsc = 0.f, bt = 0.f, bmu = 0.f, bis = 0.f;
+        if (BNB) { bsc = bnb_co[n]; bt = bnb_co[Nout + n]; bmu = bnb_co[2 * Nout + n]; bis = bnb_co[3 * Nout + n]; }
         float r[4][6];                       // A^T along rows, one bin column at a time
         const float* src = Mo + (size_t)t * Nout + n;
         const size_t bs = (size_t)g.M * Nout;
@@ -588,34 +712,33 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
                 for (int i = 0; i < 4; ++i) r[i][j] = o[i];
             }
         }
-        const float es = ep_scale ? ep_scale[n] : 1.f, et = ep_shift ? ep_shift[n] : 0.f;
-        float bsc = 0.f, bt = 0.f, bmu = 0.f, bis = 0.f;
-        if (bnb_y) { bsc = bnb_co[n]; bt = bnb_co[Nout + n]; bmu = bnb_co[2 * Nout + n]; bis = bnb_co[3 * Nout + n]; }
+        float out[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float o[4];
             w4_at(r[i], o);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int oy = 4 * a2 + i, ox = 4 * b2 + j;
-                if (oy < g.Ho && ox < g.Wo) {
-                    float val = o[j];
-                    if (!bnb_y) { s1 += val; s2 += val * val; }
-                    if (ep_scale) val = val * es + et;
-                    if (act & GDN_ACT_RELU) val = fmaxf(val, 0.f);
-                    const size_t px = (size_t)(img * g.Ho + oy) * g.Wo + ox;
-                    if (addsrc) val += addsrc[px * ld_add + n];
-                    if (act & GDN_ACT_TANH) val = tanhf(val);
-                    y[px * ldy + n] = val;
-                    if (bnb_y) {
-                        const float yv = bnb_y[px * ld_bnb + n];
-                        float dz = val;
-                        if (bnb_relu && !(yv * bsc + bt > 0.f)) dz = 0.f;
-                        s1 += dz; s2 += dz * ((yv - bmu) * bis);
-                    }
+                const bool ok = row_ok[i] && col_ok[j];
+                float val = o[j];
+                if (!BNB) { s1 = ok ? s1 + val : s1; s2 = ok ? s2 + w4_mul_rn(val, val) : s2; }
+                if (ep_scale) val = val * es + et;
+                if (act & GDN_ACT_RELU) val = fmaxf(val, 0.f);
+                if (ADD) val += av[i][j];
+                if (act & GDN_ACT_TANH) val = tanhf(val);
+                out[i][j] = val;
+                if (BNB) {
+                    float dz = val;
+                    if (bnb_relu && !(yv[i][j] * bsc + bt > 0.f)) dz = 0.f;
+                    s1 = ok ? s1 + dz : s1; s2 = ok ? s2 + w4_mul_rn(dz, (yv[i][j] - bmu) * bis) : s2;
                 }
             }
         }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (row_ok[i] && col_ok[j]) (y + (rowpx[i] + colpx[j]) * ldy)[(unsigned)n] = out[i][j];
     }
     if (stats) {
         red[threadIdx.x * 2] = s1; red[threadIdx.x * 2 + 1] = s2;
@@ -721,6 +844,26 @@ inline int tn_splits_max(const WinoGeom& f) {
     return a > b ? a : b;
 }
 
+// F(4x4,3x3) data transforms: the instantiation that holds exactly what the call uses
+inline void launch_wino4_input(const float* x, int ldx, float* V, const WinoGeom& f, const float* in_scale, const float* in_shift,
+                               int in_relu, int up2x, hipStream_t st) {
+    const dim3 grid(cdiv(f.M, 4) << f.cq_shift), blk(256);
+    if (up2x) hipLaunchKernelGGL(wino4_input_up2x_kernel, grid, blk, 0, st, x, ldx, V, f, up2x);
+    else if (in_scale) hipLaunchKernelGGL(wino4_input_kernel<true>, grid, blk, 0, st, x, ldx, V, f, in_scale, in_shift, in_relu);
+    else hipLaunchKernelGGL(wino4_input_kernel<false>, grid, blk, 0, st, x, ldx, V, f, in_scale, in_shift, in_relu);
+}
+// (f: the geometry whose tiles are the OUTPUT's; Nout / q_shift: the output's channels)
+inline void launch_wino4_output(const float* Mo, float* y, int ldy, const float* addsrc, int ld_add, float* stats,
+                                const float* ep_scale, const float* ep_shift, int act, const WinoGeom& f, int Nout, int q_shift,
+                                const float* bnb_y, int ld_bnb, const float* bnb_co, int bnb_relu, hipStream_t st) {
+    const dim3 grid(cdiv(f.M, 4) << q_shift), blk(256);
+#define W4_OUT(A, Bn) hipLaunchKernelGGL((wino4_output_kernel<A, Bn>), grid, blk, 0, st, Mo, y, ldy, addsrc, ld_add, stats, ep_scale, \
+                                         ep_shift, act, f, Nout, q_shift, bnb_y, ld_bnb, bnb_co, bnb_relu)
+    if (addsrc) { if (bnb_y) W4_OUT(true, true); else W4_OUT(true, false); }
+    else { if (bnb_y) W4_OUT(false, true); else W4_OUT(false, false); }
+#undef W4_OUT
+}
+
 }  // namespace
 
 // saved state of one forward for its backward: the transformed input V, then the data gradient's transformed weights
@@ -761,14 +904,12 @@ extern "C" int gdn_winoconv_fwd(const gdn_conv_geom* g, const float* x, int32_t 
     float* Usw = state_out ? (float*)((char*)state_out + v_bytes(f)) : nullptr;
     if (f.T == 4) {
         // F(4x4,3x3): every GEMM of the layer is a bf16 x 3 one (wino_geom); the data gradient's weight set rides along as above
-        hipLaunchKernelGGL(wino4_input_kernel, dim3(cdiv(f.M, 4) << f.cq_shift), dim3(256), 0, st, x, ldx, V, f, in_scale, in_shift,
-                           in_relu, in_up2x);
+        launch_wino4_input(x, ldx, V, f, in_scale, in_shift, in_relu, in_up2x, st);
         hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256), Usw ? 2 : 1), dim3(256), 0, st, w, (unsigned char*)U, f.N,
                            f.C, f.flip, (unsigned char*)Usw, 1 | f.flip);
         launch_gemm_x3_nt((const float*)V, U, Mo, f.bins, f.M, f.N, f.C, st);
-        hipLaunchKernelGGL(wino4_output_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, (const float*)Mo, y, ldy, addsrc,
-                           ld_add, stats, ep_scale, ep_shift, act, f, f.N, f.nq_shift, (const float*)nullptr, 0,
-                           (const float*)nullptr, 0);
+        launch_wino4_output((const float*)Mo, y, ldy, addsrc, ld_add, stats, ep_scale, ep_shift, act, f, f.N, f.nq_shift,
+                            (const float*)nullptr, 0, (const float*)nullptr, 0, st);
         return gdn_launch_status();
     }
     hipLaunchKernelGGL(wino_input_kernel, dim3(cdiv(f.M, 4) << f.cq_shift), dim3(256), 0, st, x, ldx, V, f, in_scale, in_shift,
@@ -846,16 +987,14 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
         if (dx) {
             WinoGeom fd = f;
             fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift;
-            hipLaunchKernelGGL(wino4_input_kernel, dim3(cdiv(fd.M, 4) << fd.cq_shift), dim3(256), 0, st, dy, ldy, Vd, fd,
-                               (const float*)nullptr, (const float*)nullptr, 0, 0);
+            launch_wino4_input(dy, ldy, Vd, fd, nullptr, nullptr, 0, 0, st);
             const float* Ud = U;
             if (state) Ud = (const float*)((const char*)state + v_bytes(f));      // transformed by the forward's launch
             else hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1 | f.flip,
                                     (unsigned char*)nullptr, 0);
             launch_gemm_x3_nt((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, st);
-            hipLaunchKernelGGL(wino4_output_kernel, dim3(cdiv(fd.M, 4) << fd.nq_shift), dim3(256), 0, st, (const float*)Eo, dx, ldx,
-                               addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0,
-                               fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu);
+            launch_wino4_output((const float*)Eo, dx, ldx, addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, nullptr, nullptr, 0,
+                                fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu, st);
         }
         return gdn_launch_status();
     }
@@ -952,8 +1091,7 @@ extern "C" int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, in
     WinoGeom fd = f;
     fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift;
     if (phases & 1) {
-        hipLaunchKernelGGL(wino4_input_kernel, dim3(cdiv(fd.M, 4) << fd.cq_shift), dim3(256), 0, st, dy, ldy, Vd, fd,
-                           (const float*)nullptr, (const float*)nullptr, 0, 0);
+        launch_wino4_input(dy, ldy, Vd, fd, nullptr, nullptr, 0, 0, st);
         hipLaunchKernelGGL(wino4_dy_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, dy, ldy, Dv, f);
     }
     if (phases & 2) {
@@ -964,9 +1102,8 @@ extern "C" int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, in
     if (phases & 4) {
         const float* Ud = (const float*)((const char*)state + v_bytes(f));
         launch_gemm_x3_nt((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, st);
-        hipLaunchKernelGGL(wino4_output_kernel, dim3(cdiv(fd.M, 4) << fd.nq_shift), dim3(256), 0, st, (const float*)Eo, dx, ldx,
-                           addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0,
-                           fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu);
+        launch_wino4_output((const float*)Eo, dx, ldx, addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, nullptr, nullptr, 0,
+                            fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu, st);
     }
     return gdn_launch_status();
 }
