@@ -937,6 +937,136 @@ __global__ __launch_bounds__(256) void lr_schedule_kernel(float* __restrict__ hy
     hyper[6 * k] = (float)(base_lr[k] * s);
 }
 
+// ---- per-step training record kept on the device (include/gdn_hip.h): one wave writes row count % cap of a
+// ring of 64-byte rows from records that already sit in device memory, then advances the counter.  Lane j < 16 stores dword j
+// of the row; floats travel as bit patterns (a NaN keeps its payload, -0 its sign).  The term pointers ride in the argument
+// block.  Ordinary loads and stores, no atomics: calls on one stream are ordered.
+struct StepRecordTerms { const float* p[8]; };
+constexpr unsigned STEP_RECORD_QNAN = 0x7fc00000u;
+__global__ __launch_bounds__(64) void step_record_kernel(unsigned long long* __restrict__ ring, int cap, StepRecordTerms terms,
+                                                         int n_terms, const float* __restrict__ hyper, const AdamDevState* st,
+                                                         const AdamGuard* guard) {
+    const int l = (int)threadIdx.x;
+    const unsigned long long count = ring[0];
+    unsigned* __restrict__ row = reinterpret_cast<unsigned*>(ring + 8 + 8 * (count % (unsigned long long)cap));
+    if (l < 16) {
+        unsigned v = STEP_RECORD_QNAN;
+        if (l == 0) v = (unsigned)count;
+        else if (l == 1) v = (unsigned)(count >> 32);
+        else if (l == 2) v = st != nullptr ? (unsigned)st->step : 0xffffffffu;
+        else if (l == 3) v = guard != nullptr ? (unsigned)guard->skip : 0xffffffffu;
+        else if (l == 4) { if (hyper != nullptr) v = __float_as_uint(hyper[0]); }
+        else if (l == 5) { if (guard != nullptr) v = __float_as_uint(guard->norm); }
+        else if (l == 6) { if (guard != nullptr) v = __float_as_uint(guard->coef); }
+        else if (l == 7) v = (unsigned)n_terms;
+        else {
+            const float* src = nullptr;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (l == 8 + j && j < n_terms) src = terms.p[j];
+            if (src != nullptr) v = *reinterpret_cast<const unsigned*>(src);
+        }
+        row[l] = v;
+    }
+    __syncthreads();       // every lane has read the counter and written its dword
+    if (l == 0) ring[0] = count + 1ull;
+}
+
+// ---- per-tensor sums of squares of the weights and the gradient over an arena's slices (include/gdn_hip.h).
+// Work items are (segment, slab of TSS_SLAB floats): tss_items_kernel turns the segment table into first[k], the index of
+// segment k's first item (first[T]: the number of items); tss_partial_kernel is one workgroup per item -- it finds its segment
+// by bisection of `first`, streams its slab of p (and g) as float4 with four loads in flight per array, and leaves one double
+// pair; tss_final_kernel is one workgroup per segment adding its items in index order.  Slabs start at multiples of 64 floats
+// from 16-byte aligned bases, so only a segment's last slab has a scalar tail (< 4 floats), and nothing outside
+// [offset, offset + length) is read.  No atomics; every addition has a fixed place.  A table entry that leaves [0, n) is cut to
+// it (the table's contents are the caller's, an out-of-range read is not).
+constexpr int64_t TSS_SLAB = 16384;
+__device__ __forceinline__ void tss_segment(const int64_t* __restrict__ seg, int k, int64_t n, int64_t& off, int64_t& len) {
+    off = seg[2 * k];
+    len = seg[2 * k + 1];
+    if (off < 0 || off >= n || len < 0) { off = 0; len = 0; }
+    if (len > n - off) len = n - off;
+}
+__global__ __launch_bounds__(256) void tss_items_kernel(const int64_t* __restrict__ seg, int T, int64_t n,
+                                                        int64_t* __restrict__ first) {
+    __shared__ int64_t sh[256];
+    int64_t carry = 0;
+    for (int k0 = 0; k0 < T; k0 += 256) {        // (block-uniform bound: every thread reaches the barriers)
+        const int k = k0 + (int)threadIdx.x;
+        int64_t items = 0;
+        if (k < T) {
+            int64_t off, len;
+            tss_segment(seg, k, n, off, len);
+            items = cdiv64(len, TSS_SLAB);
+        }
+        sh[threadIdx.x] = items;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {      // inclusive scan
+            const int64_t add = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (k < T) first[k] = carry + sh[threadIdx.x] - items;
+        carry += sh[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) first[T] = carry;
+}
+__device__ __forceinline__ double sq1_d(float a) { const double x = (double)a; return x * x; }
+__global__ __launch_bounds__(256) void tss_partial_kernel(const float* __restrict__ p, const float* __restrict__ g, int64_t n,
+                                                          const int64_t* __restrict__ seg, int T,
+                                                          const int64_t* __restrict__ first, double* __restrict__ partial) {
+    __shared__ double sh[8];
+    const int64_t item = blockIdx.x;
+    if (item >= first[T]) return;                // (block-uniform)
+    int lo = 0, hi = T;                          // the segment k with first[k] <= item < first[k + 1]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= item) lo = mid; else hi = mid;
+    }
+    int64_t off, len;
+    tss_segment(seg, lo, n, off, len);
+    const int64_t s0 = (item - first[lo]) * TSS_SLAB;
+    const int64_t cnt = len - s0 < TSS_SLAB ? len - s0 : TSS_SLAB;      // 1 .. TSS_SLAB floats of this slab
+    const int nv = (int)(cnt >> 2), tail = (int)(cnt & 3);
+    const int t = (int)threadIdx.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    const f32x4* __restrict__ pv = reinterpret_cast<const f32x4*>(p + off + s0);
+    int i = t;
+    for (; i + 768 < nv; i += 1024) {
+        const f32x4 x0 = pv[i], x1 = pv[i + 256], x2 = pv[i + 512], x3 = pv[i + 768];
+        a0 += sq4_d(x0); a1 += sq4_d(x1); a2 += sq4_d(x2); a3 += sq4_d(x3);
+    }
+    for (; i < nv; i += 256) a0 += sq4_d(pv[i]);
+    if (t < tail) a1 += sq1_d(p[off + s0 + 4 * (int64_t)nv + t]);
+    if (g != nullptr) {
+        const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + off + s0);
+        i = t;
+        for (; i + 768 < nv; i += 1024) {
+            const f32x4 x0 = gv[i], x1 = gv[i + 256], x2 = gv[i + 512], x3 = gv[i + 768];
+            b0 += sq4_d(x0); b1 += sq4_d(x1); b2 += sq4_d(x2); b3 += sq4_d(x3);
+        }
+        for (; i < nv; i += 256) b0 += sq4_d(gv[i]);
+        if (t < tail) b1 += sq1_d(g[off + s0 + 4 * (int64_t)nv + t]);
+    }
+    const double sp = block_sum_d256((a0 + a1) + (a2 + a3), sh);
+    const double sg = block_sum_d256((b0 + b1) + (b2 + b3), sh + 4);
+    if (t == 0) { partial[2 * item] = sp; partial[2 * item + 1] = sg; }
+}
+__global__ __launch_bounds__(256) void tss_final_kernel(const int64_t* __restrict__ first, const double* __restrict__ partial,
+                                                        int64_t max_items, double* __restrict__ out) {
+    __shared__ double sh[8];
+    const int k = (int)blockIdx.x;
+    const int64_t lo = first[k];
+    const int64_t hi = first[k + 1] < max_items ? first[k + 1] : max_items;
+    double a = 0.0, b = 0.0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+    const double sp = block_sum_d256(a, sh);
+    const double sg = block_sum_d256(b, sh + 4);
+    if (threadIdx.x == 0) { out[2 * k] = sp; out[2 * k + 1] = sg; }
+}
+
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
@@ -1592,6 +1722,44 @@ extern "C" int gdn_lr_schedule(float* hyper, const double* base_lr, const void* 
     if (((uintptr_t)hyper & 3) || ((uintptr_t)base_lr & 7) || ((uintptr_t)states & 7)) return GDN_ERR_BAD_ARG;
     hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(G <= 64 ? 64 : 256), 0, ST(stream), hyper, base_lr,
                        (const AdamDevState*)states, (int)G, (int)kind, (int)warmup, (int)total, floor);
+    return gdn_launch_status();
+}
+
+extern "C" int gdn_step_record(void* ring, int32_t cap, const float* const* terms, int32_t n_terms, const float* hyper,
+                               const void* state, const void* guard, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!ring || cap < 1 || n_terms < 0 || n_terms > 8 || (n_terms > 0 && !terms)) return GDN_ERR_BAD_ARG;
+    if (((uintptr_t)ring & 7) || ((uintptr_t)state & 7) || ((uintptr_t)guard & 7) || ((uintptr_t)hyper & 3)) return GDN_ERR_BAD_ARG;
+    StepRecordTerms t;
+    for (int j = 0; j < 8; ++j) {
+        t.p[j] = j < n_terms ? terms[j] : nullptr;
+        if (j < n_terms && (!t.p[j] || ((uintptr_t)t.p[j] & 3))) return GDN_ERR_BAD_ARG;
+    }
+    hipLaunchKernelGGL(step_record_kernel, dim3(1), dim3(64), 0, ST(stream), (unsigned long long*)ring, (int)cap, t, (int)n_terms,
+                       hyper, (const AdamDevState*)state, (const AdamGuard*)guard);
+    return gdn_launch_status();
+}
+
+// items of the streaming pass: every segment's last slab may be short, so at most cdiv(n, slab) + T of them
+static int64_t tss_max_items(int64_t n, int32_t T) { return cdiv64(n, TSS_SLAB) + (int64_t)T; }
+extern "C" size_t gdn_tensor_sumsq_workspace_bytes(int64_t n, int32_t T) {
+    if (n <= 0 || T < 1) return 0;
+    return ((size_t)T + 1) * sizeof(int64_t) + (size_t)tss_max_items(n, T) * 2 * sizeof(double);
+}
+extern "C" int gdn_tensor_sumsq(const float* p, const float* g, int64_t n, const int64_t* seg, int32_t T, double* out,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
+    if (!p || !seg || !out || !workspace || n <= 0 || T < 1) return GDN_ERR_BAD_ARG;
+    if ((((uintptr_t)p | (uintptr_t)g) & 15) || (((uintptr_t)seg | (uintptr_t)out | (uintptr_t)workspace) & 7)) return GDN_ERR_BAD_ARG;
+    const int64_t max_items = tss_max_items(n, T);
+    if (max_items > 0x7fffffff || workspace_bytes < gdn_tensor_sumsq_workspace_bytes(n, T)) return GDN_ERR_BAD_ARG;
+    int64_t* first = (int64_t*)workspace;
+    double* partial = (double*)(first + T + 1);
+    hipLaunchKernelGGL(tss_items_kernel, dim3(1), dim3(256), 0, ST(stream), seg, (int)T, n, first);
+    hipLaunchKernelGGL(tss_partial_kernel, dim3((unsigned)max_items), dim3(256), 0, ST(stream), p, g, n, seg, (int)T,
+                       (const int64_t*)first, partial);
+    hipLaunchKernelGGL(tss_final_kernel, dim3(T), dim3(256), 0, ST(stream), (const int64_t*)first, (const double*)partial,
+                       max_items, out);
     return gdn_launch_status();
 }
 

@@ -76,6 +76,14 @@ takes it off gamma / beta.  It runs with ``--graph``, ``--resume``, ``--accum_st
 ``--freeze`` / ``--lr_mult``, the schedules, ``--loss silog`` and bf16; the optimizer state in ``train_state.pt`` says which
 rule wrote it and a resumed run must repeat the flag.  ``--weight-decay`` stays accepted and ignored.  ``--optimizer adam`` is
 the run without the flag.
+``--train_log PATH`` keeps a per-step record of the run: one small launch per step copies the loss terms, the
+update count, the rate and the gradient guard's norm, coefficient and skip decision -- all already in device memory -- into a
+device ring, ``--graph`` replays it, and the host reads the ring with one asynchronous copy every ``--train_log_every N`` steps
+(256) and writes JSON lines; ``--tensor_norms_every M`` adds the norm of every parameter tensor and of its gradient every M
+steps, one deterministic pass over the arena.  The update columns are ``null`` where the run keeps no such device record: the
+flag never changes which optimizer path runs (``--skip_nonfinite`` alone gives the norm column without clipping).  Rank 0
+writes; no wall-clock value enters the file, so the same run writes the same bytes; ``--resume`` continues the file after the
+resumed step and refuses one whose header is another run's.  ``python -m gdn_amd.trainlog PATH [--top K]`` summarises it.
 """
 import contextlib
 import io
@@ -238,6 +246,23 @@ def _check_optimizer(args):
                            "the flag)")
     if adamw and args.mode in TEST_MODES:
         raise RuntimeError("--optimizer adamw is the update rule of a training run; --mode %s trains nothing" % args.mode)
+
+
+def _check_train_log(args):
+    """--train_log / --train_log_every / --tensor_norms_every record a training run; checked before anything touches the GPU."""
+    path, every, norms = option.train_log_spec(args)
+    if not path:
+        given = [k for k in ("train_log_every", "tensor_norms_every") if getattr(args, k, None) is not None]
+        if given:
+            raise RuntimeError("%s set(s) the cadence of the training log, which --train_log PATH opens (add it, or drop the "
+                               "flag)" % ", ".join("--" + k for k in given))
+        return
+    if args.mode in TEST_MODES:
+        raise RuntimeError("--train_log records the steps of a training run; --mode %s trains nothing" % args.mode)
+    if every < 1:
+        raise RuntimeError("--train_log_every %d: the device ring holds at least one row" % every)
+    if norms < 0:
+        raise RuntimeError("--tensor_norms_every %d is negative (0: no tensor norms)" % norms)
 
 
 def _announce_optimizer(args, rank):
@@ -420,6 +445,7 @@ def run(args, train_loader=None, val_loader=None):
     _check_accum(args)
     _check_schedule(args)
     _check_optimizer(args)
+    _check_train_log(args)
     _check_loss(args, train_loader)
     _check_freeze_bn(args)
     _check_eval(args)

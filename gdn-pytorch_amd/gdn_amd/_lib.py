@@ -154,6 +154,9 @@ _SIGS = {
     "gdn_adamw_step_dev": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P]),
     "gdn_adamw_step_dev_guarded": (c_int32, [_P, _P, _P, _P, _i64, _P, _P, _P, _P]),
     "gdn_adamw_step_seg": (c_int32, [_P, _P, _P, _P, _i64, _P, _i32, _P, _P, _P, _P]),
+    "gdn_step_record": (c_int32, [_P, _i32, _P, _i32, _P, _P, _P, _P]),
+    "gdn_tensor_sumsq_workspace_bytes": (_sz, [_i64, _i32]),
+    "gdn_tensor_sumsq": (c_int32, [_P, _P, _i64, _P, _i32, _P, _P, _sz, _P]),
     "gdn_clock_probe_arm": (c_int32, [_P, _P]),
     "gdn_clock_probe_watch": (c_int32, [_P, c_uint64, _P]),
     "gdn_clock_probe_stop": (c_int32, [_P, _P]),
@@ -166,7 +169,7 @@ EXPORTS = tuple(_SIGS)
 # _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
 # and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule, gdn_silog_masked and the
 # evaluation entry points gdn_depth_metrics_std*, gdn_flip_w and gdn_flip_mean, and the four gdn_adamw_step* entry points of
-# the decoupled weight decay, for the same reason.)
+# the decoupled weight decay, and gdn_step_record and gdn_tensor_sumsq* of the training log, for the same reason.)
 ABI_VERSION = 223
 
 

@@ -100,10 +100,13 @@ class GraphedDataParallelStep:
     (ParamArena.carry_reduced) and, at world > 1, utils.GLOBAL_BERHU, whose all-reduce(MAX) sits inside the loss.
     At world 1 sync_gradients() does nothing and the class is GraphedTrainStep in two launches.
 
+    after_step(outputs): captured into graph B right after ``optimizer.step()`` (the trainer's --train_log record, which reads
+    A's static outputs and the optimizer's device records); the warm-up steps of a capture that is not prewarmed do not call it.
+
     prewarmed / warmup: as for GraphedTrainStep; the eager steps before a prewarmed capture must have gone through
     sync_gradients(model, optimizer), which leaves optimizer.grad_scale = 1/world -- the value graph B is captured with."""
 
-    def __init__(self, fwd_bwd_fn, model, optimizer, example_inputs, prewarmed=False, warmup=3):
+    def __init__(self, fwd_bwd_fn, model, optimizer, example_inputs, prewarmed=False, warmup=3, after_step=None):
         from . import utils as U
         _need_capturable(optimizer, "GraphedDataParallelStep")
         world = D.world_size()
@@ -148,6 +151,8 @@ class GraphedDataParallelStep:
         self.graph_b = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_b):
             optimizer.step()
+            if after_step is not None:
+                after_step(out)                      # (the training log's record: part of graph B)
         counts = optimizer.take_back_counts(before)
         if not prewarmed:                            # (as GraphedTrainStep always did: the capture counts as a step taken)
             optimizer.count_replay(counts)

@@ -1491,3 +1491,41 @@ def grad_accumulate(acc, g):
     if acc.numel() != g.numel():
         raise GdnError("grad_accumulate: %d and %d elements" % (acc.numel(), g.numel()))
     lib.gdn_grad_accumulate(_p(acc), _p(g), acc.numel(), stream())
+
+
+STEP_RECORD_ROW = 64          # bytes of a ring row and of the ring's header (gdn_step_record)
+STEP_RECORD_TERMS = 8         # loss terms a row holds
+
+
+def step_record(ring, cap, terms, hyper=None, state=None, guard=None):
+    """One row of the training log's device ring (gdn_step_record): row count % cap takes the bit patterns of the 0-dim float32
+    device tensors `terms` (at most 8), the rate in hyper[0], the update count of the step state and the guard's norm,
+    coefficient and skip decision -- each of the three records may be None -- and the ring's counter advances.  ring: uint8
+    [64 + 64 * cap] on the device, zeroed once.  One launch, no sync, capturable."""
+    n = len(terms)
+    if ring.dtype != torch.uint8 or ring.numel() != STEP_RECORD_ROW * (1 + int(cap)) or not ring.is_contiguous():
+        raise GdnError("step_record: a ring of %d %s elements for %d rows" % (ring.numel(), ring.dtype, cap))
+    if n > STEP_RECORD_TERMS or any(t is not None and (t.dtype != torch.float32 or t.numel() != 1 or not t.is_cuda) for t in terms):
+        raise GdnError("step_record: the terms must be at most %d float32 scalars on the GPU" % STEP_RECORD_TERMS)
+    ptrs = (ctypes.c_void_p * STEP_RECORD_TERMS)(*[_p(t) for t in terms])
+    lib.gdn_step_record(_p(ring), int(cap), ptrs, n, _p(hyper), _p(state), _p(guard), stream())
+
+
+def tensor_sumsq(p, g, seg, out=None):
+    """out[k] = (sum p[i]^2, sum g[i]^2) in double over segment k = seg[k] = (offset, length) of the float32 buffers p and g
+    (g may be None: zeros), in a fixed order, padding between segments not read (gdn_tensor_sumsq).  seg: int64 [T, 2] on the
+    device, offsets multiples of 64, ascending, inside the buffer -- the caller's to check.  Returns out, float64 [T, 2]."""
+    n, T = p.numel(), seg.shape[0]
+    if seg.dtype != torch.int64 or seg.dim() != 2 or seg.shape[1] != 2 or not seg.is_contiguous() or not seg.is_cuda:
+        raise GdnError("tensor_sumsq: seg must be a dense int64 [T, 2] tensor on the GPU")
+    if p.dtype != torch.float32 or not p.is_contiguous() or (g is not None and (g.dtype != torch.float32 or g.numel() != n or
+                                                                                 not g.is_contiguous())):
+        raise GdnError("tensor_sumsq: p and g must be dense float32 buffers of one size")
+    if out is None:
+        out = torch.empty((T, 2), dtype=torch.float64, device=p.device)
+    elif out.dtype != torch.float64 or out.numel() != 2 * T or not out.is_contiguous():
+        raise GdnError("tensor_sumsq: out must be a dense float64 [T, 2] tensor")
+    nb = int(lib.gdn_tensor_sumsq_workspace_bytes(n, T))
+    ws = workspace(nb, p.device, "tensor_sumsq")
+    lib.gdn_tensor_sumsq(_p(p), _p(g), n, _p(seg), T, _p(out), _p(ws), nb, stream())
+    return out

@@ -635,6 +635,23 @@ class Adam(torch.optim.Optimizer):
                     out[gi] = rates[k]
         return out
 
+    def log_records(self, arena):
+        """(hyper row, step state, guard record) of param group 0 in `arena`'s store, as the device tensors the update kernels
+        read -- what ops.step_record copies into the training log; None for each record this optimizer does
+        not keep on the device (a host-stepped optimizer keeps none, an unguarded one no guard record), or before the first
+        step made it.  No device work, no read: safe inside a graph capture."""
+        st = None if arena is None else self._stores.get(id(arena))
+        if not self.capturable or st is None:
+            return None, None, None
+        hyper = state = None
+        table = st.plan if st.plan is not None else st.table
+        if table is not None and table.param_groups is not None:
+            k = next((k for k, g in enumerate(table.param_groups) if g is self.param_groups[0]), None)
+            if k is not None:
+                row = table.row(k)
+                hyper, state = row.hyper, row.state
+        return hyper, state, self._guard if self.guarded else None
+
     # ---- weight average ----------------------------------------------------------------------------------------------
     def _ema_views(self):
         """id(param) -> its average as a view in the parameter's logical shape, for every parameter a store averages."""

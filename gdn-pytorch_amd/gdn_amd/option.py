@@ -3,7 +3,8 @@ plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global
 --init_from, --save_state, --save_state_every, --resume, --clip_grad_norm, --skip_nonfinite, --ema_decay, --graph,
 --graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm, --warmup_steps, --lr_schedule,
 --lr_floor, --loss, --silog_lambda, --silog_weight, --silog_floor, --silog_mask, --eval_protocol, --eval_crop, --min_depth,
---max_depth, --depth_scale, --median_scaling, --flip_test, --eval_gt_list, --optimizer, --decoupled_wd).
+--max_depth, --depth_scale, --median_scaling, --flip_test, --eval_gt_list, --optimizer, --decoupled_wd, --train_log,
+--train_log_every, --tensor_norms_every).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -249,7 +250,32 @@ def build_parser():
     p.add_argument('--decoupled_wd', type=_non_negative_float, default=None, metavar='W',
                    help='with --optimizer adamw: the decoupled weight decay, >= 0 (when not given: 1e-2, torch.optim.AdamW\'s '
                         'default, a common choice that is not tuned here); --no_decay_norm takes it off the 1-D parameters')
+    p.add_argument('--train_log', type=str, default=None, metavar='PATH',
+                   help='training: write a JSON-lines record of every step to PATH (DESIGN.md 3.14): the loss terms, the '
+                        'update count, the rate, the gradient norm, the clip coefficient and the skip decision, copied on the '
+                        'device by one small launch per step (part of the --graph replay) and read by the host once every '
+                        '--train_log_every steps.  The update columns are null where the run keeps no such device record '
+                        '(no gradient guard, a host-stepped optimizer, a micro-batch inside an open --accum_steps group): '
+                        '--skip_nonfinite alone gives the norm column without clipping.  Rank 0 writes, of its own shard; a '
+                        'fresh run overwrites PATH, --resume continues it.  Summary: python -m gdn_amd.trainlog PATH')
+    # (None so that either cadence flag given without --train_log can be refused; train_log_spec() resolves them)
+    p.add_argument('--train_log_every', type=int, default=None, metavar='N',
+                   help='with --train_log: rows the device ring holds, which is also how often it is copied to the host, '
+                        '>= 1 (when not given: %d)' % TRAIN_LOG_EVERY_DEFAULT)
+    p.add_argument('--tensor_norms_every', type=int, default=None, metavar='M',
+                   help='with --train_log: every M steps also record the norm of every parameter tensor and of its gradient '
+                        '(as the update saw it), one deterministic pass over the arena; 0 or not given: off')
     return p
+
+
+TRAIN_LOG_EVERY_DEFAULT = 256
+
+
+def train_log_spec(args):
+    """(path or None, --train_log_every, --tensor_norms_every) with the cadence flags that were not given at their defaults."""
+    every, norms = getattr(args, "train_log_every", None), getattr(args, "tensor_norms_every", None)
+    return (getattr(args, "train_log", None) or None, TRAIN_LOG_EVERY_DEFAULT if every is None else int(every),
+            0 if norms is None else int(norms))
 
 
 DECOUPLED_WD_DEFAULT = 1e-2

@@ -11,7 +11,8 @@ and the reference's image/feature-map dumps (and the crashes listed in SURVEY 3.
 are not reproduced.
 
 Added here without a reference counterpart: exact resume (--resume / --save_state), the --graph replay of the step and
-gradient accumulation (--accum_steps K: K loader batches per Adam update).
+gradient accumulation (--accum_steps K: K loader batches per Adam update).  In the place of the reference's
+TensorBoard scalars: --train_log, a per-step record kept on the device and written as JSON lines (trainlog.py).
 """
 import os
 import time
@@ -53,7 +54,8 @@ def _save_checkpoint(model, path, optimizer=None):
 
 
 def _validate_epoch(args, val_loader, model, optimizer, epoch, logger):
-    """The per-epoch validation of both training loops; on the averaged weights where the optimizer keeps them."""
+    """The per-epoch validation of both training loops; on the averaged weights where the optimizer keeps them.  Returns
+    (names, mean errors), numbers already on the host."""
     evaluate = validate_std if option.eval_spec(args)["standard"] else validate       # --eval_protocol standard
     if _averaging(optimizer):
         with optimizer.averaged_weights():
@@ -63,6 +65,7 @@ def _validate_epoch(args, val_loader, model, optimizer, epoch, logger):
     if _is_main():
         print(('(averaged weights)' if _averaging(optimizer) else '') + ' * Avg ' +
               ', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(names, errors)))
+    return names, errors
 
 
 def load_checkpoint(model, path, map_location="cpu"):
@@ -202,6 +205,7 @@ class _StateSaver:
         self.every = max(0, int(getattr(args, "save_state_every", 0) or 0))
         self.path = save_dir + '/' + STATE_FILE
         self.objs = (model, optimizer, loader)
+        self.log = None                    # --train_log: flushed before every state file, which so never runs ahead of the log
         self.batches = len(loader) if hasattr(loader, "__len__") else None
         self.pending = self.held = False
 
@@ -228,6 +232,8 @@ class _StateSaver:
             progress["accum_steps"] = self.accum
         if self.schedule is not None:
             progress["schedule"] = self.schedule
+        if self.log is not None:
+            self.log.flush()
         save_training_state(self.path, *self.objs, progress)
         self.pending = False
 
@@ -352,6 +358,7 @@ class _EagerStep:
     one is the plain step -- fwd_bwd (forward, losses, zero_grad, backward), all-reduce, Adam -- and the no-op form of
     what the driver tells every stepper: begin_epoch(), end_epoch(), close()."""
     held = False                # a micro-batch group is open: the batch just taken has not reached the weights yet
+    log = None                  # --train_log (rank 0): trainlog.TrainLog, set by the loop driver; its record() follows the update
 
     def __init__(self, fwd_bwd, model, optimizer):
         self.fwd_bwd, self.model, self.optimizer = fwd_bwd, model, optimizer
@@ -365,7 +372,14 @@ class _EagerStep:
     def step(self, *inputs):
         terms = self.fwd_bwd(*inputs)
         self.update()
+        self.record(terms)
         return terms
+
+    def record(self, terms, updated=True):
+        """The step's row of the training log (one small launch, part of what --graph captures); updated False: a micro-batch
+        inside an open group, whose row carries no update columns."""
+        if self.log is not None:
+            self.log.record(terms, self.optimizer if updated else None)
 
     def __call__(self, i, *inputs):
         return self.step(*inputs)
@@ -405,7 +419,8 @@ class _GraphedStep(_EagerStep):
     def _capture(self, inputs, shapes):
         from .graph import GraphedDataParallelStep, GraphedTrainStep
         if D.world_size() > 1:
-            self.graphed = GraphedDataParallelStep(self.fwd_bwd, self.model, self.optimizer, inputs, prewarmed=True)
+            self.graphed = GraphedDataParallelStep(self.fwd_bwd, self.model, self.optimizer, inputs, prewarmed=True,
+                                                   after_step=self.record if self.log is not None else None)
         else:
             self.graphed = GraphedTrainStep(self.step, inputs, self.optimizer, prewarmed=True)
         self.shapes = shapes
@@ -482,12 +497,56 @@ class _GroupedStep(_EagerStep):
     def __call__(self, i, *inputs):
         terms = self.fwd_bwd(*inputs, first=self.micro == 0)
         self.micro += 1
-        if self.micro >= self.accum or i >= self.epoch_size - 1 or self.saver.last_batch(i):
+        closes = self.micro >= self.accum or i >= self.epoch_size - 1 or self.saver.last_batch(i)
+        if closes:
             self.end_epoch()
+        self.record(terms, updated=closes)
         return terms
 
     def close(self):
         self.optimizer.micro_batches = 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --train_log: the per-step record kept on the device
+def train_log_header(args, model, optimizer, accum, with_tensors):
+    """The run's description in line 1 of the training log: a function of the command line and the model alone, so a resumed
+    run computes the same one.  `tensors`: the parameter names in arena order (the arena takes model.parameters() in order),
+    only where the norms are on; `loose_parameters`: parameters of the optimizer that are not the model's, hence in no arena
+    row of the norms."""
+    mine = {id(p) for p in model.parameters()}
+    header = {"mode": args.mode, "dtype": str(getattr(args, "dtype", "fp32")), "loss": getattr(args, "loss", None) or "berhu",
+              "world": D.world_size(), "batch_size": int(getattr(args, "batch_size", 0) or 0), "accum_steps": int(accum),
+              "optimizer": getattr(args, "optimizer", None) or "adam",
+              "groups": [float(g.get("lr_mult", 1.0)) for g in optimizer.param_groups],
+              "loose_parameters": sum(1 for g in optimizer.param_groups for p in g["params"] if id(p) not in mine)}
+    if with_tensors:
+        header["tensors"] = [n for n, _ in model.named_parameters()]
+    return header
+
+
+def _open_train_log(args, cadence, model, optimizer, dev, progress, gstep, accum):
+    """(trainlog.TrainLog, --tensor_norms_every) on rank 0 of a run with --train_log; (None, 0) everywhere else: nothing is
+    allocated, launched or written.  A resumed run continues the file after its step (trainlog.LogFile)."""
+    path, every, norms_every = option.train_log_spec(args)
+    if not path or not _is_main():
+        return None, 0
+    from .trainlog import TrainLog, TrainLogError
+    try:
+        log = TrainLog(path, cadence.terms, every, dev,
+                       header=train_log_header(args, model, optimizer, accum, norms_every > 0), model=model,
+                       resume_step=None if progress is None else gstep)
+    except TrainLogError as e:
+        raise U.GdnError(str(e))
+    return log, norms_every
+
+
+def _log_arena(model, log):
+    """The trained model's arena for the norms row, whose items are the header's `tensors` in order."""
+    ar = getattr(model, "_gdn_param_arena", None)
+    if ar is None or [id(p) for p, _, _, _ in ar.items] != [id(p) for p in model.parameters()]:
+        raise U.GdnError("--tensor_norms_every: the trained model has no intact parameter arena in model.parameters() order")
+    return ar
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -502,12 +561,15 @@ class _Cadence(typing.NamedTuple):
     checkpoint_every: int
     checkpoint_each_epoch: bool     # every epoch a step has run in prints its loss and ends with a checkpoint; without it a
     #                                 run that wrote no checkpoint at all ends with one (and its state)
+    terms: tuple                    # the names of the step's loss terms, in the step's order (--train_log)
 
 
 _DTOD = _Cadence('_AE_DtoD_trained_model_lr000%d_color_uNet_gen2_nogradf', (0, 2), (5, 1900, 25), 50,
-                 "total_loss: %5f, output_loss: %5f, gradient_loss: %5f  (%.1f img/s)", 3000, True)
+                 "total_loss: %5f, output_loss: %5f, gradient_loss: %5f  (%.1f img/s)", 3000, True,
+                 ("total_loss", "output_loss", "gradient_loss"))
 _RTOD = _Cadence('_AE_RtoD_trained_model_lr000%d_color_uNet_gen2_nogradf', (1, 0, 2), (2, 2200, 60), 100,
-                 "total_loss: %5f, output_loss: %5f, smoothness_loss: %5f, latent_loss: %5f  (%.1f img/s)", 700, False)
+                 "total_loss: %5f, output_loss: %5f, smoothness_loss: %5f, latent_loss: %5f  (%.1f img/s)", 700, False,
+                 ("total_loss", "output_loss", "smoothness_loss", "latent_loss"))
 
 
 def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_epochs, lr, logger, progress):
@@ -535,6 +597,8 @@ def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_ep
         stepper = _GraphedStep(args, fwd_bwd, model, optimizer, loader, cadence.reads)
     else:
         stepper = _EagerStep(fwd_bwd, model, optimizer)
+    log, norms_every = _open_train_log(args, cadence, model, optimizer, dev, progress, gstep, accum)
+    stepper.log = saver.log = log
 
     def checkpoint(counted=True):
         nonlocal model_num
@@ -554,6 +618,11 @@ def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_ep
             terms = stepper(i, *inputs)
             seen += inputs[0].shape[0] * D.world_size()
             gstep += 1
+            if log is not None:
+                log.note(epoch, i, gstep)
+                if norms_every and gstep % norms_every == 0:
+                    # eager, outside the graph: the arena's gradient still holds this step's values
+                    log.tensor_norms(gstep, _log_arena(model, log), optimizer._scale())
             saver.stepped(gstep, stepper.held)
             if i >= epoch_size - 1:
                 break
@@ -578,7 +647,9 @@ def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_ep
             _print_guard_epoch(optimizer)
             checkpoint()
         if logger is not None and val_loader is not None:
-            _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
+            names, errors = _validate_epoch(args, val_loader, model, optimizer, epoch, logger)
+            if log is not None:
+                log.validation(gstep, epoch, names, errors)
         if saver.pending:               # after everything this epoch does: the resumed run starts the next one
             saver.save(epoch + 1, -1, lr, model_num, seen, gstep)
     if not cadence.checkpoint_each_epoch and terms is not None and model_num == 0:
@@ -588,6 +659,8 @@ def _run_loop(args, cadence, fwd_bwd, model, optimizer, loader, val_loader, n_ep
         if saver.on_checkpoint:
             saver.save(n_epochs, -1, lr, model_num, seen, gstep)
     stepper.close()
+    if log is not None:
+        log.close()
     return terms
 
 

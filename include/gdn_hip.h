@@ -911,6 +911,49 @@ int gdn_adamw_step_dev_guarded(float* p, const float* g, float* m, float* v, int
 int gdn_adamw_step_seg(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* map, int32_t G,
                        const float* hyper, void* states, const void* guard, void* stream);
 
+/* Training record kept on the device (no reference counterpart).  Both entry points follow this header's
+ * contract: no allocation, no sync, no host read, stream-ordered, capturable, every argument checked before any launch.
+ *
+ * gdn_step_record: one row per training step into a ring in device memory, from records that already live there.
+ *   ring     64 + 64 * cap bytes, 8-byte aligned, zeroed ONCE by the caller: a 64-byte header whose first 8 bytes are
+ *            uint64 count (the rest is reserved), then cap rows of 64 bytes;
+ *   terms    a HOST array of n_terms (0 .. 8) device pointers to float32 scalars (the step's loss terms).  The pointers travel
+ *            by value in the kernel's argument block: under capture the addresses of the capture are what replays read;
+ *   hyper, state, guard   one row of the Adam hyper table, one step state and the guard record, as gdn_adam_step_dev_guarded
+ *            takes them; any of them may be NULL.
+ *   One launch of one workgroup writes row count % cap and then count += 1 (calls on one stream are ordered: no atomic):
+ *     bytes  0- 7  uint64 seq      count as found
+ *            8-11  int32  t        state->t as found; -1 if state is NULL
+ *           12-15  int32  skip     guard->skip; -1 if guard is NULL
+ *           16-19  float  lr       hyper[0]; quiet NaN (0x7fc00000) if hyper is NULL
+ *           20-23  float  norm     guard->norm; quiet NaN if guard is NULL
+ *           24-27  float  coef     guard->coef; quiet NaN if guard is NULL
+ *           28-31  int32  n_terms
+ *           32-63  float  terms[8] *terms[j] for j < n_terms, quiet NaN beyond
+ *   Every float is copied as its BIT PATTERN: a NaN loss stays the NaN it is, -0 stays -0.
+ *   A NULL ring, cap < 1, n_terms outside 0 .. 8, a NULL term pointer (or array), a ring, state or guard that is not 8-byte
+ *   aligned or a hyper or term pointer that is not 4-byte aligned return GDN_ERR_BAD_ARG before any launch.
+ *
+ * gdn_tensor_sumsq: out[k] = { sum p[i]^2, sum g[i]^2 } over segment k of an arena of n floats, for T segments in one call.
+ *   seg      int64[T][2] = {offset, length} in device memory: the slices of a parameter arena -- offsets multiples of 64,
+ *            ascending, non-overlapping, offset + length <= n.  The CONTENTS of the table are the caller's to check, like the
+ *            chunk map of the segmented Adam (an entry that leaves [0, n) is cut to it: nothing outside the arena is read);
+ *   g        may be NULL: the second value of every pair is 0 and g is never read;
+ *   out      double[T][2] in device memory.
+ *   Each element is widened to double, squared (exact) and summed in double.  Floats outside every segment -- the padding -- are
+ *   NOT read; a NaN or an Inf makes its own segment's sum non-finite and no other's.  No floating-point atomics and a fixed
+ *   order of additions: the same buffers at the same addresses give the same bytes on every call.
+ *   Three launches: the segment table becomes a list of (segment, slab of 16384 floats) items; one workgroup per item streams
+ *   its slab with 16-byte loads and leaves one double pair in `workspace`; one workgroup per segment adds its pairs in order.
+ *   A NULL p, seg, out or workspace, n <= 0, T < 1, p or g not 16-byte aligned, seg, out or workspace not 8-byte aligned or
+ *   workspace_bytes < gdn_tensor_sumsq_workspace_bytes(n, T) return GDN_ERR_BAD_ARG before any launch.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+int gdn_step_record(void* ring, int32_t cap, const float* const* terms, int32_t n_terms, const float* hyper,
+                    const void* state, const void* guard, void* stream);
+size_t gdn_tensor_sumsq_workspace_bytes(int64_t n, int32_t T);
+int gdn_tensor_sumsq(const float* p, const float* g, int64_t n, const int64_t* seg, int32_t T, double* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
