@@ -29,6 +29,15 @@ static inline int gdn_plan_cus(const gdn_conv_geom* g) { const int v = (g->hints
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ---- launch helpers of the streaming kernels (pointwise.hip, optim.hip) ----
+#define ST(s) ((hipStream_t)(s))
+// blocks of a grid-stride launch: one lane per item, capped
+static inline int stream_blocks(int64_t n_items, int threads = 256, int cap = 2048) {
+    int64_t b = cdiv64(n_items, threads);
+    if (b < 1) b = 1;
+    return (int)(b < cap ? b : cap);
+}
+
 // ---- wave / block reductions (wave = 64 lanes on CDNA) ----
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

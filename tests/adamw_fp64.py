@@ -1,7 +1,8 @@
 """The decoupled update of the gdn_adamw_step* entry points (include/gdn_hip.h) restated twice: in float64, as
 the mathematics (torch.optim.AdamW up to the order of two additions), and in float32 with the header's roundings -- every
 product, sum, quotient and root rounded on its own, the one fma evaluated exactly (fractions.Fraction) and rounded once -- so
-a kernel that keeps those roundings gives these bits."""
+a kernel that keeps those roundings gives these bits.  The float32 form also restates the coupled update of gdn_adam_step*
+(coupled=True): both families go through one element of csrc/optim.hip, which differs in where the one fma sits."""
 import fractions
 import struct
 
@@ -58,29 +59,30 @@ def fma32(a, b, c):
     return out
 
 
-def step32(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2s, gscale):
-    """One update of float32 arrays with the header's roundings; returns (p, m, v)."""
+def step32(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2s, gscale, coupled=False):
+    """One update of float32 arrays with the header's roundings; returns (p, m, v).  coupled: the gdn_adam_step* element,
+    whose one fma puts the decay into the scaled gradient, gi = fma32(wd, p, round32(g * gscale)), and whose final
+    subtraction carries no decay."""
     p, g, m, v = (np.asarray(a, f32) for a in (p, g, m, v))
     lr, b1, b2, eps, wd, bc1, bc2s, gscale = (f32(x) for x in (lr, b1, b2, eps, wd, bc1, bc2s, gscale))
     with np.errstate(all="ignore"):
-        dec = dec32(lr, wd)
         step = lr / bc1
-        gi = g * gscale
+        gi = fma32(wd, p, g * gscale) if coupled else g * gscale
         mi = b1 * m + (f32(1) - b1) * gi
         vi = b2 * v + ((f32(1) - b2) * gi) * gi
         q = (step * mi) / (np.sqrt(vi) / bc2s + eps)
         assert all(a.dtype == f32 for a in (gi, mi, vi, q))
-        return p - fma32(dec, p, q), mi, vi
+        return (p - q if coupled else p - fma32(dec32(lr, wd), p, q)), mi, vi
 
 
-def run32(p, g, m, v, hyper, steps, coef=None, t0=0):
+def run32(p, g, m, v, hyper, steps, coef=None, t0=0, coupled=False):
     """`steps` updates from update count t0 with one gradient; hyper = (lr, b1, b2, eps, wd, grad_scale); under a guard the
     gradient scale is float32(grad_scale * coef)."""
     lr, b1, b2, eps, wd, gs = hyper
     gscale = f32(gs) if coef is None else f32(gs) * f32(coef)
     for t in range(t0 + 1, t0 + steps + 1):
         bc1, bc2s = corrections(b1, b2, t)
-        p, m, v = step32(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2s, gscale)
+        p, m, v = step32(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2s, gscale, coupled=coupled)
     return p, m, v
 
 

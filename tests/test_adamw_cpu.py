@@ -68,6 +68,27 @@ def test_dec_zero_is_the_coupled_element_without_decay():
     assert np.array_equal(got, p - q)
 
 
+def test_the_coupled_form_of_the_float32_restatement():
+    """step32(coupled=True), the element of gdn_adam_step*: without decay the decoupled form's bits; with it the moments see
+    g + wd p (one rounding: the fma) and the result follows torch.optim.Adam in float64 to float32 accuracy."""
+    rng = np.random.default_rng(6)
+    p, g = rng.standard_normal(256).astype(np.float32), rng.standard_normal(256).astype(np.float32)
+    z = np.zeros(256, np.float32)
+    bc1, bc2s = R.corrections(0.9, 0.999, 1)
+    for a, b in zip(R.step32(p, g, z, z, 0.5, 0.9, 0.999, 1e-8, 0.0, bc1, bc2s, 0.5, coupled=True),
+                    R.step32(p, g, z, z, 0.5, 0.9, 0.999, 1e-8, 0.0, bc1, bc2s, 0.5)):
+        assert np.array_equal(a, b)
+    got, m, v = R.step32(p, g, z, z, 0.5, 0.9, 0.999, 1e-8, 0.3, bc1, bc2s, 0.5, coupled=True)
+    gi = R.fma32(np.float32(0.3), p, g * np.float32(0.5))
+    assert np.array_equal(m, (np.float32(1) - np.float32(0.9)) * gi)
+    q = (np.float32(0.5) / bc1 * m) / (np.sqrt(v) / bc2s + np.float32(1e-8))
+    assert np.array_equal(got, p - q)
+    theirs = torch.nn.Parameter(torch.from_numpy(p.astype(np.float64)))
+    theirs.grad = torch.from_numpy(g.astype(np.float64) * 0.5)
+    torch.optim.Adam([theirs], lr=0.5, betas=(0.9, 0.999), eps=1e-8, weight_decay=float(np.float32(0.3))).step()
+    np.testing.assert_allclose(got, theirs.detach().numpy(), rtol=0, atol=4e-6)      # |p| < 8: a few float32 ulps of it
+
+
 def test_the_host_and_the_device_corrections_agree_for_the_first_updates():
     """gdn_adamw_step takes pow(beta, t) in double, the device multiplies t times: the float32 corrections the kernels read are
     the same for the betas and the counts the GPU tests compare the entry points at."""

@@ -177,9 +177,9 @@ def test_symbols_declared_built_and_bound_at_revision_223():
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert hasattr(dll, name) and name in L.EXPORTS, name
     assert L.ABI_VERSION == 223 and L.lib.gdn_version() == 223
-    src = (REPO / "gdn-pytorch_amd" / "csrc" / "pointwise.hip").read_text()
-    assert re.search(r"gdn_version\(void\)\s*\{\s*return 223;", src)
-    assert "fmaf(w, p - e, e)" in src
+    csrc = REPO / "gdn-pytorch_amd" / "csrc"
+    assert re.search(r"gdn_version\(void\)\s*\{\s*return 223;", (csrc / "pointwise.hip").read_text())
+    assert "fmaf(w, p - e, e)" in (csrc / "optim.hip").read_text()
 
 
 def test_argument_checks_answer_before_any_launch():

@@ -23,9 +23,10 @@ def test_symbols_declared_and_bound_without_a_revision_bump():
         assert name in declared, name
         assert name in _lib.EXPORTS, name
     assert _lib.ABI_VERSION == 223
-    src = (REPO / "gdn-pytorch_amd" / "csrc" / "pointwise.hip").read_text()
-    assert re.search(r"gdn_version\(void\)\s*\{\s*return 223;", src)
+    csrc = REPO / "gdn-pytorch_amd" / "csrc"
+    assert re.search(r"gdn_version\(void\)\s*\{\s*return 223;", (csrc / "pointwise.hip").read_text())
     # every kernel of the feature files under the optimizer in tools/kernel_family.py: its name contains 'adam'
+    src = (csrc / "optim.hip").read_text()
     kernels = re.findall(r"__global__(?:\s+__launch_bounds__\(\d+\))?\s+void\s+(\w+)\s*\(", src)
     new_kernels = [k for k in kernels if "gradnorm" in k or "guard" in k]
     assert len(new_kernels) >= 4 and all("adam" in k for k in new_kernels), new_kernels

@@ -170,18 +170,29 @@ def test_zero_gradient_and_zero_moments_leave_the_decay_alone(gpu):
     assert not _same_bits(after[0][:1000], before[0][:1000])
 
 
-def test_the_four_entry_points_agree(gpu):
-    """On the misaligned range: host count, device count and guarded with coef 1, per group.  On the arena: every live slice
-    of the segmented update against the per-slice update with the group's records, plain and under a guard (coef 0.37)."""
-    from gdn_amd import ops
+def _range_entry_points_agree(gpu, coupled):
+    """On the misaligned range: host count, device count and guarded with coef 1, per group."""
     for k, row in enumerate(GROUPS):
         bufs = _range(gpu, 40 + k)
-        a = _run_range("step", bufs, row, gpu)
-        b = _run_range("step_dev", bufs, row, gpu)
-        c = _run_range("step_dev_guarded", bufs, row, gpu, coef=1.0)
+        a = _run_range("step", bufs, row, gpu, coupled=coupled)
+        b = _run_range("step_dev", bufs, row, gpu, coupled=coupled)
+        c = _run_range("step_dev_guarded", bufs, row, gpu, coupled=coupled, coef=1.0)
         for name, x, y, z in zip("pmv", a, b, c):
             assert _same_bits(x, y) and _same_bits(y, z), (k, name)
         assert torch.equal(b[3], c[3])
+
+
+def test_the_coupled_entry_points_agree_on_the_range(gpu):
+    """gdn_adam_step, gdn_adam_step_dev and gdn_adam_step_dev_guarded at the decays of GROUPS (the arena against the
+    per-slice update is tests/test_hip_seg_adam.py's)."""
+    _range_entry_points_agree(gpu, coupled=True)
+
+
+def test_the_four_entry_points_agree(gpu):
+    """The range as above.  On the arena: every live slice of the segmented update against the per-slice update with the
+    group's records, plain and under a guard (coef 0.37)."""
+    from gdn_amd import ops
+    _range_entry_points_agree(gpu, coupled=False)
     for guarded in (False, True):
         guard = _guard(gpu, coef=0.37) if guarded else None
         before, after, (items, cmap), states = _run_arena(gpu, GROUPS, guard=guard)
@@ -209,6 +220,16 @@ RESTATEMENT_ULPS = 0
 def test_against_the_float32_restatement(gpu):
     """The full update, three steps from t = 0: the range through gdn_adamw_step_dev per group, the arena through
     gdn_adamw_step_seg under a guard (coef 0.37).  Every figure is printed before it is held to the bar."""
+    _against_the_float32_restatement(gpu, coupled=False)
+
+
+def test_coupled_against_the_float32_restatement(gpu):
+    """The same for the coupled family, gdn_adam_step_dev and gdn_adam_step_seg, against the restatement's coupled form
+    (gi = fma32(wd, p, round32(g * gscale)), no decay in the final subtraction): the bits of the main training path."""
+    _against_the_float32_restatement(gpu, coupled=True)
+
+
+def _against_the_float32_restatement(gpu, coupled):
     worst = {"n": 0, "off": 0, "ulps": 0}
 
     def hold(name, got, want):
@@ -220,16 +241,16 @@ def test_against_the_float32_restatement(gpu):
 
     for k, row in enumerate(GROUPS):
         bufs = _range(gpu, 50 + k)
-        got = _run_range("step_dev", bufs, row, gpu)
-        want = R.run32(*(t.cpu().numpy() for t in bufs), row, STEPS)
+        got = _run_range("step_dev", bufs, row, gpu, coupled=coupled)
+        want = R.run32(*(t.cpu().numpy() for t in bufs), row, STEPS, coupled=coupled)
         for name, a, b in zip("pmv", got, want):
             hold("range group %d %s" % (k, name), a.cpu().numpy(), b)
         assert got[3].numpy().tobytes()[:28] == R.state_bytes(row[1], row[2], STEPS)[:28]
-    before, after, (items, cmap), _ = _run_arena(gpu, GROUPS, guard=_guard(gpu, coef=0.37))
+    before, after, (items, cmap), _ = _run_arena(gpu, GROUPS, coupled=coupled, guard=_guard(gpu, coef=0.37))
     host = [t.cpu().numpy() for t in before]
     for o, k, grp in _live(items):
         sl = slice(o, o + k)
-        want = R.run32(host[0][sl], host[1][sl], host[2][sl], host[3][sl], GROUPS[grp], STEPS, coef=0.37)
+        want = R.run32(host[0][sl], host[1][sl], host[2][sl], host[3][sl], GROUPS[grp], STEPS, coef=0.37, coupled=coupled)
         for name, a, b in zip("pmv", (after[0], after[2], after[3]), want):
             hold("arena slice %d group %d %s" % (o, grp, name), a[sl].cpu().numpy(), b)
     print("in all: %d of %d elements not the restatement's bits, largest distance %d ulp" % (worst["off"], worst["n"], worst["ulps"]))

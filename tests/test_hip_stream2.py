@@ -1,4 +1,4 @@
-"""The one streaming skeleton under gdn_ema_update, gdn_swap_f32 and gdn_grad_accumulate (stream2_kernel in pointwise.hip),
+"""The one streaming skeleton under gdn_ema_update, gdn_swap_f32 and gdn_grad_accumulate (stream2_kernel in optim.hip),
 at the sizes where its head / 16-byte body / tail split can go wrong and at every pair of base offsets: bit for bit against
 the restatement each kernel's own test uses (tests/ema_fp64.py's float32 difference and one fused multiply-add; numpy's exact
 exchange and float32 add), and the elements on both sides of both ranges keep their old bits."""
