@@ -1101,7 +1101,8 @@ extern "C" int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, in
     }
     if (phases & 4) {
         const float* Ud = (const float*)((const char*)state + v_bytes(f));
-        launch_gemm_x3_nt((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, st);
+        // phase 4 without phase 2 is the forked form: the weight-gradient chain runs beside this GEMM on another stream
+        launch_gemm_x3_nt_cfg((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, X3_NT_AUTO | ((phases & 2) ? 0 : X3_NT_SHARED), 0, st);
         launch_wino4_output((const float*)Eo, dx, ldx, addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, nullptr, nullptr, 0,
                             fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu, st);
     }

@@ -60,6 +60,24 @@ __device__ __forceinline__ void x3_split2(float x, float y, unsigned& p1, unsign
 // C[bin][m][n] = sum_k A[bin][m][k] * B[bin][n][k]:  A fp32 row-major [bins][M][K]; Bp packed panels of B (x3_pack_rows);
 // C fp32 row-major [bins][M][N].  N a multiple of 128, K a multiple of 32.
 void launch_gemm_x3_nt(const float* A, const void* Bp, float* C, int bins, int M, int N, int K, hipStream_t st);
+// The same with the kernel form chosen by the caller (tests, measurements).  cfg & 0xff: X3_NT_AUTO = what launch_gemm_x3_nt
+// runs; the one-shot launches (a workgroup per 128- or 64-row output block) and the persistent ones (a resident grid walking a
+// static unit list, gemm_x3.hip) of the two kernels.  Flags for the persistent forms: X3_NT_KEEP_BINS = an XCD keeps whole
+// bins (default: (bin, M tile) pairs dealt in contiguous ranges), X3_NT_NO_HALVES = a ragged last round is not cut into
+// half-height units.  X3_NT_SHARED (with X3_NT_AUTO): another stream's GEMM chain runs beside this launch (the forked Winograd
+// backward).  grid: workgroups of the persistent forms, a multiple of 8; 0 = two per CU.  All forms give the same bits.
+#define X3_NT_AUTO GDN_X3_NT_AUTO
+#define X3_NT_ONESHOT_128 GDN_X3_NT_ONESHOT_128
+#define X3_NT_ONESHOT_64 GDN_X3_NT_ONESHOT_64
+#define X3_NT_UNITS_128 GDN_X3_NT_UNITS_128
+#define X3_NT_UNITS_64 GDN_X3_NT_UNITS_64
+#define X3_NT_KEEP_BINS GDN_X3_NT_KEEP_BINS
+#define X3_NT_NO_HALVES GDN_X3_NT_NO_HALVES
+#define X3_NT_SHARED GDN_X3_NT_SHARED
+void launch_gemm_x3_nt_cfg(const float* A, const void* Bp, float* C, int bins, int M, int N, int K, int cfg, int grid, hipStream_t st);
+// kernel-side walk flags (the complement of the two cfg flags)
+#define X3_UNITS_PAIRS 1
+#define X3_UNITS_HALVE 2
 // packs fp32 row-major [bins][rows][K] into panels (rows padded with zeros to whole tiles)
 void launch_x3_pack_rows(const float* src, void* dst, int bins, int rows, int K, hipStream_t st);
 static inline bool gemm_x3_ok(int M, int N, int K) { return M >= 1 && N >= 128 && N % 128 == 0 && K >= 32 && K % 32 == 0; }

@@ -81,6 +81,7 @@ _SIGS = {
     "gdn_gemm_x3_pack": (c_int32, [_P, _P, _i32, _i32, _i32, _P]),
     "gdn_gemm_x3_nt": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, _P]),
     "gdn_gemm_x3_tn": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _P]),
+    "gdn_gemm_x3_nt_cfg": (c_int32, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
     "gdn_gemm_x3_tn_splits": (_i64, [_i32, _i32, _i32, _i32]),
     "gdn_transpose_taps": (c_int32, [_P, _P, _i32, _i32, _i32, _i32, _P]),
     "gdn_cast": (c_int32, [_P, _P, _i64, _i32, _P]),
@@ -169,7 +170,8 @@ EXPORTS = tuple(_SIGS)
 # _load() binds every name above, so a library built before it fails at load with the missing symbol; so did gdn_bn_frozen_coeffs
 # and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule, gdn_silog_masked and the
 # evaluation entry points gdn_depth_metrics_std*, gdn_flip_w and gdn_flip_mean, and the four gdn_adamw_step* entry points of
-# the decoupled weight decay, and gdn_step_record and gdn_tensor_sumsq* of the training log, for the same reason.)
+# the decoupled weight decay, and gdn_step_record and gdn_tensor_sumsq* of the training log, and the kernel-form selector
+# gdn_gemm_x3_nt_cfg, for the same reason.)
 ABI_VERSION = 223
 
 

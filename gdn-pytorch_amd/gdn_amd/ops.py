@@ -709,12 +709,22 @@ def gemm_x3_pack(Bm):
     return out
 
 
-def gemm_x3_nt(A, Bp, N, out=None):
-    """C[bin] = A[bin] @ B[bin]^T with fp32 A [bins, M, K], packed B (gemm_x3_pack of [bins, N, K]); fp32 C [bins, M, N]."""
+# kernel forms of gemm_x3_nt (GDN_X3_NT_* of gdn_hip.h): the one-shot launches, the persistent unit walks, and the flags of the latter
+X3_NT_AUTO, X3_NT_ONESHOT_128, X3_NT_ONESHOT_64, X3_NT_UNITS_128, X3_NT_UNITS_64 = 0, 1, 2, 3, 4
+X3_NT_KEEP_BINS, X3_NT_NO_HALVES, X3_NT_SHARED = 0x100, 0x200, 0x400
+
+
+def gemm_x3_nt(A, Bp, N, out=None, tile_cfg=X3_NT_AUTO, grid=0):
+    """C[bin] = A[bin] @ B[bin]^T with fp32 A [bins, M, K], packed B (gemm_x3_pack of [bins, N, K]); fp32 C [bins, M, N].
+    tile_cfg (tests, measurements): the kernel form, X3_NT_*; grid: workgroups of a persistent form (a multiple of 8, 0 = two
+    per CU).  Every form gives the same bits."""
     _chk(A, "A")
     bins, M, K = A.shape
     C = out if out is not None else torch.empty((bins, M, N), dtype=torch.float32, device=A.device)
-    lib.gdn_gemm_x3_nt(_p(A), _p(Bp), _p(C), bins, M, N, K, stream())
+    if tile_cfg == X3_NT_AUTO and grid == 0:
+        lib.gdn_gemm_x3_nt(_p(A), _p(Bp), _p(C), bins, M, N, K, stream())
+    else:
+        lib.gdn_gemm_x3_nt_cfg(_p(A), _p(Bp), _p(C), bins, M, N, K, tile_cfg, grid, stream())
     return C
 
 

@@ -373,6 +373,24 @@ int gdn_gemm_x3_pack(const float* src, void* dst, int32_t bins, int32_t rows, in
 int gdn_gemm_x3_nt(const float* A, const void* Bp, float* C, int32_t bins, int32_t M, int32_t N, int32_t K, void* stream);
 int gdn_gemm_x3_tn(const float* A, const float* B, float* P, int32_t bins, int32_t T, int32_t NI, int32_t NJ, int32_t nsplit,
                    void* stream);
+/* gdn_gemm_x3_nt with the kernel form chosen by the caller (tests and measurements; every form gives the same bits).
+ * cfg & 0xff: GDN_X3_NT_AUTO = what gdn_gemm_x3_nt and the Winograd layers run; the one-shot launches (one workgroup per 128-
+ * or 64-row output block) and the persistent ones (a resident grid, every workgroup walking a static list of output blocks).
+ * Flags of the persistent forms: GDN_X3_NT_KEEP_BINS (an XCD keeps whole bins instead of a contiguous range of (bin, row tile)
+ * pairs), GDN_X3_NT_NO_HALVES (a ragged last round is not cut into half-height blocks).  GDN_X3_NT_SHARED, with GDN_X3_NT_AUTO
+ * only: the launch shares the chip with another stream's GEMM chain, as in the forked Winograd backward.  grid: workgroups of a persistent form,
+ * a multiple of 8 up to 8192; 0 = two per CU.  GDN_ERR_BAD_ARG for anything else.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+#define GDN_X3_NT_AUTO 0
+#define GDN_X3_NT_ONESHOT_128 1
+#define GDN_X3_NT_ONESHOT_64 2
+#define GDN_X3_NT_UNITS_128 3
+#define GDN_X3_NT_UNITS_64 4
+#define GDN_X3_NT_KEEP_BINS 0x100
+#define GDN_X3_NT_NO_HALVES 0x200
+#define GDN_X3_NT_SHARED 0x400
+int gdn_gemm_x3_nt_cfg(const float* A, const void* Bp, float* C, int32_t bins, int32_t M, int32_t N, int32_t K, int32_t cfg,
+                       int32_t grid, void* stream);
 /* host query: the number of reduction splits gdn_winoconv_bwd / gdn_wino2conv_bwd give gdn_gemm_x3_tn for a shape (0: shape not
  * eligible): rounds of the chip per split plus the partial-product sets read back, DESIGN.md 2.10 */
 int64_t gdn_gemm_x3_tn_splits(int32_t bins, int32_t T, int32_t NI, int32_t NJ);
