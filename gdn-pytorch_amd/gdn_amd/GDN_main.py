@@ -69,6 +69,10 @@ the ``--min_depth`` / ``--max_depth`` cap, the ``--eval_crop {garg,eigen,none}``
 ``--flip_test``, nine metrics averaged per image.  ``--eval_gt_list FILE`` (test modes with ``--real_test``) takes the ground
 truth from 16-bit KITTI depth maps at their native size; the prediction is resampled to each map inside the metrics kernel.
 The result line states the protocol's parameters.  ``--eval_protocol reference`` is the run without the flag.
+``--eval_velodyne LIST --kitti_raw ROOT`` (same conditions, instead of ``--eval_gt_list``) makes that ground truth on the
+device from the raw Velodyne scan of each test sample: one scatter kernel per batch projects the scans
+through each date's calibration, the nearest point wins a pixel, ``--velo_depth {camera,forward}`` picks the depth that is
+stored; the result line names the list and the run ends with the mean number of LiDAR pixels per image.
 ``--optimizer adamw`` trains with decoupled weight decay: ``--decoupled_wd W`` (1e-2 when not given) takes
 the place of the reference's 5e-4, stays out of the gradient and the moments and shrinks each weight by ``rate x W x weight``
 inside the fused update's own launches, ``rate`` being the update's (after ``--lr_mult`` and the schedule); ``--no_decay_norm``
@@ -306,7 +310,7 @@ def _check_eval(args):
     """--eval_protocol standard and its flags; checked before anything touches the GPU."""
     spec = option.eval_spec(args)
     if not spec["standard"]:
-        given = option.eval_flags_given(args)
+        given = option.eval_flags_given(args) + option.velo_flags_given(args)
         if given:
             raise RuntimeError("%s set(s) the Eigen-split evaluation, which --eval_protocol standard selects (add it, or drop "
                                "the flag)" % ", ".join("--" + k for k in given))
@@ -327,6 +331,41 @@ def _check_eval(args):
             raise RuntimeError("--eval_gt_list lists the ground truth of the Eigen test split: add --real_test")
         if not os.path.isfile(spec["gt_list"]):
             raise FileNotFoundError("--eval_gt_list %r: no such file" % (spec["gt_list"],))
+    _check_velodyne(args, spec)
+
+
+def _check_velodyne(args, spec):
+    """--eval_velodyne / --kitti_raw / --velo_depth under --eval_protocol standard."""
+    given = option.velo_flags_given(args)
+    if not given:
+        return
+    lst, root = getattr(args, "eval_velodyne", None), getattr(args, "kitti_raw", None)
+    if not lst:
+        raise RuntimeError("%s belong(s) to --eval_velodyne LIST, which names the scans to project (add it, or drop the "
+                           "flag)" % ", ".join("--" + k for k in given))
+    if not root:
+        raise RuntimeError("--eval_velodyne names scans inside a raw KITTI tree: add --kitti_raw ROOT")
+    if spec["gt_list"]:
+        raise RuntimeError("--eval_velodyne and --eval_gt_list both supply the ground truth of the test split: drop one of "
+                           "the two")
+    if args.mode not in TEST_MODES:
+        raise RuntimeError("--eval_velodyne is the ground truth of a test run; --mode %s validates on the loader's "
+                           "(use --mode DtoD_test / RtoD_test)" % args.mode)
+    if not args.real_test:
+        raise RuntimeError("--eval_velodyne lists the scans of the Eigen test split: add --real_test")
+    if not os.path.isfile(lst):
+        raise FileNotFoundError("--eval_velodyne %r: no such file" % (lst,))
+    if not os.path.isdir(root):
+        raise FileNotFoundError("--kitti_raw %r: no such directory" % (root,))
+    from .datasets import TestFolder
+    split = os.path.join(str(getattr(args, "data", None)), TestFolder.LISTS[0])
+    if not getattr(args, "synthetic", False) and os.path.isfile(split):     # (trainer.validate_std checks any other loader)
+        with open(lst) as f:
+            lines = sum(1 for line in f if line.strip())
+        with open(split) as f:
+            samples = sum(1 for line in f if line.split())
+        if lines != samples:
+            raise RuntimeError("--eval_velodyne names %d scans, the test split has %d samples" % (lines, samples))
 
 
 def _check_freeze_bn(args):
@@ -571,10 +610,16 @@ def run(args, train_loader=None, val_loader=None):
             if spec["gt_list"]:
                 from .datasets import EigenGt16
                 gt16 = EigenGt16(spec["gt_list"], args.data)
-            errors, left_out, names = validate_std(args, val_loader, model, 0, logger, args.mode, on_batch=saver, gt16=gt16)
+            # --eval_velodyne: the raw scans, projected on the device batch by batch
+            vspec, velo = option.velo_spec(args), None
+            if vspec:
+                from .datasets import EigenVelodyne
+                velo = EigenVelodyne(vspec["list"], vspec["root"], vspec["depth"])
+            errors, left_out, names = validate_std(args, val_loader, model, 0, logger, args.mode, on_batch=saver, gt16=gt16,
+                                                   velo=velo)
             if rank == 0:
                 print("Results: " + ", ".join("%s %.4f" % (n, e) for n, e in zip(names, errors)) +
-                      " [standard: %s; %d image(s) left out]" % (option.eval_describe(spec), left_out))
+                      " [standard: %s; %d image(s) left out]" % (option.eval_describe(spec, vspec), left_out))
             return errors
         evaluate = validate_NYU if args.dataset == "NYU" else validate
         errors, min_errors, names = evaluate(args, val_loader, model, 0, logger, args.mode, on_batch=saver)

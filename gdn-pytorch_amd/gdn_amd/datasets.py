@@ -168,6 +168,77 @@ def assemble_gt16(maps, device):
     return (pool.to(device, non_blocking=True) if device.type == "cuda" else pool), sizes
 
 
+class EigenVelodyne:
+    """--eval_velodyne: the raw Velodyne scan of each Eigen test sample (kitti_raw.parse_velo_list names them, in the order
+    of the test lists).  A sample is (points float32 [N,4] as stored, P [3,4] float64, (h0, w0)): what ops.velo_project
+    turns into the sample's sparse ground truth at the camera's native size.  The calibration is read once per date and
+    camera.  depth ('camera' | 'forward') is kept for the caller: which depth the projected maps hold."""
+
+    def __init__(self, list_file, raw_root, depth='camera'):
+        from .kitti_raw import parse_velo_list
+        if depth not in ops.VELO_DEPTHS:
+            raise GdnError("EigenVelodyne: depth %r is not one of camera / forward" % (depth,))
+        self.list_file, self.depth = str(list_file), depth
+        self.samples = parse_velo_list(list_file, raw_root)
+        self._calib = {}
+
+    def __getitem__(self, index):
+        from .kitti_raw import projection
+        scan, date_dir, cam = self.samples[index]
+        try:
+            raw = np.fromfile(scan, dtype=np.float32)
+        except OSError as e:
+            raise GdnError("cannot read %s: %s" % (scan, e)) from e
+        if raw.size % 4:
+            raise GdnError("%s holds %d floats: not x, y, z, reflectance per point" % (scan, raw.size))
+        key = (str(date_dir), cam)
+        if key not in self._calib:
+            self._calib[key] = projection(date_dir, cam)
+        P, size = self._calib[key]
+        return raw.reshape(-1, 4), P, size
+
+    def __len__(self):
+        return len(self.samples)
+
+
+def assemble_scans(samples, device):
+    """B samples of EigenVelodyne -> the device arguments of ops.velo_project: (points float32 [N,4], offsets int64 [B+1],
+    proj float64 [B,12], sizes int32 [B,2], Hmax, Wmax, [(h0, w0), ...]).  The points travel through one pinned staging
+    buffer in one host-to-device copy; offsets, matrices and sizes share one small table and one more copy."""
+    B = len(samples)
+    if B == 0:
+        raise GdnError("assemble_scans: a non-empty list of (points, P, (h0, w0))")
+    counts, sizes = [], []
+    for pts, P, (h0, w0) in samples:
+        if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.ndim == 2 and pts.shape[1] == 4):
+            raise GdnError("assemble_scans: points must be float32 [N,4] arrays")
+        if np.shape(P) != (3, 4) or int(h0) < 1 or int(w0) < 1:
+            raise GdnError("assemble_scans: P must be 3 x 4 and the image size positive")
+        counts.append(int(pts.shape[0]))
+        sizes.append((int(h0), int(w0)))
+    device = torch.device(device)
+    pin = device.type == "cuda"
+    total = sum(counts)
+    stage = torch.empty((total, 4), dtype=torch.float32, pin_memory=pin)
+    table = torch.empty(8 * (B + 1) + 96 * B + 8 * B, dtype=torch.uint8, pin_memory=pin)
+    o_off, o_proj, o_size = 0, 8 * (B + 1), 8 * (B + 1) + 96 * B
+    view = table.numpy()
+    offsets = view[o_off:o_proj].view(np.int64)
+    proj = view[o_proj:o_size].view(np.float64).reshape(B, 12)
+    hw = view[o_size:].view(np.int32).reshape(B, 2)
+    offsets[0] = 0
+    np.cumsum(counts, out=offsets[1:])
+    points = stage.numpy()
+    for b, (pts, P, _) in enumerate(samples):
+        points[offsets[b]:offsets[b + 1]] = pts
+        proj[b] = np.asarray(P, dtype=np.float64).reshape(12)
+        hw[b] = sizes[b]
+    if pin:
+        stage, table = stage.to(device, non_blocking=True), table.to(device, non_blocking=True)
+    return (stage, table[o_off:o_proj].view(torch.int64), table[o_proj:o_size].view(torch.float64).reshape(B, 12),
+            table[o_size:].view(torch.int32).reshape(B, 2), max(h for h, _ in sizes), max(w for _, w in sizes), sizes)
+
+
 class NYUdataset:
     """NYU Depth v2 (datasets_list.py:366-444).  train=False: root/test/test_depths/*.png (16-bit depth) paired in sorted
     order with root/test/test_colors/*.png, in that order (the reference shuffles unless --img_test).  train=True:

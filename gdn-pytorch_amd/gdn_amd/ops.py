@@ -1103,6 +1103,40 @@ def flip_mean(a, b, out=None):
     return out
 
 
+VELO_DEPTHS = {'camera': 0, 'forward': 1}   # depth_kind of gdn_velo_project
+
+
+def velo_project(points, offsets, proj, sizes, Hmax, Wmax, depth='camera', hits=False, max_points=None):
+    """gdn_velo_project: points float32 [N,4] (the scans of B images, one after the other), offsets int64 [B+1], proj
+    float64 [B,12] (or [B,3,4]) and sizes int32 [B,2] = (h0, w0), all dense and on the GPU -> float32 [B,Hmax,Wmax] metres
+    (0 where no point lands, and in the padding), and with hits=True also int32 [B], the > 0 pixels of each image.
+    depth: 'camera' (along the optical axis) or 'forward' (the scanner's x).  max_points: at least the largest scan (it
+    sizes the grid; when not given: N).  No sync, nothing is read on the host."""
+    if depth not in VELO_DEPTHS:
+        raise GdnError("velo_project: depth %r is not one of camera / forward" % (depth,))
+    if not (points.is_cuda and points.dim() == 2 and points.shape[1] == 4 and points.dtype == torch.float32 and
+            points.is_contiguous()):
+        raise GdnError("velo_project: points must be a dense [N,4] float32 tensor on the GPU")
+    if not (offsets.is_cuda and offsets.dim() == 1 and offsets.dtype == torch.int64 and offsets.is_contiguous() and
+            offsets.numel() >= 2):
+        raise GdnError("velo_project: offsets must be a dense int64 [B+1] tensor on the GPU")
+    B = offsets.numel() - 1
+    if not (proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.numel() == 12 * B and
+            proj.shape[0] == B):
+        raise GdnError("velo_project: proj must be a dense float64 [B,12] tensor on the GPU for the %d images of offsets" % B)
+    if not (sizes.is_cuda and sizes.dtype == torch.int32 and sizes.is_contiguous() and tuple(sizes.shape) == (B, 2)):
+        raise GdnError("velo_project: sizes must be a dense int32 [B,2] tensor on the GPU for the %d images of offsets" % B)
+    Hmax, Wmax = int(Hmax), int(Wmax)
+    if Hmax < 1 or Wmax < 1:
+        raise GdnError("velo_project: a pool of %d x %d" % (Hmax, Wmax))
+    n = int(points.shape[0]) if max_points is None else int(max_points)
+    out = torch.empty((B, Hmax, Wmax), dtype=torch.float32, device=points.device)
+    count = torch.empty((B,), dtype=torch.int32, device=points.device) if hits else None
+    lib.gdn_velo_project(_p(points) if points.shape[0] else None, _p(offsets), _p(proj), _p(sizes), B, n, Hmax, Wmax,
+                         VELO_DEPTHS[depth], _p(out), _p(count) if hits else None, stream())
+    return (out, count) if hits else out
+
+
 def center_crop_offsets(in_h, in_w, out_h, out_w):
     """CenterCrop.get_params (transform_list.py:260-261): Python's round, i.e. half to even."""
     return int(round((in_h - out_h) / 2.)), int(round((in_w - out_w) / 2.))

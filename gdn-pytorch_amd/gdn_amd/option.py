@@ -4,7 +4,7 @@ plus the few the MI355X build adds (--synthetic, --local_rank, --dtype, --global
 --graph_warmup, --accum_steps, --freeze_bn, --freeze, --lr_mult, --no_decay_norm, --warmup_steps, --lr_schedule,
 --lr_floor, --loss, --silog_lambda, --silog_weight, --silog_floor, --silog_mask, --eval_protocol, --eval_crop, --min_depth,
 --max_depth, --depth_scale, --median_scaling, --flip_test, --eval_gt_list, --optimizer, --decoupled_wd, --train_log,
---train_log_every, --tensor_norms_every).
+--train_log_every, --tensor_norms_every, --eval_velodyne, --kitti_raw, --velo_depth).
 
 Unlike the reference the parser is not evaluated at import time; call ``parse_args()``.
 """
@@ -241,6 +241,18 @@ def build_parser():
                    help='with --eval_protocol standard, a test mode and --real_test: one 16-bit KITTI depth PNG (metres x '
                         '256) per test sample, at its native size, as the ground truth; the network\'s inputs stay what '
                         'the test lists feed it')
+    p.add_argument('--eval_velodyne', type=str, default=None, metavar='LIST',
+                   help='with --eval_protocol standard, a test mode and --real_test: the ground truth is projected on the '
+                        'device from the raw Velodyne scan of each test sample (DESIGN.md 3.15), at the camera\'s native '
+                        'size.  LIST names one sample per line, DATE/DRIVE/image_0C/data/FRAME.png or DATE/DRIVE FRAME l|r, '
+                        'in the order of the test lists; needs --kitti_raw, excludes --eval_gt_list')
+    p.add_argument('--kitti_raw', type=str, default=None, metavar='ROOT',
+                   help='with --eval_velodyne: the raw KITTI tree (ROOT/DATE/calib_*.txt, '
+                        'ROOT/DATE/DRIVE/velodyne_points/data/*.bin)')
+    p.add_argument('--velo_depth', default=None, choices=['camera', 'forward'],
+                   help='with --eval_velodyne: camera = the depth along the camera\'s axis, as the 2017-2019 Eigen-split '
+                        'tables use it; forward = the scanner\'s forward distance, monodepth2\'s export (when not given: '
+                        'camera)')
     p.add_argument('--optimizer', default='adam', choices=['adam', 'adamw'],
                    help='training: the update rule of the fused optimizer.  adam: the reference\'s Adam with its L2 term of '
                         '5e-4 folded into the gradient, as ever.  adamw: decoupled weight decay (DESIGN.md 3.13) -- the decay '
@@ -309,12 +321,34 @@ def eval_flags_given(args):
            [k for k in EVAL_SWITCHES if getattr(args, k, None)]
 
 
-def eval_describe(spec):
-    """What a result line of the standard protocol says about itself."""
+VELO_FLAGS = ('eval_velodyne', 'kitti_raw', 'velo_depth')
+
+
+def velo_spec(args):
+    """--eval_velodyne beside eval_spec(): None without the flag, else {'list', 'root', 'depth'} with --velo_depth not given
+    at its default (camera)."""
+    if not getattr(args, 'eval_velodyne', None):
+        return None
+    return {'list': args.eval_velodyne, 'root': getattr(args, 'kitti_raw', None),
+            'depth': getattr(args, 'velo_depth', None) or 'camera'}
+
+
+def velo_flags_given(args):
+    """The names of the --eval_velodyne flags the command line sets."""
+    return [k for k in VELO_FLAGS if getattr(args, k, None)]
+
+
+def eval_describe(spec, velo=None):
+    """What a result line of the standard protocol says about itself (velo: velo_spec() of the same command line)."""
+    if velo:
+        gt = 'Velodyne scans projected on the device (%s, %s)' % (velo['list'], velo['depth'])
+    elif spec['gt_list']:
+        gt = '16-bit maps at native size (%s)' % spec['gt_list']
+    else:
+        gt = "the loader's, at the network's size"
     return "crop %s, cap %g-%g m, depth_scale %g m, median scaling %s, flip %s, gt %s" % (
         spec['crop'], spec['min_depth'], spec['max_depth'], spec['depth_scale'], 'on' if spec['median_scaling'] else 'off',
-        'on' if spec['flip_test'] else 'off',
-        '16-bit maps at native size (%s)' % spec['gt_list'] if spec['gt_list'] else "the loader's, at the network's size")
+        'on' if spec['flip_test'] else 'off', gt)
 
 
 SILOG_DEFAULTS = {'silog_lambda': 0.85, 'silog_weight': 10.0, 'silog_floor': 0.0125, 'silog_mask': 'dense'}

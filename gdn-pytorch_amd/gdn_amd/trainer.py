@@ -796,18 +796,22 @@ def validate(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None)
                      on_batch)
 
 
-def validate_std(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None, gt16=None):
+def validate_std(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=None, gt16=None, velo=None):
     """KITTI under the Eigen-split protocol (--eval_protocol standard): metric depth, the --min_depth /
     --max_depth cap, the --eval_crop box at the ground truth's own resolution, optional --median_scaling and --flip_test.
     The ground truth is the loader's third tensor (in [-1, 1], at the network's size) or, with gt16 (datasets.EigenGt16,
-    one map per sample in loader order), the 16-bit maps at their native size.  The per-image rows stay on the device; one
-    D2H copy at the end.  Returns (the nine metrics as the float64 mean over ALL images with a valid pixel -- not the mean
-    of batch means --, the number of images left out, names); rank 0 prints that number whenever it is not 0."""
+    one map per sample in loader order), the 16-bit maps at their native size, or, with velo (datasets.EigenVelodyne, one
+    scan per sample in loader order), the maps ops.velo_project makes of the raw scans, batch by batch (DESIGN.md 3.15);
+    rank 0 then prints the mean number of LiDAR pixels per image.  The per-image rows (and hit counts) stay on the device;
+    one D2H copy (each) at the end.  Returns (the nine metrics as the float64 mean over ALL images with a valid pixel --
+    not the mean of batch means --, the number of images left out, names); rank 0 prints that number whenever it is not 0."""
     from . import ops
-    from .datasets import assemble_gt16
+    from .datasets import assemble_gt16, assemble_scans
     dev = _device_of(model)
     opt = option.eval_spec(args)
-    rows, k = [], 0
+    rows, hits, k = [], [], 0
+    if velo is not None and len(velo) != len(val_loader.ds):
+        raise U.GdnError("--eval_velodyne names %d scans, the test split has %d samples" % (len(velo), len(val_loader.ds)))
     if gt16 is not None and len(gt16) != len(val_loader.ds):
         raise U.GdnError("--eval_gt_list names %d maps, the test split has %d samples" % (len(gt16), len(val_loader.ds)))
     for depth, img, depth_np in val_loader:
@@ -820,19 +824,30 @@ def validate_std(args, val_loader, model, epoch, logger, mode='DtoD', on_batch=N
                 mirrored = model(ops.flip_w(x.float().contiguous()), istrain=False).detach().float().contiguous()
                 out = ops.flip_mean(out, mirrored, out=out)
         B = out.shape[0]
-        if gt16 is None:
+        gt_kind = None
+        if velo is not None:
+            scans = [velo[k + i] for i in range(B)]
+            points, offsets, proj, hw, Hmax, Wmax, sizes = assemble_scans(scans, dev)
+            gt, n_hit = ops.velo_project(points, offsets, proj, hw, Hmax, Wmax, depth=velo.depth, hits=True,
+                                         max_points=max(len(s[0]) for s in scans))
+            gt_kind = ops.GT_METRES
+            hits.append(n_hit)
+        elif gt16 is None:
             gt, sizes = depth_np, None
         else:
             gt, sizes = assemble_gt16([gt16[k + i] for i in range(B)], dev)
         k += B
         rows.append(compute_errors_std_device(gt, sizes, out, crop=opt["crop"], min_depth=opt["min_depth"],
                                               max_depth=opt["max_depth"], depth_scale=opt["depth_scale"],
-                                              median_scaling=opt["median_scaling"]))
+                                              median_scaling=opt["median_scaling"], gt_kind=gt_kind))
         if on_batch is not None:
             on_batch(depth, img, depth_np, out)
     if not rows:
         return [float('nan')] * len(ERROR_NAMES_STD), 0, ERROR_NAMES_STD
     errors, left_out = mean_errors_std(torch.cat(rows).cpu())
+    if hits and _is_main():
+        print("=> Velodyne ground truth: %.1f LiDAR pixels per image on average (%d images)"
+              % (float(torch.cat(hits).cpu().double().mean()), k))
     if left_out and _is_main():
         print("=> standard protocol: %d of %d images have no valid pixel and are left out of the mean" % (left_out, k))
     return errors, left_out, ERROR_NAMES_STD

@@ -40,7 +40,7 @@ typedef enum {
     GDN_ERR_LAUNCH = -4
 } gdn_status;
 
-/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn); gdn_silog_masked (--loss silog; gdn_loss_workspace_bytes grows by a third partial array, which every caller queries); gdn_depth_metrics_std*, gdn_flip_w, gdn_flip_mean (--eval_protocol standard, --flip_test).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
+/* Revision of this header (argument lists, struct layouts).  223: gdn_depth_metrics_nyu*, gdn_depth_metrics_make3d*, gdn_crop_normalize, gdn_bytescale_u8 (evaluation); added later without a bump (purely additive: a library without them fails at load on the missing symbol): gdn_nyu_aug_params, gdn_nyu_augment*, gdn_pil_resize*, gdn_spline_rotate3* (NYU training); gdn_grad_sumsq*, gdn_grad_guard_finalize, gdn_adam_step_dev_guarded (gradient guard of the capturable Adam); gdn_hints_supported with GDN_HINT_FLIP_TAPS (a library that would ignore the bit lacks the symbol); gdn_bn_frozen_coeffs, gdn_bn_frozen_bwd* (--freeze_bn); gdn_silog_masked (--loss silog; gdn_loss_workspace_bytes grows by a third partial array, which every caller queries); gdn_depth_metrics_std*, gdn_flip_w, gdn_flip_mean (--eval_protocol standard, --flip_test); gdn_velo_project (--eval_velodyne).  222: gdn_fftconv_bwd bnb_*, gdn_fftconv_bnb_slots.  221: gdn_clock_probe_*.  220: gdn_conv_dgrad dx_up2x; gdn_bn_apply_up2x; bf16 tile id 12 (conv_ring2_bf16).  219: gdn_conv_wgrad_bf16 cfg 4 (wgrad_ring_bf16); gdn_fftconv_cgemm* measurement hooks; plan overrides in gdn_conv_geom.hints; gdn_gemm_x3_nt_packed / gdn_gemm_x3_ring_workspace_bytes removed (the measured-and-not-wired kernel now lives under tests/diag/).  218: gdn_gemm_x3_tn_splits.  217: gdn_conv_dgrad bnb_*.  216: gdn_conv_c1_fwd Cin.  215: GDN_HINT_NO_WINO_F4.  214: gdn_gemm_x3_nt_packed.  213: gdn_conv_c1_fwd dtypes / gdn_conv_c1_wgrad gw_bf16.  212: GDN_HINT_NO_X3 (replaces the GDN_X3 environment read).  211: gdn_gemm_x3_*.  210: gdn_conv_geom.hints, in_up2x / dx_up2x.  A binding checks it
  * for equality at load time (gdn_amd/_lib.py: ABI_VERSION). */
 int gdn_version(void);
 /* The GDN_HINT_* bits (below) this library acts on.  A binding that sets a bit that CHANGES WHAT IS COMPUTED (GDN_HINT_FLIP_TAPS)
@@ -971,6 +971,33 @@ int gdn_step_record(void* ring, int32_t cap, const float* const* terms, int32_t 
 size_t gdn_tensor_sumsq_workspace_bytes(int64_t n, int32_t T);
 int gdn_tensor_sumsq(const float* p, const float* g, int64_t n, const int64_t* seg, int32_t T, double* out, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* Raw Velodyne scans -> sparse ground-truth maps (no reference counterpart): a ragged batch of B scans is
+ * projected into the padded pool that gdn_depth_metrics_std reads as gt_kind 0.  All pointers are device memory.
+ *   points   float[total][4] as the .bin files store them (x, y, z, reflectance), the scans one after the other, 16-byte
+ *            aligned; the fourth float is never used (the homogeneous coordinate is 1);
+ *   offsets  int64[B + 1]: image b owns points offsets[b] .. offsets[b + 1] - 1.  The CONTENTS of the table are the caller's
+ *            to check, like the chunk map of the segmented Adam;
+ *   proj     double[B][12]: the row-major 3 x 4 matrix P = P_rect . R_rect . T_velo_to_cam of each image;
+ *   sizes    int32[B][2] = {h0, w0} of each image (held inside Hmax x Wmax);
+ *   max_points  at least the largest scan of the batch: it sizes the grid and nothing else (a longer scan is still
+ *            projected whole, by the grid stride);
+ *   depth    float[B][Hmax][Wmax], 16-byte aligned: every cell is written, the padding and an image without points as +0;
+ *   hits     int32[B] or NULL: the number of pixels of each image that come out > 0.
+ * Per point, in double without contraction:  drop it unless x >= 0;  r_i = ((P[i][0] x + P[i][1] y) + P[i][2] z) + P[i][3];
+ *   u = rint(r_0 / r_2) - 1, v = rint(r_1 / r_2) - 1 (half to even; the -1 is the KITTI devkit's 1-based pixel); keep it iff
+ *   u >= 0, v >= 0, u < w0, v < h0, compared in double (NaN and +-inf fail);  d = (float)(depth_kind ? x : r_2): 0 is the
+ *   depth along the camera's axis, 1 the scanner's forward distance.  The pixel takes the MINIMUM d of the points on it; a
+ *   minimum that is not > 0 reads +0, like a pixel no point hits.
+ * One memset node (two with hits), a scatter launch (one no-return 32-bit unsigned atomic min per kept point on an
+ * order-preserving key kept in the output cell) and a finalise launch over the whole pool: no workspace, no allocation, no
+ * sync, no host read, capturable; integer atomics only, so two calls give the same bytes.  A NULL pointer (hits excepted;
+ * points only when max_points is 0), B outside 1 .. 65535, Hmax or Wmax < 1, Hmax * Wmax >= 2^31, depth_kind outside 0 .. 1,
+ * max_points < 0 or a misaligned buffer return GDN_ERR_BAD_ARG before any launch.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+int gdn_velo_project(const float* points, const int64_t* offsets, const double* proj, const int32_t* sizes, int32_t B,
+                     int64_t max_points, int32_t Hmax, int32_t Wmax, int32_t depth_kind, float* depth, int32_t* hits,
+                     void* stream);
 
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
