@@ -1,13 +1,13 @@
-// KITTI depth metrics (compute_errors, calculate_error.py:10-103) as one
-// workgroup per image: min/max normalisation, Godard crop + validity mask,
-// lower-median scaling by an 8-bit radix select over the float bit patterns
-// (all values are positive, so bit order == value order), clamp, and the eight
-// reductions in fp64.  No host round trips, no sorts, no atomics on global memory.
-// The NYU Depth v2 and Make3D variants (compute_errors_NYU :105-150, compute_errors_Make3D :152-182) share the
-// structure: one workgroup per image, every pixel value recomputed from the inputs on each pass (the images stay
-// L2-resident), the mask-deciding chain with correctly rounded divisions and no FMA contraction so that every
-// valid / invalid decision equals torch's fp32 one.  An image without a valid pixel yields NaN metrics (the
-// reference raises there: torch.median of an empty tensor).
+// The reference's three depth-metric protocols (calculate_error.py: compute_errors :10-103 for KITTI, compute_errors_NYU
+// :105-150, compute_errors_Make3D :152-182), each as one workgroup per image: min/max normalisation, crop + validity mask,
+// lower-median scaling by an 8-bit radix select over the float bit patterns (the selected values are >= +0, so bit order ==
+// value order), clamp, and the reductions in fp64.  No host round trips, no sorts, no atomics on global memory.  Every
+// pixel value is recomputed from the inputs on each pass (the images stay L2-resident), with correctly rounded divisions
+// and no FMA contraction, so that every valid / invalid decision, median and threshold decision equals torch's fp32 one.
+// An image without a valid pixel yields NaN metrics (the reference raises there: torch.median of an empty tensor).
+// Non-finite inputs follow torch: min / max / median propagate NaN and the clamp keeps it, so a NaN or +-inf pixel in the
+// prediction, or a constant prediction (0 / 0), gives NaN sums and a1 = a2 = a3 = 0; a NaN pixel in, or a constant,
+// ground truth leaves no valid pixel.
 #include "common.h"
 
 namespace {
@@ -25,145 +25,45 @@ __device__ __forceinline__ double block_sum_d1024(double v, double* sh) {
     return s;
 }
 
-struct PixVals { float g, p, s; bool valid; };
+// torch.min / torch.max: NaN as soon as one operand is NaN (fminf / fmaxf alone would drop it)
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fminf(a, b); }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
 
-__device__ __forceinline__ PixVals load_px(const float* gs, const float* gt, const float* pr, int i, int W, float gmin,
-                                          float gmax, float pmin, float pmax, int y1, int y2, int x1, int x2) {
-    PixVals v;
-    v.p = ((pr[i] - pmin) / (pmax - pmin)) * 80.f;
-    v.g = ((gt[i] - gmin) / (gmax - gmin)) * 80.f;
-    v.s = ((gs[i] + 1.0f) / 2.0f) * 80.f;
-    const int y = i / W, x = i - y * W;
-    v.valid = (v.s < 80.f) && (v.g < 80.f) && (v.s > 1.f) && (v.g > 1.f) && y >= y1 && y < y2 && x >= x1 && x < x2;
-    return v;
-}
-
-__global__ __launch_bounds__(MT) void depth_metrics_kernel(const float* __restrict__ gt_sparse,
-                                                           const float* __restrict__ gt,
-                                                           const float* __restrict__ pred, int H, int W, int y1,
-                                                           int y2, int x1, int x2, double* __restrict__ per_image) {
-    __shared__ double shd[MT / 64];
-    __shared__ float shf[4][MT / 64];
-    __shared__ int hist[256];
-    __shared__ unsigned sel_prefix;
-    __shared__ int sel_k;
-    const int b = blockIdx.x, n = H * W, tid = threadIdx.x;
-    const float* gs = gt_sparse + (size_t)b * n;
-    const float* g = gt + (size_t)b * n;
-    const float* p = pred + (size_t)b * n;
-
-    // ---- min / max over the whole image (calculate_error.py:38-39) ----
-    float gmin = INFINITY, gmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY;
-    for (int i = tid; i < n; i += MT) {
-        const float a = g[i], c = p[i];
-        gmin = fminf(gmin, a); gmax = fmaxf(gmax, a); pmin = fminf(pmin, c); pmax = fmaxf(pmax, c);
-    }
+// lo[k] = a[k].min(), hi[k] = a[k].max() over the n pixels of K planes of one image as torch gives them: NaN when a pixel
+// is NaN, +-inf kept (the normalisation that follows then yields 0 and NaN by plain IEEE arithmetic, as torch's does).
+// The pixel loop keeps fminf / fmaxf and only notes, per wave, that a lane saw a NaN (one compare into a lane mask); the
+// few steps across lanes and waves carry it.  All MT threads call it; all get the result.
+template <int K>
+__device__ __forceinline__ void image_minmax(const float* const (&a)[K], int n, float (&lo)[K], float (&hi)[K],
+                                             float* shlo, float* shhi) {
+    unsigned long long nan[K];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        gmin = fminf(gmin, __shfl_xor(gmin, o, 64)); gmax = fmaxf(gmax, __shfl_xor(gmax, o, 64));
-        pmin = fminf(pmin, __shfl_xor(pmin, o, 64)); pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
-    }
-    if ((tid & 63) == 0) { shf[0][tid >> 6] = gmin; shf[1][tid >> 6] = gmax; shf[2][tid >> 6] = pmin; shf[3][tid >> 6] = pmax; }
-    __syncthreads();
-    for (int i = 0; i < MT / 64; ++i) {
-        gmin = fminf(gmin, shf[0][i]); gmax = fmaxf(gmax, shf[1][i]);
-        pmin = fminf(pmin, shf[2][i]); pmax = fmaxf(pmax, shf[3][i]);
-    }
-
-    // ---- count of valid pixels ----
-    int cnt = 0;
-    for (int i = tid; i < n; i += MT) cnt += load_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2).valid ? 1 : 0;
-    const int nvalid = (int)(block_sum_d1024((double)cnt, shd) + 0.5);
-
-    // ---- lower medians (torch.median) of valid gt and valid pred ----
-    float med[2] = {0.f, 0.f};
-    for (int which = 0; which < 2; ++which) {
-        unsigned prefix = 0u, mask = 0u;
-        int kk = nvalid > 0 ? (nvalid - 1) / 2 : 0;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            __syncthreads();
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += MT) {
-                const PixVals v = load_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2);
-                if (!v.valid) continue;
-                const unsigned bits = __float_as_uint(which == 0 ? v.g : v.p);
-                if ((bits & mask) == prefix) atomicAdd(&hist[(bits >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int cum = 0, sel = 255;
-                for (int q = 0; q < 256; ++q) {
-                    if (cum + hist[q] > kk) { sel = q; break; }
-                    cum += hist[q];
-                }
-                sel_k = kk - cum;
-                sel_prefix = prefix | ((unsigned)sel << shift);
-            }
-            __syncthreads();
-            kk = sel_k;
-            prefix = sel_prefix;
-            mask |= 0xFFu << shift;
+    for (int k = 0; k < K; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; nan[k] = 0ull; }
+    for (int i = threadIdx.x; i < n; i += MT) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float v = a[k][i];
+            lo[k] = fminf(lo[k], v); hi[k] = fmaxf(hi[k], v); nan[k] |= __ballot(v != v);
         }
-        med[which] = __uint_as_float(prefix);
     }
-
-    // ---- the eight reductions over valid pixels ----
-    double s_abs = 0, s_rel = 0, s_sq = 0, c1 = 0, c2 = 0, c3 = 0, s_d2 = 0, s_log = 0;
-    for (int i = tid; i < n; i += MT) {
-        const PixVals v = load_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2);
-        if (!v.valid) continue;
-        float vp = v.p * med[0] / med[1];
-        vp = fminf(fmaxf(vp, 1.f), 80.f);
-        const float vg = v.g;
-        const float th = fmaxf(vg / vp, vp / vg);
-        const float d = vg - vp;
-        s_abs += (double)fabsf(d);
-        s_rel += (double)(fabsf(d) / vg);
-        s_sq += (double)((d * d) / vg);
-        c1 += th < 1.25f ? 1.0 : 0.0;
-        c2 += th < 1.5625f ? 1.0 : 0.0;
-        c3 += th < 1.953125f ? 1.0 : 0.0;
-        s_d2 += (double)(d * d);
-        const float lg = logf(vg) - logf(vp);
-        s_log += (double)(lg * lg);
-    }
-    s_abs = block_sum_d1024(s_abs, shd); s_rel = block_sum_d1024(s_rel, shd); s_sq = block_sum_d1024(s_sq, shd);
-    c1 = block_sum_d1024(c1, shd); c2 = block_sum_d1024(c2, shd); c3 = block_sum_d1024(c3, shd);
-    s_d2 = block_sum_d1024(s_d2, shd); s_log = block_sum_d1024(s_log, shd);
-    if (tid == 0) {
-        const double nv = (double)nvalid;
-        double* o = per_image + (size_t)b * 8;
-        o[0] = s_abs / nv; o[1] = s_rel / nv; o[2] = s_sq / nv;
-        o[3] = c1 / nv; o[4] = c2 / nv; o[5] = c3 / nv;
-        o[6] = sqrt(s_d2 / nv); o[7] = sqrt(s_log / nv);
-    }
-}
-
-__global__ void metrics_mean_kernel(const double* __restrict__ per_image, int B, float* __restrict__ errors) {
-    const int m = threadIdx.x;
-    if (m >= 8) return;
-    double s = 0.0;
-    for (int b = 0; b < B; ++b) s += per_image[(size_t)b * 8 + m];
-    errors[m] = (float)(s / (double)B);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Shared by the NYU / Make3D kernels (the KITTI kernel above keeps its own inline copies).
-
-// block-wide min and max of (lo, hi) for MT threads; every thread gets the result
-__device__ __forceinline__ void block_minmax1024(float& lo, float& hi, float* shlo, float* shhi) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, 64)); hi = fmaxf(hi, __shfl_xor(hi, o, 64)); }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { shlo[threadIdx.x >> 6] = lo; shhi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    for (int i = 0; i < MT / 64; ++i) { lo = fminf(lo, shlo[i]); hi = fmaxf(hi, shhi[i]); }
+    for (int k = 0; k < K; ++k) {
+        if (nan[k]) lo[k] = hi[k] = __builtin_nanf("");
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[k] = min_nan(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = max_nan(hi[k], __shfl_xor(hi[k], o, 64));
+        }
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) { shlo[threadIdx.x >> 6] = lo[k]; shhi[threadIdx.x >> 6] = hi[k]; }
+        __syncthreads();
+        for (int i = 0; i < MT / 64; ++i) { lo[k] = min_nan(lo[k], shlo[i]); hi[k] = max_nan(hi[k], shhi[i]); }
+    }
 }
 
 // k-th smallest (0-based) of { v : f(i, v) is true, 0 <= i < n } by an 8-bit radix select over the float bits.
-// Every selected value must be >= +0 (bit order == value order).  All MT threads call it; all get the result.
+// Every selected value must be >= +0 and not NaN (bit order == value order): the normalised values are, except that a
+// constant or non-finite prediction normalises to NaN -- the kernels count the valid NaN pixels first and, where there
+// is one, take the median to be NaN (torch.median) without coming here.  All MT threads call it; all get the result.
 template <class F>
 __device__ float block_select_kth(F f, int n, int k, int* hist, unsigned* sh_prefix, int* sh_k) {
     const int tid = threadIdx.x;
@@ -197,6 +97,10 @@ __device__ float block_select_kth(F f, int n, int k, int* hist, unsigned* sh_pre
     return __uint_as_float(prefix);
 }
 
+// (x - mn) / (mx - mn) can only be NaN when mx - mn is not a finite positive number: a NaN or +-inf pixel, or mx == mn.
+// Otherwise every x in [mn, mx] normalises to a finite value and nobody has to look for NaN among them.
+__device__ __forceinline__ bool may_normalise_to_nan(float mn, float mx) { return !(mx - mn > 0.f && mx - mn < INFINITY); }
+
 // torch.clamp: NaN stays NaN (fminf / fmaxf alone would drop it)
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
 
@@ -204,6 +108,96 @@ __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return
 __device__ __forceinline__ float minmax_scale(float x, float mn, float mx, float s) {
 #pragma clang fp contract(off)
     return __fdiv_rn(x - mn, mx - mn) * s;
+}
+
+// ---- KITTI: compute_errors (calculate_error.py:10-103) ----
+struct KittiPx { float g, p; bool valid; };
+
+__device__ __forceinline__ KittiPx kitti_px(const float* gs, const float* g, const float* p, int i, int W, float gmin,
+                                            float gmax, float pmin, float pmax, int y1, int y2, int x1, int x2) {
+#pragma clang fp contract(off)
+    KittiPx v;
+    v.p = minmax_scale(p[i], pmin, pmax, 80.f);
+    v.g = minmax_scale(g[i], gmin, gmax, 80.f);
+    const float s = ((gs[i] + 1.0f) * 0.5f) * 80.f;     // x 0.5 is / 2 exactly; a NaN return fails the comparisons below
+    const int y = i / W, x = i - y * W;
+    v.valid = (s < 80.f) && (v.g < 80.f) && (s > 1.f) && (v.g > 1.f) && y >= y1 && y < y2 && x >= x1 && x < x2;
+    return v;
+}
+
+__global__ __launch_bounds__(MT) void depth_metrics_kernel(const float* __restrict__ gt_sparse,
+                                                           const float* __restrict__ gt,
+                                                           const float* __restrict__ pred, int H, int W, int y1,
+                                                           int y2, int x1, int x2, double* __restrict__ per_image) {
+#pragma clang fp contract(off)
+    __shared__ double shd[MT / 64];
+    __shared__ float shf[2][MT / 64];
+    __shared__ int hist[256];
+    __shared__ unsigned sel_prefix;
+    __shared__ int sel_k;
+    const int b = blockIdx.x, n = H * W, tid = threadIdx.x;
+    const float* gs = gt_sparse + (size_t)b * n;
+    const float* g = gt + (size_t)b * n;
+    const float* p = pred + (size_t)b * n;
+
+    const float* const planes[2] = {g, p};      // calculate_error.py:38-39
+    float lo[2], hi[2];
+    image_minmax(planes, n, lo, hi, shf[0], shf[1]);
+    const float gmin = lo[0], gmax = hi[0], pmin = lo[1], pmax = hi[1];
+
+    // the valid count; and, for the median of the prediction, whether a valid pixel's normalised prediction is NaN (its
+    // ground truth passed two comparisons, so that cannot be)
+    const bool p_may_nan = may_normalise_to_nan(pmin, pmax);
+    int cnt = 0;
+    for (int i = tid; i < n; i += MT) cnt += kitti_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2).valid ? 1 : 0;
+    const int nvalid = (int)(block_sum_d1024((double)cnt, shd) + 0.5);
+    bool med_p_nan = false;     // the same in every thread
+    if (p_may_nan) {
+        int nan_p = 0;
+#pragma nounroll        // hardly ever taken: kept small so that it does not cost the passes around it registers
+        for (int i = tid; i < n; i += MT) {
+            const KittiPx q = kitti_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2);
+            nan_p += (q.valid && q.p != q.p) ? 1 : 0;
+        }
+        med_p_nan = block_sum_d1024((double)nan_p, shd) > 0.5;
+    }
+    const int kk = nvalid > 0 ? (nvalid - 1) / 2 : 0;
+
+    const float med_g = block_select_kth([&](int i, float& v) {
+        const KittiPx q = kitti_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2); v = q.g; return q.valid; },
+        n, kk, hist, &sel_prefix, &sel_k);
+    const float med_p = med_p_nan ? __builtin_nanf("") : block_select_kth([&](int i, float& v) {
+        const KittiPx q = kitti_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2); v = q.p; return q.valid; },
+        n, kk, hist, &sel_prefix, &sel_k);
+
+    double s_abs = 0, s_rel = 0, s_sq = 0, c1 = 0, c2 = 0, c3 = 0, s_d2 = 0, s_log = 0;
+    for (int i = tid; i < n; i += MT) {
+        const KittiPx v = kitti_px(gs, g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2);
+        if (!v.valid) continue;
+        const float vp = clamp_nan(__fdiv_rn(v.p * med_g, med_p), 1.f, 80.f);
+        const float vg = v.g;
+        const float th = fmaxf(__fdiv_rn(vg, vp), __fdiv_rn(vp, vg));      // NaN only when both are: vg is finite
+        const float d = vg - vp;
+        s_abs += (double)fabsf(d);
+        s_rel += (double)__fdiv_rn(fabsf(d), vg);
+        s_sq += (double)__fdiv_rn(d * d, vg);
+        c1 += th < 1.25f ? 1.0 : 0.0;
+        c2 += th < 1.5625f ? 1.0 : 0.0;
+        c3 += th < 1.953125f ? 1.0 : 0.0;
+        s_d2 += (double)(d * d);
+        const float lg = logf(vg) - logf(vp);
+        s_log += (double)(lg * lg);
+    }
+    s_abs = block_sum_d1024(s_abs, shd); s_rel = block_sum_d1024(s_rel, shd); s_sq = block_sum_d1024(s_sq, shd);
+    c1 = block_sum_d1024(c1, shd); c2 = block_sum_d1024(c2, shd); c3 = block_sum_d1024(c3, shd);
+    s_d2 = block_sum_d1024(s_d2, shd); s_log = block_sum_d1024(s_log, shd);
+    if (tid == 0) {
+        const double nv = nvalid > 0 ? (double)nvalid : __longlong_as_double(0x7ff8000000000000ll);   // none valid: NaN
+        double* o = per_image + (size_t)b * 8;
+        o[0] = s_abs / nv; o[1] = s_rel / nv; o[2] = s_sq / nv;
+        o[3] = c1 / nv; o[4] = c2 / nv; o[5] = c3 / nv;
+        o[6] = sqrt(s_d2 / nv); o[7] = sqrt(s_log / nv);
+    }
 }
 
 // ---- NYU Depth v2: compute_errors_NYU (calculate_error.py:105-150) ----
@@ -232,23 +226,31 @@ __global__ __launch_bounds__(MT) void depth_metrics_nyu_kernel(const float* __re
     const float* g = gt + (size_t)b * n;
     const float* p = pred + (size_t)b * n;
 
-    float gmin = INFINITY, gmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY;
-    for (int i = tid; i < n; i += MT) {
-        const float a = g[i], c = p[i];
-        gmin = fminf(gmin, a); gmax = fmaxf(gmax, a); pmin = fminf(pmin, c); pmax = fmaxf(pmax, c);
-    }
-    block_minmax1024(gmin, gmax, shf[0], shf[1]);
-    block_minmax1024(pmin, pmax, shf[0], shf[1]);
+    const float* const planes[2] = {g, p};
+    float lo[2], hi[2];
+    image_minmax(planes, n, lo, hi, shf[0], shf[1]);
+    const float gmin = lo[0], gmax = hi[0], pmin = lo[1], pmax = hi[1];
 
+    const bool p_may_nan = may_normalise_to_nan(pmin, pmax);
     int cnt = 0;
     for (int i = tid; i < n; i += MT) cnt += nyu_px(g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2).valid ? 1 : 0;
     const int nvalid = (int)(block_sum_d1024((double)cnt, shd) + 0.5);
+    bool med_p_nan = false;     // the same in every thread
+    if (p_may_nan) {
+        int nan_p = 0;
+#pragma nounroll        // hardly ever taken: kept small so that it does not cost the passes around it registers
+        for (int i = tid; i < n; i += MT) {
+            const NyuPx q = nyu_px(g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2);
+            nan_p += (q.valid && q.p != q.p) ? 1 : 0;
+        }
+        med_p_nan = block_sum_d1024((double)nan_p, shd) > 0.5;
+    }
     const int kk = nvalid > 0 ? (nvalid - 1) / 2 : 0;     // torch.median: the lower of the two middle values
 
     const float med_g = block_select_kth([&](int i, float& v) {
         const NyuPx q = nyu_px(g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2); v = q.g; return q.valid; },
         n, kk, hist, &sel_prefix, &sel_k);
-    const float med_p = block_select_kth([&](int i, float& v) {
+    const float med_p = med_p_nan ? __builtin_nanf("") : block_select_kth([&](int i, float& v) {
         const NyuPx q = nyu_px(g, p, i, W, gmin, gmax, pmin, pmax, y1, y2, x1, x2); v = q.p; return q.valid; },
         n, kk, hist, &sel_prefix, &sel_k);
 
@@ -313,25 +315,31 @@ __global__ __launch_bounds__(MT) void depth_metrics_make3d_kernel(const float* _
     const float* g = gt + (size_t)b * n;
     const float* p = pred + (size_t)b * n;
 
-    float smin = INFINITY, smax = -INFINITY, gmin = INFINITY, gmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY;
-    for (int i = tid; i < n; i += MT) {
-        const float a = s[i], c = g[i], e = p[i];
-        smin = fminf(smin, a); smax = fmaxf(smax, a); gmin = fminf(gmin, c); gmax = fmaxf(gmax, c);
-        pmin = fminf(pmin, e); pmax = fmaxf(pmax, e);
-    }
-    block_minmax1024(smin, smax, shf[0], shf[1]);
-    block_minmax1024(gmin, gmax, shf[0], shf[1]);
-    block_minmax1024(pmin, pmax, shf[0], shf[1]);
+    const float* const planes[3] = {s, g, p};
+    float lo[3], hi[3];
+    image_minmax(planes, n, lo, hi, shf[0], shf[1]);
+    const float smin = lo[0], smax = hi[0], gmin = lo[1], gmax = hi[1], pmin = lo[2], pmax = hi[2];
 
+    const bool p_may_nan = may_normalise_to_nan(pmin, pmax);
     int cnt = 0;
     for (int i = tid; i < n; i += MT) cnt += m3_px(s, g, p, i, smin, smax, gmin, gmax, pmin, pmax).valid ? 1 : 0;
     const int nvalid = (int)(block_sum_d1024((double)cnt, shd) + 0.5);
+    bool med_p_nan = false;     // the same in every thread
+    if (p_may_nan) {
+        int nan_p = 0;
+#pragma nounroll        // hardly ever taken: kept small so that it does not cost the passes around it registers
+        for (int i = tid; i < n; i += MT) {
+            const M3Px q = m3_px(s, g, p, i, smin, smax, gmin, gmax, pmin, pmax);
+            nan_p += (q.valid && q.p != q.p) ? 1 : 0;
+        }
+        med_p_nan = block_sum_d1024((double)nan_p, shd) > 0.5;
+    }
     const int kk = nvalid > 0 ? (nvalid - 1) / 2 : 0;
 
     const float med_g = block_select_kth([&](int i, float& v) {
         const M3Px q = m3_px(s, g, p, i, smin, smax, gmin, gmax, pmin, pmax); v = q.g; return q.valid; },
         n, kk, hist, &sel_prefix, &sel_k);
-    const float med_p = block_select_kth([&](int i, float& v) {
+    const float med_p = med_p_nan ? __builtin_nanf("") : block_select_kth([&](int i, float& v) {
         const M3Px q = m3_px(s, g, p, i, smin, smax, gmin, gmax, pmin, pmax); v = q.p; return q.valid; },
         n, kk, hist, &sel_prefix, &sel_k);
 
@@ -376,7 +384,8 @@ extern "C" int gdn_depth_metrics(const float* gt_sparse, const float* gt, const 
                                  int32_t W, int32_t crop, float* errors, void* workspace, size_t workspace_bytes,
                                  void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
-    if (!gt_sparse || !gt || !pred || !errors || B <= 0 || H <= 0 || W <= 0) return GDN_ERR_BAD_ARG;
+    if (!gt_sparse || !gt || !pred || !errors || B <= 0 || H <= 0 || W <= 0 || (int64_t)H * W > INT32_MAX)
+        return GDN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < gdn_depth_metrics_workspace_bytes(B, H, W)) return GDN_ERR_WORKSPACE;
     int y1 = 0, y2 = H, x1 = 0, x2 = W;
     if (crop) {  // Godard crop, calculate_error.py:28-29
@@ -386,7 +395,7 @@ extern "C" int gdn_depth_metrics(const float* gt_sparse, const float* gt, const 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(depth_metrics_kernel, dim3(B), dim3(MT), 0, st, gt_sparse, gt, pred, H, W, y1, y2, x1, x2,
                        (double*)workspace);
-    hipLaunchKernelGGL(metrics_mean_kernel, dim3(1), dim3(64), 0, st, (const double*)workspace, B, errors);
+    hipLaunchKernelGGL(metrics_mean_m_kernel, dim3(1), dim3(64), 0, st, (const double*)workspace, B, 8, errors);
     return gdn_launch_status();
 }
 

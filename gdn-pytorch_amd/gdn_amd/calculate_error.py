@@ -2,7 +2,13 @@
 compute_errors_NYU :105-150, compute_errors_Make3D :152-182).
 
 Where the reference raises (an image with no valid pixel: torch.median of an empty tensor) these return NaN for that
-image, so the batch mean is NaN."""
+image, so the batch mean is NaN.
+
+Non-finite inputs give what the reference gives, since torch's min / max / median propagate NaN and clamp keeps it: a NaN
+or +-inf pixel in pred, or a constant pred (0 / 0 in the min-max normalisation), makes every sum NaN and a1 = a2 = a3 = 0
+-- a diverged network does not get finite numbers -- and a NaN pixel in gt, or a constant gt, leaves no valid pixel (NaN
+throughout).  A NaN in compute_errors' gt_np only drops that pixel; compute_errors_Make3D normalises gt_np as well, so
+there it leaves none."""
 
 from . import ops
 from ._lib import GdnError

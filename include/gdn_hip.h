@@ -600,6 +600,14 @@ int gdn_silog_masked(const float* out, const float* gt, const float* sparse, int
  * Depth metrics, calculate_error.py:10-103: per image min-max -> x80, Godard
  * crop, validity mask, median scaling (lower median), clamp, 8 reductions.
  * gt_sparse/gt/pred are [B,1,H,W]; errors[8] = batch means, device memory.
+ * H * W > INT32_MAX is GDN_ERR_BAD_ARG (here and in the two variants below).
+ * Non-finite inputs give torch's results, in all three: min / max / median
+ * propagate NaN and the clamp keeps it.  A NaN or +-inf pixel in pred, or a
+ * constant pred (0 / 0), gives NaN for every sum and a1 = a2 = a3 = 0; a NaN
+ * pixel in gt, or a constant gt, leaves no valid pixel, which like any image
+ * without one gives NaN throughout (the reference raises: torch.median of an
+ * empty tensor).  A NaN in gt_sparse only drops that pixel here; in the
+ * Make3D variant, which min-max normalises gt_np too, it leaves none.
  * ---------------------------------------------------------------------- */
 size_t gdn_depth_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int gdn_depth_metrics(const float* gt_sparse, const float* gt, const float* pred,

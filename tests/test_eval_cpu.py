@@ -45,6 +45,166 @@ def test_restatement_matches_reference_kitti(golden):
     np.testing.assert_allclose(E.compute_errors(*args, crop=False), g["metrics.errors_nocrop"], rtol=1e-5)
 
 
+EDGE_NAMES = [c[0] for c in E.EDGE_CASES]
+
+
+def _images(case):
+    """(gt_np, gt, pred) [H,W] of every image of an edge case."""
+    s, g, p = E.edge_inputs(case)
+    return [(s[b, 0], g[b, 0], p[b, 0]) for b in range(g.shape[0])]
+
+
+def test_edge_inputs_rebuild_bit_for_bit(golden):
+    g = golden["metrics_edges"]
+    assert [str(c) for c in g["cases"]] == EDGE_NAMES
+    for name, _, B, H, W, _ in E.EDGE_CASES:
+        arrays = E.edge_inputs(name)
+        assert all(a.shape == (B, 1, H, W) and a.dtype == np.float32 for a in arrays), name
+        assert E.inputs_digest(arrays) == str(g[name + "_digest"]), name
+        assert H * W <= 3328
+
+
+def test_edge_set_sizes_and_valid_counts():
+    """The set straddles the 1024-thread workgroup and the 64-lane wave, holds one and two valid pixels, and even and odd
+    valid counts under both masks (the lower median of an even count is where an upper median would differ)."""
+    sizes = {c[3] * c[4] for c in E.EDGE_CASES}
+    assert {24, 1023, 1024, 1025, 3328} <= sizes and min(sizes) < 64
+    (s, g, p), = _images("s4x6")
+    assert E.Rules.box(4, 6, *E.KITTI_BOX) == (int(0.33 * 4), 3, 0, 5)
+    assert E.kitti_masked(s, g, p, True)[0].size == 1
+    (s, g, p), = _images("two")
+    assert [E.kitti_masked(s, g, p, c)[0].size for c in (True, False)] == [2, 2]
+    assert [E.nyu_masked(g, p, c)[0].size for c in (True, False)] == [2, 2]
+    nk = [E.kitti_masked(*im, c)[0].size for n in EDGE_NAMES for im in _images(n) for c in (True, False)]
+    nn = [E.nyu_masked(im[1], im[2], c)[0].size for n in EDGE_NAMES for im in _images(n) for c in (True, False)]
+    for counts in (nk, nn):
+        assert any(n > 1 and n % 2 == 0 for n in counts) and any(n > 1 and n % 2 == 1 for n in counts)
+        assert 0 in counts
+
+
+def test_edge_medians_straddle_a_radix_bucket():
+    """The two middle values of the valid gt lie on either side of 8.0, those of the valid pred on either side of 2.0: the
+    top byte of the float32 bit pattern, the first digit of the kernels' radix select, changes there."""
+    for case, which, edge in (("bucket_g", 0, 8.0), ("bucket_p", 1, 2.0)):
+        (s, g, p), = _images(case)
+        for crop in (True, False):
+            v = np.sort(E.kitti_masked(s, g, p, crop)[which])
+            assert v.size % 2 == 0 and v.size >= 64
+            lo, hi = v[v.size // 2 - 1], v[v.size // 2]
+            assert lo < edge <= hi, (case, lo, hi)
+            assert lo.view(np.uint32) >> 24 != hi.view(np.uint32) >> 24
+            assert E._median(v) == lo
+
+
+def test_edge_thresholds_tie_exactly():
+    """`thresh`: float32 thresh equals 1.25, 1.5625 and 1.953125 on at least 32 valid pixels each, under the KITTI and the
+    NYU mask.  The comparison is strict, so none of them counts; a1..a3 hold exactly the pixels strictly below."""
+    (s, g, p), = _images("thresh")
+    for crop in (True, False):
+        for (vg, vp), lo, hi, row in ((E.kitti_masked(s, g, p, crop), 1, 80, E._per_image_kitti(s, g, p, crop)),
+                                      (E.nyu_masked(g, p, crop), 1e-3, 10, E._per_image_nyu(g, p, crop))):
+            _, th = E.scaled_thresh(vg, vp, lo, hi)
+            assert th.dtype == np.float32
+            for k, bound in enumerate((1.25, 1.5625, 1.953125)):
+                assert int((th == np.float32(bound)).sum()) >= 32, (crop, bound)
+                assert row[3 + k] == (th < bound).sum() / th.size
+                assert row[3 + k] < (th <= bound).sum() / th.size
+
+
+def test_edge_sparse_nan_only_drops_its_pixel():
+    (s, g, p), = _images("sparse_nan")
+    y, x = E.NAN_AT
+    assert np.isnan(s[y, x]) and np.isfinite(E._per_image_kitti(s, g, p, True)).all()
+    s2 = s.copy()
+    s2[y, x] = 0.0
+    assert E.kitti_masked(s2, g, p, True)[0].size == E.kitti_masked(s, g, p, True)[0].size + 1
+
+
+def _assert_rows(got, want, msg):
+    assert got.shape == want.shape, msg
+    assert np.array_equal(np.isnan(got), np.isnan(want)), msg
+    np.testing.assert_allclose(got, want, rtol=1e-5, err_msg=msg)          # NaN == NaN here; positions checked above
+
+
+def test_restatement_matches_reference_edges(golden):
+    """The restatement against the reference's own results on the edge inputs, image by image: the same NaN positions
+    (the reference's NaN rows where it raises included) and finite values at rtol 1e-5."""
+    g = golden["metrics_edges"]
+    for case in EDGE_NAMES:
+        s, gt, p = E.edge_inputs(case)
+        for crop, tag in ((True, "crop"), (False, "nocrop")):
+            _assert_rows(E.kitti_per_image(s, gt, p, crop), g["%s_kitti_%s_per" % (case, tag)], (case, "kitti", tag))
+            _assert_rows(E.nyu_per_image(gt, p, crop), g["%s_nyu_%s_per" % (case, tag)], (case, "nyu", tag))
+        _assert_rows(E.make3d_per_image(s, gt, p), g[case + "_make3d_per"], (case, "make3d"))
+    rows = g["pred_const_kitti_crop_per"][0]
+    assert np.isnan(rows[[0, 1, 2, 6, 7]]).all() and (rows[3:6] == 0).all()
+    assert np.isnan(g["gt_nan_kitti_crop_per"]).all() and np.isnan(g["gt_nan_make3d_per"]).all()
+    mixed = g["mixed_kitti_crop_per"].mean(0)
+    assert np.array_equal(np.isnan(mixed), np.isnan(E.compute_errors(*E.edge_inputs("mixed")))) and np.isnan(mixed).all()
+
+
+def test_restatement_matches_reference_kitti_on_eval_cases(golden):
+    """compute_errors of the reference on the inputs of metrics_eval.npz (the tie cases among them)."""
+    g = golden["metrics_edges"]
+    for case in [c[0] for c in E.GOLDEN_CASES]:
+        s, gt, p = E.golden_inputs(case)
+        for crop, tag in ((True, "crop"), (False, "nocrop")):
+            _assert_rows(E.kitti_per_image(s, gt, p, crop), g["%s_kitti_%s_per" % (case, tag)], (case, tag))
+            _assert_rows(E.compute_errors(s, gt, p, crop), g["%s_kitti_%s" % (case, tag)], (case, tag))
+
+
+def _upper_median(v):
+    return np.float32("nan") if np.isnan(v).any() else np.sort(v)[v.size // 2]
+
+
+def _shifted(dy, dx):
+    def box(H, W, fy, fx):
+        y1, y2, x1, x2 = E.Rules.box(H, W, fy, fx)
+        return y1 + dy, y2 + dy, x1 + dx, x2 + dx
+    return staticmethod(box)
+
+
+def _nanskip(f):
+    def g(x):
+        return f(x) if not np.isnan(x).all() else np.float32("nan")
+    return staticmethod(g)
+
+
+WRONG = {
+    "upper median": dict(median=staticmethod(_upper_median)),
+    "<= at the thresholds": dict(less=staticmethod(np.less_equal)),
+    "crop one row down": dict(box=_shifted(1, 0)),
+    "crop one row up": dict(box=_shifted(-1, 0)),
+    "crop one column right": dict(box=_shifted(0, 1)),
+    "crop one column left": dict(box=_shifted(0, -1)),
+    "clamp drops NaN": dict(clip=staticmethod(lambda v, lo, hi: np.fmin(np.fmax(v, lo), hi))),
+    "min/max skip NaN": dict(amin=_nanskip(np.nanmin), amax=_nanskip(np.nanmax)),
+}
+# the log metrics' bar of test_hip_metric_edges.py can only be smaller than this cap
+LOG_BAR_CAP = 1e-5
+
+
+@pytest.mark.parametrize("wrong", sorted(WRONG))
+def test_edge_cases_catch_wrong_variants(wrong):
+    """Each wrong variant of the arithmetic, run in the restatement's place, misses the bars the kernels are held to
+    (test_hip_metric_edges.py) on at least one edge case -- per kernel it can affect: the cases can catch that error."""
+    R = type("Wrong", (E.Rules,), WRONG[wrong])
+    caught = {"kitti": [], "nyu": [], "make3d": []}
+    for case in EDGE_NAMES:
+        s, gt, p = E.edge_inputs(case)
+        for crop in (True, False):
+            for kind, fn, args in (("kitti", E.kitti_per_image, (s, gt, p, crop)), ("nyu", E.nyu_per_image, (gt, p, crop)),
+                                   ("make3d", E.make3d_per_image, (s, gt, p))):
+                for got, want in zip(fn(*args, R=R), fn(*args)):
+                    if E.row_mismatch(got.astype(np.float32), want, kind, LOG_BAR_CAP):
+                        caught[kind].append(case)
+    applies = {"kitti", "nyu", "make3d"}
+    if "threshold" in wrong or "crop" in wrong:
+        applies.discard("make3d")               # Make3D has neither thresholds nor a crop box
+    for kind in sorted(applies):
+        assert caught[kind], "%s survives every edge case of %s" % (wrong, kind)
+
+
 def test_restatement_bytescale_constant_image():
     assert (E.bytescale(np.full((1, 4, 5), 3.5, np.float32)) == 0).all()      # cscale 0 -> 1: (x - min) = 0 -> 0
     x = np.array([[[0.0, 1.0], [0.5, 0.25]]], np.float32)
