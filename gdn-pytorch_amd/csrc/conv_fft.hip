@@ -23,6 +23,7 @@
 //                    ordered launches (even tiles store, odd tiles add) -- deterministic, no atomics
 //   weight gradient  P[bin] = Df[bin]^T * Xf[bin] (reduction over tiles, MFMA), inverse DFT at the k*k taps only
 #include "common.h"
+#include "bn_math.h"
 #include <cstdlib>
 #include "up2x.h"
 
@@ -931,8 +932,7 @@ __global__ __launch_bounds__(NP * FFT_CG_OF(NP), NP == 16 ? 4 : 2) void fft2d_fw
                     const int bb = hb * HB + b2, ix = ix0 + bb;
                     const bool colok = bb < nvalid && ix >= 0 && ix < g.W;
                     const float d = dv[b2], yv = im[bb];
-                    const float dz = (in_relu && !(yv * bs + bt > 0.f)) ? 0.f : d;
-                    const float val = bsl * (dz - k1 - ((yv - bmu) * bis) * k2);
+                    const float val = bn_bwd_dy(bn_dz(d, yv, bs, bt, in_relu), bn_xhat(yv, bmu, bis), bsl, k1, k2);
                     re[bb] = colok ? val : 0.f;
                     im[bb] = 0.f;
                 }
@@ -1112,7 +1112,7 @@ __global__ __launch_bounds__(NP * FFT_CG_OF(NP), NP == 16 ? 8 : NP == 32 ? 4 : 2
 // patch-column of every x is tabulated once per workgroup in LDS (no division per pixel).
 // bnb_y != NULL: dx is the final gradient of z = [relu](BN_train(bnb_y)) (this layer's input): the workgroup also emits that
 // BatchNorm's backward partial sums (sum dz, sum dz * xhat; bnb_co = {scale, shift, mean, invstd}[C]) into bnb_part[blockIdx.x][2][C]
-// -- the values are in registers here, so the stand-alone reduce pass over (dx, y) (bn_bwd_reduce: two tensor reads) becomes one
+// -- the values are in registers here, so the stand-alone reduce pass over (dx, y) (bn_bwd_sums_kernel: two tensor reads) becomes one
 // read of y.  Fixed order everywhere: a thread's pixels in sequence, the threads of a channel group in index order.
 constexpr int FFT_GATHER_MAX_W = 1024;       // widest output row the x table holds (wider rows: gdn_fftconv_bwd takes the two-kernel inverse)
 constexpr int FFT_GATHER_MAX_BLOCKS = 8192;  // workgroups (= BatchNorm-backward partial slots) of one gather launch
@@ -1168,9 +1168,9 @@ __global__ __launch_bounds__(256) void fft_overlap_gather_kernel(const float* __
                 const f32x4 yv = *reinterpret_cast<const f32x4*>(bnb_y + px * ld_bnb + c4 * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float dz = (bnb_relu && !(yv[e] * bsc[e] + bsh[e] > 0.f)) ? 0.f : s[e];
+                    const float dz = bn_dz(s[e], yv[e], bsc[e], bsh[e], bnb_relu);
                     s1[e] += dz;
-                    s2[e] += dz * ((yv[e] - bmu[e]) * bis[e]);
+                    s2[e] += dz * bn_xhat(yv[e], bmu[e], bis[e]);
                 }
             }
         }

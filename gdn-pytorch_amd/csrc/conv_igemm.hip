@@ -22,6 +22,7 @@
 // (issue loads for k-step i+1, run the MFMAs of k-step i, then write LDS) so
 // HBM/L2 latency hides under the 2-4k MFMA cycles of a k-step.
 #include "common.h"
+#include "bn_math.h"
 #include "up2x.h"
 
 #define MAX_TAPS 81
@@ -964,34 +965,22 @@ __global__ __launch_bounds__(256) void splitk_combine_kernel(const float* __rest
                 }
                 st4_any(y, (size_t)pix * ldy + c, v, bf16);
                 if (bnb_y) {
-                    // v is the final gradient of z = [relu](BN(bnb_y)): the BatchNorm backward's partial sums (conv_ring.h, same arithmetic)
+                    // v is the final gradient of z = [relu](BN(bnb_y)): the BatchNorm backward's partial sums (bn_math.h)
                     const f32x4 yv = ld4_any(bnb_y, (size_t)pix * ld_bnb + c, bf16);
                     const f32x4 sc = *reinterpret_cast<const f32x4*>(bnb_co + c), sf = *reinterpret_cast<const f32x4*>(bnb_co + N + c);
                     const f32x4 mu = *reinterpret_cast<const f32x4*>(bnb_co + 2 * N + c), is = *reinterpret_cast<const f32x4*>(bnb_co + 3 * N + c);
                     // (the gradient as the consumer reads it: rounded to the tensor's dtype)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float dz = bf16 ? bf16_h_to_f32(f32_to_bf16_h(v[e])) : v[e];
-                        if (bnb_relu && !(yv[e] * sc[e] + sf[e] > 0.f)) dz = 0.f;
-                        s1[e] += dz; s2[e] += dz * ((yv[e] - mu[e]) * is[e]);
+                        const float dz = bn_dz(bf16 ? bf16_h_to_f32(f32_to_bf16_h(v[e])) : v[e], yv[e], sc[e], sf[e], bnb_relu);
+                        s1[e] += dz; s2[e] += dz * bn_xhat(yv[e], mu[e], is[e]);
                     }
                 }
             }
         }
         if (stats) {
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { sh[threadIdx.x * 8 + e] = s1[e]; sh[threadIdx.x * 8 + 4 + e] = s2[e]; }
-            __syncthreads();
-            if (ty == 0) {
-                f32x4 r1 = {0.f, 0.f, 0.f, 0.f}, r2 = {0.f, 0.f, 0.f, 0.f};
-                for (int j = 0; j < PY; ++j) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { r1[e] += sh[(j * CQ + tx) * 8 + e]; r2[e] += sh[(j * CQ + tx) * 8 + 4 + e]; }
-                }
-                *reinterpret_cast<f32x4*>(stats + ((size_t)blockIdx.x * 2 + 0) * N + c) = r1;
-                *reinterpret_cast<f32x4*>(stats + ((size_t)blockIdx.x * 2 + 1) * N + c) = r2;
-            }
+            float* dst = stats + (size_t)blockIdx.x * 2 * N + c;
+            bn_lane_reduce(sh, s1, s2, tx, ty, CQ, PY, dst, dst + N);
         }
     }
 }

@@ -15,6 +15,7 @@
 // dW = G^T [ sum_tiles (B^T d B) (.) (A dy A^T) ] G: V is kept from the forward, dy gets the 2x2 -> 4x4 transform, the sum
 // over tiles is a reduction GEMM per bin on the MFMA, and a last small kernel folds the 16 bins into the 9 taps.
 #include "common.h"
+#include "bn_math.h"
 #include "wino_gemm.h"
 #include "up2x.h"
 #include "gemm_x3.h"
@@ -296,9 +297,8 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
                     y[px * ldy + n] = val;
                     if (bnb_y) {
                         const float yv = bnb_y[px * ld_bnb + n];
-                        float dz = val;
-                        if (bnb_relu && !(yv * bsc + bt > 0.f)) dz = 0.f;
-                        s1 += dz; s2 += dz * ((yv - bmu) * bis);
+                        const float dz = bn_dz(val, yv, bsc, bt, bnb_relu);
+                        s1 += dz; s2 += dz * bn_xhat(yv, bmu, bis);
                     }
                 }
             }
@@ -728,9 +728,8 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
                 if (act & GDN_ACT_TANH) val = tanhf(val);
                 out[i][j] = val;
                 if (BNB) {
-                    float dz = val;
-                    if (bnb_relu && !(yv[i][j] * bsc + bt > 0.f)) dz = 0.f;
-                    s1 = ok ? s1 + dz : s1; s2 = ok ? s2 + w4_mul_rn(dz, (yv[i][j] - bmu) * bis) : s2;
+                    const float dz = bn_dz(val, yv[i][j], bsc, bt, bnb_relu);
+                    s1 = ok ? s1 + dz : s1; s2 = ok ? s2 + w4_mul_rn(dz, bn_xhat(yv[i][j], bmu, bis)) : s2;
                 }
             }
         }

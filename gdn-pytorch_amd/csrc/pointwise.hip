@@ -3,20 +3,18 @@
 // All are 16-byte-per-lane streaming kernels (NHWC, channel count % 4 == 0).
 // The optimizer's kernels are in optim.hip.
 #include "common.h"
+#include "bn_math.h"
 #include "up2x.h"
 
 namespace {
 
-// log2 of v if v is a power of two, else -1: the channel-quad counts of these networks (16..128) all are, which turns
-// the per-element 64-bit division of the flat index into a shift (the division alone cost more than the memory traffic).
+// log2 of v if v is a power of two, else -1: the channel-vector counts of these networks (16..128) all are, which turns
+// the per-element 64-bit division of the flat index into a shift (bn_split, bn_math.h).
 inline int pow2_shift(int v) {
     for (int s = 0; s < 31; ++s)
         if ((1 << s) == v) return s;
     return -1;
 }
-#define SPLIT_PIX_C(i, cq, sh, pix, c)                                       \
-    const int64_t pix = (sh) >= 0 ? ((i) >> (sh)) : (i) / (cq);              \
-    const int c = (int)((sh) >= 0 ? ((i) & ((cq) - 1)) : ((i) - pix * (cq))) * 4
 
 // ------------------------------------------------------------------ BN forward
 __global__ __launch_bounds__(256) void bn_finalize_train_kernel(
@@ -52,114 +50,99 @@ __global__ __launch_bounds__(256) void bn_finalize_train_kernel(
     }
 }
 
-__global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv,
-                                      float eps, int C, float* scale, float* shift) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
+// scale / shift of a BatchNorm applied with its RUNNING statistics (eval mode, frozen layers); returns invstd
+__device__ __forceinline__ float bn_running_coeffs(const float* gamma, const float* beta, const float* rm, const float* rv,
+                                                   float eps, int c, float* scale, float* shift) {
     const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     const float inv = 1.0f / sqrtf(rv[c] + eps);
     scale[c] = g * inv;
     shift[c] = b - rm[c] * g * inv;
+    return inv;
 }
 
+__global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv,
+                                      float eps, int C, float* scale, float* shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    bn_running_coeffs(gamma, beta, rm, rv, eps, c, scale, shift);
+}
+
+// out = [relu](y * scale + shift) (+ residual).  NH = 2 for bf16 tensors: 8 channels per lane, 16-byte accesses.
+template <int NH>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const void* __restrict__ y, int ldy,
                                                        const float* __restrict__ scale,
                                                        const float* __restrict__ shift,
                                                        const void* __restrict__ res, int ld_res,
                                                        void* __restrict__ out, int ld_out, int64_t npix, int C,
                                                        int relu, int dt, int sh) {
-    const int cq = C >> 2;
-    const int64_t total = npix * cq;
+    const int cv = C / (4 * NH);
+    const int64_t total = npix * cv;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        SPLIT_PIX_C(i, cq, sh, pix, c);
-        const f32x4 v = ld4_any(y, pix * ldy + c, dt & 1);
-        const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c);
-        const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c);
-        f32x4 o = v * s + t;
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
-        }
-        if (res) o += ld4_any(res, pix * ld_res + c, dt & 2);
-        st4_any(out, pix * ld_out + c, o, dt & 4);
-    }
-}
-
-// bf16 tensors: 8 channels per lane (16-byte accesses); same arithmetic
-__global__ __launch_bounds__(256) void bn_apply8_kernel(const void* __restrict__ y, int ldy,
-                                                        const float* __restrict__ scale,
-                                                        const float* __restrict__ shift,
-                                                        const void* __restrict__ res, int ld_res,
-                                                        void* __restrict__ out, int ld_out, int64_t npix, int C,
-                                                        int relu, int dt, int sh) {
-    const int co = C >> 3;
-    const int64_t total = npix * co;
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t pix = sh >= 0 ? (i >> sh) : i / co;
-        const int c = (int)(sh >= 0 ? (i & (co - 1)) : (i - pix * co)) * 8;
-        f32x4 v0, v1;
-        ld8_any(y, pix * ldy + c, dt & 1, v0, v1);
-        f32x4 o0 = v0 * *reinterpret_cast<const f32x4*>(scale + c) + *reinterpret_cast<const f32x4*>(shift + c);
-        f32x4 o1 = v1 * *reinterpret_cast<const f32x4*>(scale + c + 4) + *reinterpret_cast<const f32x4*>(shift + c + 4);
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { o0[e] = fmaxf(o0[e], 0.f); o1[e] = fmaxf(o1[e], 0.f); }
-        }
-        if (res) {
-            f32x4 r0, r1;
-            ld8_any(res, pix * ld_res + c, dt & 2, r0, r1);
-            o0 += r0; o1 += r1;
-        }
-        st8_any(out, pix * ld_out + c, o0, o1, dt & 4);
+        int64_t pix; int c;
+        bn_split<NH>(i, cv, sh, pix, c);
+        BnLane<NH> s, t, o;
+        o.load(y, pix * ldy + c, dt & 1);
+        s.coef(scale, c);
+        t.coef(shift, c);
+        o.act(s, t, relu, res, pix * ld_res + c, dt & 2, 0);
+        o.store(out, pix * ld_out + c, dt & 4);
     }
 }
 
 // ----------------------------------------------------------------- BN backward
-#define BNB_MAXBLK 1024
-// pass 1: partial[blk][2][C] = sum over the block's pixels of dz, dz*xhat
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
+#define BNB_MAXBLK 1024      // blocks of pass 1 on batch statistics (gdn_bn_bwd, gdn_bn_bwd_coeffs)
+#define BNF_MAXBLK 2048      // ... on frozen statistics (gdn_bn_frozen_bwd)
+// pass 1: partial[blk][2][C] = sum over the block's pixels of dz, dz*xhat; with DY also dy = scale * dz, the whole backward of
+// a BatchNorm on FROZEN statistics (no reduction feeds back into dy).  Channel-vector lanes x pixel lanes over one contiguous
+// pixel range per block, 8 KB of LDS.  A lane sums its pixels in order, lane 0 of each channel vector adds the pixel lanes in
+// order (bn_lane_reduce): a fixed order, no atomics.
+template <int NH, bool DY>
+__global__ __launch_bounds__(256) void bn_bwd_sums_kernel(
     const void* __restrict__ dout, int ld_dout, const void* __restrict__ y, int ldy,
     const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float* __restrict__ partial, int64_t npix, int C, int relu, int dt) {
+    const float* __restrict__ invstd, void* __restrict__ dy, int ld_dy, float* __restrict__ partial, int64_t npix, int C,
+    int relu, int dt) {
     __shared__ float sh[256 * 8];
-    const int cq = C >> 2;
-    const int CQ = cq < 256 ? cq : 256;      // channel-quad lanes
+    const int cv = C / (4 * NH);
+    const int CQ = cv < 256 ? cv : 256;      // channel-vector lanes
     const int PY = 256 / CQ;                 // pixel lanes
     const int tx = threadIdx.x % CQ, ty = threadIdx.x / CQ;
     const int64_t per = cdiv64(npix, gridDim.x);
     const int64_t p0 = blockIdx.x * per, p1 = (p0 + per < npix) ? p0 + per : npix;
-    for (int q = tx; q < cq; q += CQ) {
-        const int c = q * 4;
-        f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
-        if (ty < PY) {
-            const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c);
-            const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c);
-            const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c);
-            const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + c);
+    for (int q0 = 0; q0 < cv; q0 += CQ) {    // (uniform trip count: bn_lane_reduce's barriers are reached by every lane)
+        const int q = q0 + tx;
+        const bool lane = ty < PY && q < cv;
+        const int c = q * 4 * NH;
+        BnLane<NH> a1, a2;
+        a1.zero();
+        a2.zero();
+        if (lane) {
+            BnLane<NH> s, t, mu, is;
+            s.coef(scale, c);
+            t.coef(shift, c);
+            mu.coef(mean, c);
+            is.coef(invstd, c);
             for (int64_t pix = p0 + ty; pix < p1; pix += PY) {
-                const f32x4 d = ld4_any(dout, pix * ld_dout + c, dt & 1);
-                const f32x4 v = ld4_any(y, pix * ldy + c, dt & 2);
+                BnLane<NH> d, v, o;
+                d.load(dout, pix * ld_dout + c, dt & 1);
+                v.load(y, pix * ldy + c, dt & 2);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float dz = d[e];
-                    if (relu && !(v[e] * s[e] + t[e] > 0.f)) dz = 0.f;
-                    a1[e] += dz;
-                    a2[e] += dz * ((v[e] - mu[e]) * is[e]);
+                for (int k = 0; k < NH; ++k) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float dz = bn_dz(d.h[k][e], v.h[k][e], s.h[k][e], t.h[k][e], relu);
+                        if constexpr (DY) o.h[k][e] = bn_fixed_dy(d.h[k][e], v.h[k][e], s.h[k][e], t.h[k][e], relu);
+                        a1.h[k][e] += dz;
+                        a2.h[k][e] += dz * bn_xhat(v.h[k][e], mu.h[k][e], is.h[k][e]);
+                    }
                 }
+                if constexpr (DY) o.store(dy, pix * ld_dy + c, dt & 4);
             }
         }
-        __syncthreads();
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { sh[threadIdx.x * 8 + e] = a1[e]; sh[threadIdx.x * 8 + 4 + e] = a2[e]; }
-        __syncthreads();
-        if (ty == 0) {
-            f32x4 r1 = {0.f, 0.f, 0.f, 0.f}, r2 = {0.f, 0.f, 0.f, 0.f};
-            for (int j = 0; j < PY; ++j) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { r1[e] += sh[(j * CQ + tx) * 8 + e]; r2[e] += sh[(j * CQ + tx) * 8 + 4 + e]; }
-            }
-            *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C + c) = r1;
-            *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C + c) = r2;
+        for (int k = 0; k < NH; ++k) {
+            float* dst = ty == 0 && q < cv ? partial + (size_t)blockIdx.x * 2 * C + c + 4 * k : nullptr;
+            bn_lane_reduce(sh, a1.h[k], a2.h[k], tx, ty, CQ, PY, dst, dst + C);
         }
     }
 }
@@ -186,66 +169,83 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
 }
 
 // pass 3: dy = gamma*invstd * (dz - mean(dz) - xhat*mean(dz*xhat))
+template <int NH>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const void* __restrict__ dout, int ld_dout, const void* __restrict__ y, int ldy,
     const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ k1, const float* __restrict__ k2,
     void* __restrict__ dy, int ld_dy, int64_t npix, int C, int relu, int dt, int sh) {
-    const int cq = C >> 2;
-    const int64_t total = npix * cq;
+    const int cv = C / (4 * NH);
+    const int64_t total = npix * cv;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        SPLIT_PIX_C(i, cq, sh, pix, c);
-        const f32x4 d = ld4_any(dout, pix * ld_dout + c, dt & 1);
-        const f32x4 v = ld4_any(y, pix * ldy + c, dt & 2);
-        const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c);   // gamma*invstd
-        const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c);
-        const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c);
-        const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + c);
-        const f32x4 a = *reinterpret_cast<const f32x4*>(k1 + c);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(k2 + c);
-        f32x4 o;
+        int64_t pix; int c;
+        bn_split<NH>(i, cv, sh, pix, c);
+        BnLane<NH> d, v, s, t, mu, is, a, b, o;
+        d.load(dout, pix * ld_dout + c, dt & 1);
+        v.load(y, pix * ldy + c, dt & 2);
+        s.coef(scale, c);      // gamma*invstd
+        t.coef(shift, c);
+        mu.coef(mean, c);
+        is.coef(invstd, c);
+        a.coef(k1, c);
+        b.coef(k2, c);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float dz = d[e];
-            if (relu && !(v[e] * s[e] + t[e] > 0.f)) dz = 0.f;
-            const float xh = (v[e] - mu[e]) * is[e];
-            o[e] = s[e] * (dz - a[e] - xh * b[e]);
+        for (int k = 0; k < NH; ++k) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float dz = bn_dz(d.h[k][e], v.h[k][e], s.h[k][e], t.h[k][e], relu);
+                o.h[k][e] = bn_bwd_dy(dz, bn_xhat(v.h[k][e], mu.h[k][e], is.h[k][e]), s.h[k][e], a.h[k][e], b.h[k][e]);
+            }
         }
-        st4_any(dy, pix * ld_dy + c, o, dt & 4);
+        o.store(dy, pix * ld_dy + c, dt & 4);
     }
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(
-    const void* __restrict__ dout, int ld_dout, const void* __restrict__ y, int ldy,
-    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ k1, const float* __restrict__ k2,
-    void* __restrict__ dy, int ld_dy, int64_t npix, int C, int relu, int dt, int sh) {
-    const int co = C >> 3;
-    const int64_t total = npix * co;
+// Backward of out = [relu](y*scale + shift) with FIXED per-channel coefficients (eval-mode BatchNorm of a frozen network, or
+// a trained layer whose BatchNorm stays in eval() and whose sums came from the producer of dout): dy = scale * dout * [z > 0].
+// No reductions, no parameter gradients: a flat grid-stride stream.
+template <int NH>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const void* __restrict__ dout, int ld_dout,
+                                                          const void* __restrict__ y, int ldy,
+                                                          const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, void* __restrict__ dy,
+                                                          int ld_dy, int64_t npix, int C, int relu, int dt, int sh) {
+    const int cv = C / (4 * NH);
+    const int64_t total = npix * cv;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t pix = sh >= 0 ? (i >> sh) : i / co;
-        const int c = (int)(sh >= 0 ? (i & (co - 1)) : (i - pix * co)) * 8;
-        f32x4 d[2], v[2], o[2];
-        ld8_any(dout, pix * ld_dout + c, dt & 1, d[0], d[1]);
-        ld8_any(y, pix * ldy + c, dt & 2, v[0], v[1]);
+        int64_t pix; int c;
+        bn_split<NH>(i, cv, sh, pix, c);
+        BnLane<NH> d, s, o;
+        d.load(dout, pix * ld_dout + c, dt & 1);
+        s.coef(scale, c);
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c + 4 * hh);
-            const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c + 4 * hh);
-            const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c + 4 * hh);
-            const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + c + 4 * hh);
-            const f32x4 a = *reinterpret_cast<const f32x4*>(k1 + c + 4 * hh);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(k2 + c + 4 * hh);
+        for (int k = 0; k < NH; ++k) o.h[k] = d.h[k] * s.h[k];
+        if (relu) {
+            BnLane<NH> v, t;
+            v.load(y, pix * ldy + c, dt & 2);
+            t.coef(shift, c);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float dz = d[hh][e];
-                if (relu && !(v[hh][e] * s[e] + t[e] > 0.f)) dz = 0.f;
-                const float xh = (v[hh][e] - mu[e]) * is[e];
-                o[hh][e] = s[e] * (dz - a[e] - xh * b[e]);
+            for (int k = 0; k < NH; ++k) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    // relu == 2: y already IS the activated output (conv + BN + ReLU fused in the conv epilogue)
+                    const bool on = relu == 2 ? v.h[k][e] > 0.f : bn_on(v.h[k][e], s.h[k][e], t.h[k][e]);
+                    if (!on) o.h[k][e] = 0.f;
+                }
             }
         }
-        st8_any(dy, pix * ld_dy + c, o[0], o[1], dt & 4);
+        o.store(dy, pix * ld_dy + c, dt & 4);
     }
+}
+
+// the coefficients of a trained layer whose BatchNorm stays in eval(): bn_eval_coeffs_kernel's scale / shift plus the
+// running mean and invstd that xhat = (y - running_mean) * invstd needs
+__global__ void bn_frozen_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                        int C, float* scale, float* shift, float* mean, float* invstd) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    invstd[c] = bn_running_coeffs(gamma, beta, rm, rv, eps, c, scale, shift);
+    mean[c] = rm[c];
 }
 
 // ------------------------------------------------------------------- upsample
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const void* __restr
 // Round 5 (row N1, bf16 forward half): out = [relu](y * scale + shift) (+ residual) and its x2 bilinear upsampling in ONE pass
 // -- a ResidualBlock's output x + bn2(conv2(.)) followed by F.interpolate (AE_model_unet.py:55-57 -> :336-359).  Reads the raw
 // convolution output and the residual, writes the block output (low resolution; `low` may be null) and the upsampled tensor; the
-// block output is not read back.  Same arithmetic and the same rounding points as bn_apply8_kernel followed by
+// block output is not read back.  Same arithmetic and the same rounding points as bn_apply_kernel followed by
 // upsample2x_fwd_kernel: the four neighbours are rounded to the block output's storage type before they are interpolated, so the
 // two forms agree bit for bit.  grid.y = output row (b, oy); the thread at odd (oy, ox) also stores the low-resolution value.
 __global__ __launch_bounds__(256) void bn_apply_up2x_kernel(const void* __restrict__ y, const float* __restrict__ scale,
@@ -286,26 +286,21 @@ __global__ __launch_bounds__(256) void bn_apply_up2x_kernel(const void* __restri
     float ly; int y0, y1;
     up_src(oy, H, align, ly, y0, y1);
     const size_t xb = (size_t)b * H * W * C;
-    auto act = [&](int yy, int xx, int c, const f32x4& s, const f32x4& t) {
+    auto act = [&](int yy, int xx, int c, const BnLane<1>& s, const BnLane<1>& t) {
         const size_t at = xb + ((size_t)yy * W + xx) * C + c;
-        f32x4 o = ld4_any(y, at, dt & 1) * s + t;
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
-        }
-        if (res) o += ld4_any(res, at, dt & 2);
-        if (dt & 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = bf16_h_to_f32(f32_to_bf16_h(o[e]));
-        }
-        return o;
+        BnLane<1> o;
+        o.load(y, at, dt & 1);
+        o.act(s, t, relu, res, at, dt & 2, dt & 4);
+        return o.h[0];
     };
     for (int j = blockIdx.x * 256 + threadIdx.x; j < Wo * cq; j += gridDim.x * 256) {
         const int ox = sh >= 0 ? j >> sh : j / cq;
         const int c = (sh >= 0 ? j & (cq - 1) : j - ox * cq) * 4;
         float lx; int x0, x1;
         up_src(ox, W, align, lx, x0, x1);
-        const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c), t = *reinterpret_cast<const f32x4*>(shift + c);
+        BnLane<1> s, t;
+        s.coef(scale, c);
+        t.coef(shift, c);
         const f32x4 v00 = act(y0, x0, c, s, t), v01 = act(y0, x1, c, s, t), v10 = act(y1, x0, c, s, t), v11 = act(y1, x1, c, s, t);
         const f32x4 o = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
         st4_any(up, (((size_t)b * Ho + oy) * Wo + ox) * C + c, o, dt & 8);
@@ -337,23 +332,13 @@ __global__ __launch_bounds__(256) void bn_apply_up2x8_kernel(const void* __restr
     const size_t xb = (size_t)b * H * W * C;
     auto act = [&](int yy, int xx, int cc, f32x4& o0, f32x4& o1) {
         const size_t at = xb + ((size_t)yy * W + xx) * C + cc;
-        f32x4 v0, v1;
-        ld8_any(y, at, dt & 1, v0, v1);
-        o0 = v0 * *reinterpret_cast<const f32x4*>(scale + cc) + *reinterpret_cast<const f32x4*>(shift + cc);
-        o1 = v1 * *reinterpret_cast<const f32x4*>(scale + cc + 4) + *reinterpret_cast<const f32x4*>(shift + cc + 4);
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { o0[e] = fmaxf(o0[e], 0.f); o1[e] = fmaxf(o1[e], 0.f); }
-        }
-        if (res) {
-            f32x4 q0, q1;
-            ld8_any(res, at, dt & 2, q0, q1);
-            o0 += q0; o1 += q1;
-        }
-        if (dt & 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { o0[e] = bf16_h_to_f32(f32_to_bf16_h(o0[e])); o1[e] = bf16_h_to_f32(f32_to_bf16_h(o1[e])); }
-        }
+        BnLane<2> s, t, o;
+        o.load(y, at, dt & 1);
+        s.coef(scale, cc);
+        t.coef(shift, cc);
+        o.act(s, t, relu, res, at, dt & 2, dt & 4);
+        o0 = o.h[0];
+        o1 = o.h[1];
     };
     auto load_row = [&](int iy) {                              // block output row iy, columns xb0 - 1 .. xb0 + TXL -> slot iy % 3
         if (iy < 0 || iy >= H) return;                         // (never referenced: up_src clamps)
@@ -515,7 +500,8 @@ __global__ __launch_bounds__(256) void add_pitched_kernel(const void* __restrict
     const int cq = C >> 2;
     const int64_t total = npix * cq;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        SPLIT_PIX_C(i, cq, sh, pix, c);
+        int64_t pix; int c;
+        bn_split<1>(i, cq, sh, pix, c);
         f32x4 v = ld4_any(a, pix * lda + c, dt & 1);
         if (b) v += ld4_any(b, pix * ldb + c, dt & 2);
         st4_any(o, pix * ldo + c, v, dt & 4);
@@ -565,32 +551,75 @@ extern "C" int gdn_bn_eval_coeffs(const float* gamma, const float* beta, const f
     return gdn_launch_status();
 }
 
+// ---- BatchNorm launches.  8-channel lanes (NH = 2) where a tensor is bf16 and the channel count and every pitch in use
+// (0 for an absent tensor) are multiples of 8: 16-byte accesses.
+static bool bn_wide(int dtypes, int C, int ld0, int ld1, int ld2) {
+    return dtypes && (C % 8) == 0 && (ld0 % 8) == 0 && (ld1 % 8) == 0 && (ld2 % 8) == 0;
+}
+
+static void bn_apply_launch(bool wide, hipStream_t st, const void* y, int ldy, const float* scale, const float* shift,
+                            const void* res, int ld_res, void* out, int ld_out, int64_t npix, int C, int relu, int dt) {
+    const int cv = C / (wide ? 8 : 4);
+    hipLaunchKernelGGL(wide ? bn_apply_kernel<2> : bn_apply_kernel<1>, dim3(stream_blocks(npix * cv)), dim3(256), 0, st, y, ldy,
+                       scale, shift, res, ld_res, out, ld_out, npix, C, relu, dt, pow2_shift(cv));
+}
+
+// pass 1 (dy == nullptr), or the whole backward on frozen statistics
+static void bn_bwd_sums_launch(bool wide, int nblk, hipStream_t st, const void* dout, int ld_dout, const void* y, int ldy,
+                               const float* scale, const float* shift, const float* mean, const float* invstd, void* dy,
+                               int ld_dy, float* partial, int64_t npix, int C, int relu, int dt) {
+    auto* k = wide ? (dy ? bn_bwd_sums_kernel<2, true> : bn_bwd_sums_kernel<2, false>)
+                   : (dy ? bn_bwd_sums_kernel<1, true> : bn_bwd_sums_kernel<1, false>);
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(256), 0, st, dout, ld_dout, y, ldy, scale, shift, mean, invstd, dy, ld_dy, partial,
+                       npix, C, relu, dt);
+}
+
+static void bn_bwd_finalize_launch(hipStream_t st, const float* partial, int slots, int C, int64_t npix, float* dgamma,
+                                   float* dbeta, float* k1, float* k2) {
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, slots, C, (double)npix, dgamma, dbeta, k1, k2);
+}
+
+static void bn_bwd_apply_launch(bool wide, hipStream_t st, const void* dout, int ld_dout, const void* y, int ldy,
+                                const float* scale, const float* shift, const float* mean, const float* invstd,
+                                const float* k1, const float* k2, void* dy, int ld_dy, int64_t npix, int C, int relu, int dt) {
+    const int cv = C / (wide ? 8 : 4);
+    hipLaunchKernelGGL(wide ? bn_bwd_apply_kernel<2> : bn_bwd_apply_kernel<1>, dim3(stream_blocks(npix * cv)), dim3(256), 0, st,
+                       dout, ld_dout, y, ldy, scale, shift, mean, invstd, k1, k2, dy, ld_dy, npix, C, relu, dt, pow2_shift(cv));
+}
+
+static void bn_eval_bwd_launch(bool wide, hipStream_t st, const void* dout, int ld_dout, const void* y, int ldy,
+                               const float* scale, const float* shift, void* dy, int ld_dy, int64_t npix, int C, int relu,
+                               int dt) {
+    const int cv = C / (wide ? 8 : 4);
+    hipLaunchKernelGGL(wide ? bn_eval_bwd_kernel<2> : bn_eval_bwd_kernel<1>, dim3(stream_blocks(npix * cv)), dim3(256), 0, st,
+                       dout, ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu, dt, pow2_shift(cv));
+}
+
+static int bn_sums_blocks(int64_t npix, int maxblk) {
+    int64_t b = cdiv64(npix, 64);
+    if (b < 1) b = 1;
+    return (int)(b < maxblk ? b : maxblk);
+}
+static int bnb_blocks(int64_t npix) { return bn_sums_blocks(npix, BNB_MAXBLK); }
+static int bnf_blocks(int64_t npix) { return bn_sums_blocks(npix, BNF_MAXBLK); }
+
 extern "C" int gdn_bn_apply(const void* y, int32_t ldy, const float* scale, const float* shift, const void* residual,
                             int32_t ld_res, void* out, int32_t ld_out, int64_t npix, int32_t C, int32_t relu,
                             int32_t dtypes, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!y || !scale || !shift || !out || npix <= 0 || C <= 0) return GDN_ERR_BAD_ARG;
     if ((C % 4) || (ldy % 4) || (ld_out % 4) || (residual && (ld_res % 4))) return GDN_ERR_UNSUPPORTED;
-    if (dtypes && (C % 8) == 0 && (ldy % 8) == 0 && (ld_out % 8) == 0 && (!residual || (ld_res % 8) == 0)) {
-        hipLaunchKernelGGL(bn_apply8_kernel, dim3(stream_blocks(npix * (C / 8))), dim3(256), 0, ST(stream), y, ldy, scale,
-                           shift, residual, ld_res, out, ld_out, npix, C, relu, dtypes, pow2_shift(C / 8));
-        return gdn_launch_status();
-    }
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(stream_blocks(npix * (C / 4))), dim3(256), 0, ST(stream), y, ldy, scale,
-                       shift, residual, ld_res, out, ld_out, npix, C, relu, dtypes, pow2_shift(C / 4));
+    bn_apply_launch(bn_wide(dtypes, C, ldy, ld_out, residual ? ld_res : 0), ST(stream), y, ldy, scale, shift, residual, ld_res,
+                    out, ld_out, npix, C, relu, dtypes);
     return gdn_launch_status();
-}
-
-static int bnb_blocks(int64_t npix) {
-    int64_t b = cdiv64(npix, 64);
-    if (b < 1) b = 1;
-    return (int)(b < BNB_MAXBLK ? b : BNB_MAXBLK);
 }
 
 extern "C" size_t gdn_bn_bwd_workspace_bytes(int64_t npix, int32_t C) {
     return ((size_t)bnb_blocks(npix) * 2 * C + 2 * (size_t)C) * sizeof(float);
 }
 
+// Pass 1 runs on 4-channel lanes for bf16 tensors too: the order of its sums, and with it dgamma / dbeta to the bit, depends
+// on the lane width.  Widening it is a speed change of its own.
 extern "C" int gdn_bn_bwd(const void* dout, int32_t ld_dout, const void* y, int32_t ldy, const float* gamma,
                           const float* scale, const float* shift, const float* mean, const float* invstd, void* dy,
                           int32_t ld_dy, float* dgamma, float* dbeta, int64_t npix, int32_t C, int32_t relu,
@@ -608,22 +637,14 @@ extern "C" int gdn_bn_bwd(const void* dout, int32_t ld_dout, const void* y, int3
     float* k2 = k1 + C;
     if (ext_partial) {
         // pass 1 already happened in the epilogue of the kernel that produced dout (gdn_winoconv_bwd / gdn_fftconv_bwd)
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, ST(stream), ext_partial, (int)ext_slots, C,
-                           (double)npix, dgamma, dbeta, k1, k2);
+        bn_bwd_finalize_launch(ST(stream), ext_partial, (int)ext_slots, C, npix, dgamma, dbeta, k1, k2);
     } else {
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, ST(stream), dout, ld_dout, y, ldy, scale, shift,
-                           mean, invstd, partial, npix, C, relu, dtypes);
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, ST(stream), (const float*)partial, nblk, C,
-                           (double)npix, dgamma, dbeta, k1, k2);
+        bn_bwd_sums_launch(false, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, nullptr, 0, partial, npix,
+                           C, relu, dtypes);
+        bn_bwd_finalize_launch(ST(stream), partial, nblk, C, npix, dgamma, dbeta, k1, k2);
     }
-    if (dtypes && (C % 8) == 0 && (ldy % 8) == 0 && (ld_dout % 8) == 0 && (ld_dy % 8) == 0)
-        hipLaunchKernelGGL(bn_bwd_apply8_kernel, dim3(stream_blocks(npix * (C / 8))), dim3(256), 0, ST(stream), dout,
-                           ld_dout, y, ldy, scale, shift, mean, invstd, (const float*)k1, (const float*)k2, dy, ld_dy,
-                           npix, C, relu, dtypes, pow2_shift(C / 8));
-    else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_blocks(npix * (C / 4))), dim3(256), 0, ST(stream), dout,
-                       ld_dout, y, ldy, scale, shift, mean, invstd, (const float*)k1, (const float*)k2, dy, ld_dy, npix,
-                       C, relu, dtypes, pow2_shift(C / 4));
+    bn_bwd_apply_launch(bn_wide(dtypes, C, ldy, ld_dout, ld_dy), ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd,
+                        k1, k2, dy, ld_dy, npix, C, relu, dtypes);
     return gdn_launch_status();
 }
 
@@ -637,8 +658,7 @@ extern "C" int gdn_bn_bwd_coeffs(const void* dout, int32_t ld_dout, const void* 
     if (!scale || !shift || !mean || !invstd || !kk || npix <= 0 || C <= 0) return GDN_ERR_BAD_ARG;
     if (ext_partial && (ext_slots <= 0 || ext_slots > 0x7fffffff)) return GDN_ERR_BAD_ARG;
     if (ext_partial) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, ST(stream), ext_partial, (int)ext_slots, C,
-                           (double)npix, dgamma, dbeta, kk, kk + C);
+        bn_bwd_finalize_launch(ST(stream), ext_partial, (int)ext_slots, C, npix, dgamma, dbeta, kk, kk + C);
         return gdn_launch_status();
     }
     if (!dout || !y) return GDN_ERR_BAD_ARG;
@@ -646,198 +666,28 @@ extern "C" int gdn_bn_bwd_coeffs(const void* dout, int32_t ld_dout, const void* 
     if (!workspace || workspace_bytes < gdn_bn_bwd_workspace_bytes(npix, C)) return GDN_ERR_WORKSPACE;
     const int nblk = bnb_blocks(npix);
     float* partial = (float*)workspace;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, ST(stream), dout, ld_dout, y, ldy, scale, shift,
-                       mean, invstd, partial, npix, C, relu, dtypes);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, ST(stream), (const float*)partial, nblk, C,
-                       (double)npix, dgamma, dbeta, kk, kk + C);
+    bn_bwd_sums_launch(false, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, nullptr, 0, partial, npix, C,
+                       relu, dtypes);
+    bn_bwd_finalize_launch(ST(stream), partial, nblk, C, npix, dgamma, dbeta, kk, kk + C);
     return gdn_launch_status();
 }
 
-// Backward of out = [relu](y*scale + shift) with FIXED per-channel coefficients (eval-mode BatchNorm of a frozen
-// network): dy = scale * dout * [z > 0].  No reductions, no parameter gradients.
-__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const void* __restrict__ dout, int ld_dout,
-                                                          const void* __restrict__ y, int ldy,
-                                                          const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, void* __restrict__ dy,
-                                                          int ld_dy, int64_t npix, int C, int relu, int dt, int sh) {
-    const int cq = C >> 2;
-    const int64_t total = npix * cq;
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        SPLIT_PIX_C(i, cq, sh, pix, c);
-        const f32x4 d = ld4_any(dout, pix * ld_dout + c, dt & 1);
-        const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c);
-        f32x4 o = d * s;
-        if (relu) {
-            const f32x4 v = ld4_any(y, pix * ldy + c, dt & 2);
-            const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // relu == 2: y already IS the activated output (conv + BN + ReLU fused in the conv epilogue)
-                const bool on = relu == 2 ? v[e] > 0.f : v[e] * s[e] + t[e] > 0.f;
-                if (!on) o[e] = 0.f;
-            }
-        }
-        st4_any(dy, pix * ld_dy + c, o, dt & 4);
-    }
-}
-
+// 4-channel lanes for every dtype, as it always ran; widening it for bf16 is a speed change of its own.
 extern "C" int gdn_bn_eval_bwd(const void* dout, int32_t ld_dout, const void* y, int32_t ldy, const float* scale,
                                const float* shift, void* dy, int32_t ld_dy, int64_t npix, int32_t C, int32_t relu,
                                int32_t dtypes, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other HIP users of this thread
     if (!dout || !y || !scale || !shift || !dy || npix <= 0 || C <= 0) return GDN_ERR_BAD_ARG;
     if ((C % 4) || (ldy % 4) || (ld_dout % 4) || (ld_dy % 4)) return GDN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(stream_blocks(npix * (C / 4))), dim3(256), 0, ST(stream), dout, ld_dout,
-                       y, ldy, scale, shift, dy, ld_dy, npix, C, relu, dtypes, pow2_shift(C / 4));
+    bn_eval_bwd_launch(false, ST(stream), dout, ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu, dtypes);
     return gdn_launch_status();
 }
 
 // ------------------------------------------------ BN backward on FROZEN statistics
 // A trained layer whose BatchNorm stays in eval(): out = [relu](y*scale + shift) with scale / shift from the RUNNING statistics.
-// dy = scale * dout * [z > 0] depends on no reduction, so one pass reads dout and y once, writes dy and leaves the per-block
-// sums of dz and dz*xhat (xhat = (y - running_mean) * invstd) that bn_bwd_finalize_kernel turns into dbeta / dgamma.
-__global__ void bn_frozen_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                        int C, float* scale, float* shift, float* mean, float* invstd) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    // (scale / shift: bn_eval_coeffs_kernel's expressions, letter for letter -- the two must agree to the bit)
-    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    const float inv = 1.0f / sqrtf(rv[c] + eps);
-    scale[c] = g * inv;
-    shift[c] = b - rm[c] * g * inv;
-    mean[c] = rm[c];
-    invstd[c] = inv;
-}
-
-#define BNF_MAXBLK 2048
-// bn_bwd_reduce_kernel's block layout -- channel-vector lanes x pixel lanes over one contiguous pixel range per block, the same
-// 8 KB of LDS -- with the dy store added.  NH: 4-channel halves per lane (1: 16 bytes of fp32; 2: 16 bytes of bf16).
-// partial[blk][2][C]: a lane sums its pixels in order, lane 0 of each channel vector adds the pixel lanes in order -- a fixed
-// order, no atomics.  DY: dy is written, with bn_eval_bwd_kernel's arithmetic.
-template <int NH, bool DY>
-__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(
-    const void* __restrict__ dout, int ld_dout, const void* __restrict__ y, int ldy,
-    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-    const float* __restrict__ invstd, void* __restrict__ dy, int ld_dy, float* __restrict__ partial, int64_t npix, int C,
-    int relu, int dt) {
-    __shared__ float sh[256 * 8];
-    const int cv = C / (4 * NH);
-    const int CQ = cv < 256 ? cv : 256;      // channel-vector lanes
-    const int PY = 256 / CQ;                 // pixel lanes
-    const int tx = threadIdx.x % CQ, ty = threadIdx.x / CQ;
-    const int64_t per = cdiv64(npix, gridDim.x);
-    const int64_t p0 = blockIdx.x * per, p1 = (p0 + per < npix) ? p0 + per : npix;
-    for (int q0 = 0; q0 < cv; q0 += CQ) {    // (uniform trip count: the barriers below are reached by every lane)
-        const int q = q0 + tx;
-        const bool lane = ty < PY && q < cv;
-        const int c = q * 4 * NH;
-        f32x4 a1[NH], a2[NH];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) { a1[h] = f32x4{0.f, 0.f, 0.f, 0.f}; a2[h] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        if (lane) {
-            f32x4 s[NH], t[NH], mu[NH], is[NH];
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                s[h] = *reinterpret_cast<const f32x4*>(scale + c + 4 * h);
-                t[h] = *reinterpret_cast<const f32x4*>(shift + c + 4 * h);
-                mu[h] = *reinterpret_cast<const f32x4*>(mean + c + 4 * h);
-                is[h] = *reinterpret_cast<const f32x4*>(invstd + c + 4 * h);
-            }
-            for (int64_t pix = p0 + ty; pix < p1; pix += PY) {
-                f32x4 d[NH], v[NH], o[NH];
-                if (NH == 2) ld8_any(dout, pix * ld_dout + c, dt & 1, d[0], d[NH - 1]);
-                else d[0] = ld4_any(dout, pix * ld_dout + c, dt & 1);
-                if (NH == 2) ld8_any(y, pix * ldy + c, dt & 2, v[0], v[NH - 1]);
-                else v[0] = ld4_any(y, pix * ldy + c, dt & 2);
-#pragma unroll
-                for (int h = 0; h < NH; ++h) {
-                    o[h] = d[h] * s[h];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float dz = d[h][e];
-                        if (relu) {
-                            const bool on = v[h][e] * s[h][e] + t[h][e] > 0.f;
-                            if (!on) { o[h][e] = 0.f; dz = 0.f; }
-                        }
-                        a1[h][e] += dz;
-                        a2[h][e] += dz * ((v[h][e] - mu[h][e]) * is[h][e]);
-                    }
-                }
-                if (DY) {
-                    if (NH == 2) st8_any(dy, pix * ld_dy + c, o[0], o[NH - 1], dt & 4);
-                    else st4_any(dy, pix * ld_dy + c, o[0], dt & 4);
-                }
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { sh[threadIdx.x * 8 + e] = a1[h][e]; sh[threadIdx.x * 8 + 4 + e] = a2[h][e]; }
-            __syncthreads();
-            if (ty == 0 && q < cv) {
-                f32x4 r1 = {0.f, 0.f, 0.f, 0.f}, r2 = {0.f, 0.f, 0.f, 0.f};
-                for (int j = 0; j < PY; ++j) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { r1[e] += sh[(j * CQ + tx) * 8 + e]; r2[e] += sh[(j * CQ + tx) * 8 + 4 + e]; }
-                }
-                *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * C + c + 4 * h) = r1;
-                *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * C + c + 4 * h) = r2;
-            }
-        }
-    }
-}
-
-// The dy pass alone (the sums came from the producer of dout): nothing is reduced, so it is the flat grid-stride stream of
-// bn_eval_bwd_kernel -- that kernel itself for 4-channel lanes, this one for the 16-byte bf16 lanes; the same arithmetic.
-__global__ __launch_bounds__(256) void bn_frozen_apply8_kernel(const void* __restrict__ dout, int ld_dout,
-                                                               const void* __restrict__ y, int ldy,
-                                                               const float* __restrict__ scale,
-                                                               const float* __restrict__ shift, void* __restrict__ dy,
-                                                               int ld_dy, int64_t npix, int C, int relu, int dt, int sh) {
-    const int co = C >> 3;
-    const int64_t total = npix * co;
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t pix = sh >= 0 ? (i >> sh) : i / co;
-        const int c = (int)(sh >= 0 ? (i & (co - 1)) : (i - pix * co)) * 8;
-        f32x4 d[2], v[2], o[2];
-        ld8_any(dout, pix * ld_dout + c, dt & 1, d[0], d[1]);
-        if (relu) ld8_any(y, pix * ldy + c, dt & 2, v[0], v[1]);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const f32x4 s = *reinterpret_cast<const f32x4*>(scale + c + 4 * h);
-            o[h] = d[h] * s;
-            if (relu) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(shift + c + 4 * h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const bool on = v[h][e] * s[e] + t[e] > 0.f;
-                    if (!on) o[h][e] = 0.f;
-                }
-            }
-        }
-        st8_any(dy, pix * ld_dy + c, o[0], o[1], dt & 4);
-    }
-}
-
-static int bnf_blocks(int64_t npix) {
-    int64_t b = cdiv64(npix, 64);
-    if (b < 1) b = 1;
-    return (int)(b < BNF_MAXBLK ? b : BNF_MAXBLK);
-}
-
-template <int NH>
-static void bnf_launch(bool wdy, int nblk, hipStream_t st, const void* dout, int ld_dout, const void* y, int ldy,
-                       const float* scale, const float* shift, const float* mean, const float* invstd, void* dy, int ld_dy,
-                       float* partial, int64_t npix, int C, int relu, int dt) {
-#define BNF_GO(D)                                                                                                      \
-    hipLaunchKernelGGL((bn_frozen_bwd_kernel<NH, D>), dim3(nblk), dim3(256), 0, st, dout, ld_dout, y, ldy, scale, shift, \
-                       mean, invstd, dy, ld_dy, partial, npix, C, relu, dt)
-    if (wdy) BNF_GO(true);
-    else BNF_GO(false);
-#undef BNF_GO
-}
-
+// dy = scale * dout * [z > 0] depends on no reduction, so one pass (bn_bwd_sums_kernel<NH, true>) reads dout and y once, writes
+// dy and leaves the per-block sums of dz and dz*xhat (xhat = (y - running_mean) * invstd) that bn_bwd_finalize_kernel turns
+// into dbeta / dgamma.  Where the sums came from the producer of dout, the dy pass alone is bn_eval_bwd_kernel.
 extern "C" int gdn_bn_frozen_coeffs(const float* gamma, const float* beta, const float* running_mean,
                                     const float* running_var, float eps, int32_t C, float* scale, float* shift,
                                     float* mean, float* invstd, void* stream) {
@@ -869,26 +719,15 @@ extern "C" int gdn_bn_frozen_bwd(const void* dout, int32_t ld_dout, const void* 
     float* partial = (float*)workspace;
     float* k1 = partial + (size_t)nblk * 2 * C;
     float* k2 = k1 + C;
-    const bool wide = dtypes && (C % 8) == 0 && (ldy % 8) == 0 && (ld_dout % 8) == 0 && (!dy || (ld_dy % 8) == 0);
-    if (dy && !sums) {
-        if (wide)
-            hipLaunchKernelGGL(bn_frozen_apply8_kernel, dim3(stream_blocks(npix * (C / 8))), dim3(256), 0, ST(stream), dout,
-                               ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu ? 1 : 0, dtypes, pow2_shift(C / 8));
-        else
-            hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(stream_blocks(npix * (C / 4))), dim3(256), 0, ST(stream), dout,
-                               ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu ? 1 : 0, dtypes, pow2_shift(C / 4));
-    } else if (sums) {
-        if (wide)
-            bnf_launch<2>(dy != nullptr, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, dy, ld_dy,
-                          partial, npix, C, relu ? 1 : 0, dtypes);
-        else
-            bnf_launch<1>(dy != nullptr, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, dy, ld_dy,
-                          partial, npix, C, relu ? 1 : 0, dtypes);
-    }
+    const bool wide = bn_wide(dtypes, C, ldy, ld_dout, dy ? ld_dy : 0);
+    if (sums)
+        bn_bwd_sums_launch(wide, nblk, ST(stream), dout, ld_dout, y, ldy, scale, shift, mean, invstd, dy, ld_dy, partial, npix, C,
+                           relu ? 1 : 0, dtypes);
+    else if (dy)
+        bn_eval_bwd_launch(wide, ST(stream), dout, ld_dout, y, ldy, scale, shift, dy, ld_dy, npix, C, relu ? 1 : 0, dtypes);
     if (want_sums)
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, ST(stream),
-                           ext_partial ? ext_partial : (const float*)partial, ext_partial ? (int)ext_slots : nblk, C,
-                           (double)npix, dgamma, dbeta, k1, k2);
+        bn_bwd_finalize_launch(ST(stream), ext_partial ? ext_partial : partial, ext_partial ? (int)ext_slots : nblk, C, npix,
+                               dgamma, dbeta, k1, k2);
     return gdn_launch_status();
 }
 

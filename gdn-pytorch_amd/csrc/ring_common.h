@@ -334,10 +334,9 @@ __device__ __forceinline__ void ring_epilogue(const IgemmParams& p, const int* t
                         const f32x4 cis = *reinterpret_cast<const f32x4*>(coef + 3 * BN + cg * 8 + hh * 4);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float dz = bf16_h_to_f32(f32_to_bf16_h(dv[e]));
-                            if (p.bnb_relu && !(yv[e] * csc[e] + csh[e] > 0.f)) dz = 0.f;
+                            const float dz = bn_dz(bf16_h_to_f32(f32_to_bf16_h(dv[e])), yv[e], csc[e], csh[e], p.bnb_relu);
                             bs1[hh * 4 + e] += dz;
-                            bs2[hh * 4 + e] += dz * ((yv[e] - cmu[e]) * cis[e]);
+                            bs2[hh * 4 + e] += dz * bn_xhat(yv[e], cmu[e], cis[e]);
                         }
                     }
                 }

@@ -11,8 +11,8 @@ A step is forward, DtoD loss, backward and the fused Adam update.  Also printed:
 The flag-off loop against another build (the parent commit): run this script in both trees with --only batch-stat and compare
 the medians with the rounds' spread.  The BatchNorm share of a step from a kernel breakdown:
     rocprofv3 --kernel-trace --stats -d OUT -- python tests/diag/freeze_bn_time.py 20 1 --dtype fp32 --only frozen
-and sum the bn_* kernels of OUT's kernel statistics (bn_frozen_bwd_kernel, bn_bwd_finalize_kernel, bn_apply*; for the other
-form bn_bwd_reduce / _apply, bn_finalize_train).
+and sum the bn_* kernels of OUT's kernel statistics (bn_bwd_sums_kernel<NH, true>, bn_bwd_finalize_kernel, bn_apply*; for the
+other form bn_bwd_sums_kernel<1, false>, bn_bwd_apply_kernel<NH>, bn_finalize_train).
 
 usage: freeze_bn_time.py [steps per window = 30] [rounds = 3] [--dtype fp32|bf16|both] [--only batch-stat|frozen] [--batch 20]
                          [--out FILE]"""

@@ -215,6 +215,25 @@ def test_frozen_bwd_more_pixels_than_one_sweep(gpu):
     _frozen_case(gpu, C, (1, 1, npix), (0, 0, 0), True, None, None, None, 8900, "bn_frozen_bwd C4 600007px")
 
 
+@pytest.mark.parametrize("C,dtypes", [(1040, "f32"), (1040, "bf16"), (2080, "bf16")])
+def test_frozen_bwd_more_channel_vectors_than_lanes(gpu, C, dtypes):
+    """More channel vectors than the 256 channel lanes of a block: 260 quads (C = 1040, fp32) and 260 eight-channel vectors
+    (C = 2080, bf16) make the channel loop run twice with 4 lanes busy in the second trip, and every lane must still reach the
+    barriers of the LDS sum; C = 1040 in bf16 is 130 vectors, one trip with idle lanes.  With dy and without (the sums only):
+    the same dgamma / dbeta, bit for bit."""
+    from gdn_amd import ops
+    shape = (3, 7, 5)
+    dts = BWD_DTYPES[dtypes]
+    assert C // (8 if any(dts) else 4) in (130, 260)
+    for relu in (False, True):
+        what = "bn_frozen_bwd C%d %s %s relu%d" % (C, "x".join(map(str, shape)), dtypes, relu)
+        dv, yv, co, dy, dg, db = _frozen_case(gpu, C, shape, dts, relu, None, None, None, 8960 + relu, what)
+        dg2, db2 = (torch.full((C,), float("nan"), device=gpu) for _ in range(2))
+        assert ops.bn_frozen_bwd(dv, yv, co, relu, dg2, db2, need_dy=False) is None
+        _same_bits(dg2, dg, what + " sums-only dgamma")
+        _same_bits(db2, db, what + " sums-only dbeta")
+
+
 @pytest.mark.parametrize("dtypes", ["f32", "bf16"])
 @pytest.mark.parametrize("C", [12, 64])
 def test_frozen_bwd_dyadic_relu_ties(gpu, C, dtypes):

@@ -635,7 +635,7 @@ def test_rtod_train_step_b20_vs_oracle(gpu):
 def test_train_bn_fusion_matches_unfused(gpu, monkeypatch):
     """Row N1 (north_star 'conv+BN+ReLU fused'): with the train-mode fusion on -- relu(bn1(conv1 x)) applied in conv2's
     patch loader, BatchNorm-backward reductions emitted by the data-gradient epilogues -- the step must equal the unfused
-    step (engine._FUSE_TRAIN_BN False: bn_apply + bn_bwd_reduce passes) up to summation order, for both trained networks."""
+    step (engine._FUSE_TRAIN_BN False: bn_apply + bn_bwd_sums passes) up to summation order, for both trained networks."""
     import gdn_amd.AE_model_unet as M
     from gdn_amd import engine as E
     from gdn_amd import utils as U

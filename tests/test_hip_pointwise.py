@@ -5,7 +5,8 @@ operation plus at most one round-to-nearest-even store).
     entry point                   test
     ----------------------------  ------------------------------------------------------------------------
     gdn_bn_apply                  test_bn_apply, test_bn_dyadic_relu_ties, test_bn_training_shapes
-    gdn_bn_bwd                    test_bn_bwd, test_bn_bwd_external_partial, test_bn_dyadic_relu_ties, test_bn_training_shapes
+    gdn_bn_bwd                    test_bn_bwd, test_bn_bwd_external_partial, test_bn_dyadic_relu_ties, test_bn_training_shapes,
+                                  test_bn_bwd_more_channel_vectors_than_lanes
     gdn_bn_bwd_coeffs             test_bn_bwd (k1, k2), test_bn_bwd_external_partial
     gdn_bn_eval_bwd               test_bn_eval_bwd (relu 0 / 1 / 2), test_bn_dyadic_relu_ties
     gdn_bn_finalize_train         supplies the coefficients of all of the above from fp32 partial sums
@@ -290,6 +291,19 @@ def test_bn_bwd(gpu, C, dtypes):
                 _check_vec(kk[1], b["k2"], (e2 + 2 * EPS * np.abs(b["dgamma"])) / n, what + " k2")
                 _check_vec(db.cpu(), b["dbeta"], e1 + EPS * np.abs(b["dbeta"]), what + " coeffs dbeta")
                 _check_vec(dg.cpu(), b["dgamma"], e2 + EPS * np.abs(b["dgamma"]), what + " coeffs dgamma")
+
+
+@pytest.mark.parametrize("dtypes", ["f32", "bf16"])
+def test_bn_bwd_more_channel_vectors_than_lanes(gpu, dtypes):
+    """C = 1040: 260 channel quads for the 256 channel lanes of a pass-1 block (4-channel lanes for bf16 too), so the kernel's
+    channel loop runs twice and only 4 lanes have a quad in the second trip; every lane must still reach the barriers of the
+    LDS sum.  One pixel lane per channel lane, 105 pixels in two blocks.  Pass 3 splits its flat index by 260 quads (fp32)
+    or 130 eight-channel vectors (bf16), neither a power of two."""
+    C, shape = 1040, (3, 7, 5)
+    assert C // 4 > 256 and (C // 4) % 256 == 4
+    for relu in (False, True):
+        what = "bn_bwd C%d %s %s relu%d" % (C, "x".join(map(str, shape)), dtypes, relu)
+        _bwd_case(gpu, C, shape, BWD_DTYPES[dtypes], relu, None, None, 2900 + relu, what)
 
 
 @pytest.mark.parametrize("slots", [1, 37, 1500])
