@@ -748,28 +748,7 @@ __global__ __launch_bounds__(256) void ifft_rows_overlap_kernel(const float2* __
 __global__ __launch_bounds__(256) void fft_reflect_fold_kernel(const float* __restrict__ dxp, float* __restrict__ dx, int ldx,
                                                                const float* __restrict__ addsrc, int ld_add,
                                                                int B, int H, int W, int C, int p) {
-    const int Hp = H + 2 * p, Wp = W + 2 * p, c4n = C / 4;
-    const int64_t total = (int64_t)B * H * W * c4n;
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c4 = (int)(i % c4n);
-        int64_t t = i / c4n;
-        const int x = (int)(t % W); t /= W;
-        const int y = (int)(t % H), b = (int)(t / H);
-        int qy[3], qx[3], ny = 0, nx = 0;
-        qy[ny++] = y + p;
-        if (y >= 1 && y <= p) qy[ny++] = p - y;
-        if (y <= H - 2 && y >= H - 1 - p) qy[ny++] = 2 * (H - 1) - y + p;
-        qx[nx++] = x + p;
-        if (x >= 1 && x <= p) qx[nx++] = p - x;
-        if (x <= W - 2 && x >= W - 1 - p) qx[nx++] = 2 * (W - 1) - x + p;
-        f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
-        for (int a = 0; a < ny; ++a)
-            for (int e = 0; e < nx; ++e)
-                s4 += *reinterpret_cast<const f32x4*>(dxp + ((size_t)(b * Hp + qy[a]) * Wp + qx[e]) * C + c4 * 4);
-        const size_t op = (size_t)(b * H + y) * W + x;
-        if (addsrc) s4 += *reinterpret_cast<const f32x4*>(addsrc + op * ld_add + c4 * 4);
-        *reinterpret_cast<f32x4*>(dx + op * ldx + c4 * 4) = s4;
-    }
+    reflect_fold_f32x4(dxp, dx, ldx, addsrc, ld_add, B, H, W, C, p);
 }
 
 // ---- single-pass 2-D transforms: one workgroup = one tile x 16 channels, rows and columns meet in LDS (68 KB) ----
@@ -1413,7 +1392,6 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
     float2* Ef = (float2*)p; p += al256((size_t)f.M * f.bins * f.C * 8);
     float* Wf = (float*)p; p += wf_region_bytes(f);   // weight-gradient products P (per split), or the weight spectrum when the forward saved none
     float* dxp = (float*)p;          // reflection layers: gradient over the padded domain
-    auto blocks = [](int64_t n) { const int64_t b = cdiv64(n, 256); return (unsigned)(b < 65536 * 8 ? b : 65536 * 8); };
     if (phases & GDN_FFT_BWD_TRANSFORM) {
         // spectrum of the dy tiles (no halo: rows / columns >= T are the zero padding of the linear convolution)
         FftGeom fd = f;
@@ -1441,7 +1419,7 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
             GDN_TAPS(3) GDN_TAPS(5) GDN_TAPS(7) GDN_TAPS(9)
         }
         const int64_t n4 = (int64_t)f.k * f.k * f.N * f.C / 4;
-        hipLaunchKernelGGL(fft_taps_reduce_kernel, dim3(blocks(n4)), dim3(256), 0, st, (const float*)part, dw, n4, taps_groups(f),
+        hipLaunchKernelGGL(fft_taps_reduce_kernel, dim3(stream_blocks(n4, 256, 65536 * 8)), dim3(256), 0, st, (const float*)part, dw, n4, taps_groups(f),
                            1.0f / (f.np * f.np), f.flip ? f.k * f.k : 0, (int64_t)f.N * f.C / 4);
 #undef GDN_TAPS
     }
@@ -1499,10 +1477,10 @@ extern "C" int gdn_fftconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t 
         }
         if (f.reflect && dx_up2x)
             // dx is the gradient of the LOW-resolution tensor the forward upsampled on load: fold + adjoint interpolation
-            hipLaunchKernelGGL(reflect_fold_up2x_kernel, dim3(blocks((int64_t)f.B * (f.H / 2) * (f.W / 2) * (f.C / 4))), dim3(256), 0,
+            hipLaunchKernelGGL(reflect_fold_up2x_kernel, dim3(fold_blocks((int64_t)f.B * (f.H / 2) * (f.W / 2) * (f.C / 4))), dim3(256), 0,
                                st, (const void*)dxp, (void*)dx, ldx, (const void*)addsrc, ld_add, f.B, f.H, f.W, f.C, f.pad, dx_up2x - 1, 0);
         else if (f.reflect)
-            hipLaunchKernelGGL(fft_reflect_fold_kernel, dim3(blocks((int64_t)f.B * f.H * f.W * (f.C / 4))), dim3(256), 0, st,
+            hipLaunchKernelGGL(fft_reflect_fold_kernel, dim3(fold_blocks((int64_t)f.B * f.H * f.W * (f.C / 4))), dim3(256), 0, st,
                                (const float*)dxp, dx, ldx, addsrc, ld_add, f.B, f.H, f.W, f.C, f.pad);
     }
     return gdn_launch_status();

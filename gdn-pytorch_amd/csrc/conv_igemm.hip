@@ -1321,7 +1321,7 @@ bool geom_ok(const gdn_conv_geom* g) {
 __global__ void reflect_fold_kernel(const void* __restrict__ dxp, void* __restrict__ dx,
                                     const void* __restrict__ addsrc, int ld_add, int ldx,
                                     int B, int H, int W, int C, int p, int bf16) {
-    // dx[y][x] = sum of dxp over the padded coordinates that reflect onto (y, x).
+    // dx[y][x] = sum of dxp over the padded coordinates that reflect onto (y, x) (reflect_fold.h).
     const int Hp = H + 2 * p, Wp = W + 2 * p;
     const int c4n = C / 4;
     const int64_t total = (int64_t)B * H * W * c4n;
@@ -1331,13 +1331,8 @@ __global__ void reflect_fold_kernel(const void* __restrict__ dxp, void* __restri
         const int x = (int)(t % W); t /= W;
         const int y = (int)(t % H);
         const int b = (int)(t / H);
-        int qy[3], qx[3], ny = 0, nx = 0;
-        qy[ny++] = y + p;
-        if (y >= 1 && y <= p) qy[ny++] = p - y;
-        if (y <= H - 2 && y >= H - 1 - p) qy[ny++] = 2 * (H - 1) - y + p;
-        qx[nx++] = x + p;
-        if (x >= 1 && x <= p) qx[nx++] = p - x;
-        if (x <= W - 2 && x >= W - 1 - p) qx[nx++] = 2 * (W - 1) - x + p;
+        int qy[3], qx[3];
+        const int ny = reflect_sources(y, H, p, qy), nx = reflect_sources(x, W, p, qx);
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
         for (int a = 0; a < ny; ++a)
             for (int e = 0; e < nx; ++e)
@@ -1360,13 +1355,8 @@ __global__ void reflect_fold_scalar_kernel(const float* __restrict__ dxp, float*
         const int x = (int)(t % W); t /= W;
         const int y = (int)(t % H);
         const int b = (int)(t / H);
-        int qy[3], qx[3], ny = 0, nx = 0;
-        qy[ny++] = y + p;
-        if (y >= 1 && y <= p) qy[ny++] = p - y;
-        if (y <= H - 2 && y >= H - 1 - p) qy[ny++] = 2 * (H - 1) - y + p;
-        qx[nx++] = x + p;
-        if (x >= 1 && x <= p) qx[nx++] = p - x;
-        if (x <= W - 2 && x >= W - 1 - p) qx[nx++] = 2 * (W - 1) - x + p;
+        int qy[3], qx[3];
+        const int ny = reflect_sources(y, H, p, qy), nx = reflect_sources(x, W, p, qx);
         float s = 0.f;
         for (int a = 0; a < ny; ++a)
             for (int e = 0; e < nx; ++e) s += dxp[((size_t)(b * Hp + qy[a]) * Wp + qx[e]) * C + c];
@@ -1594,23 +1584,18 @@ extern "C" int gdn_conv_dgrad(const gdn_conv_geom* g, const void* dyv, int32_t l
     int rc = launch_igemm(P, cfg, st, ksplit, (ksplit > 1 || rb) ? (char*)workspace + fb : nullptr);
     if (rc != GDN_OK) return rc;
     if (fold && (g->Cin % 4)) {
-        const int64_t total = (int64_t)g->B * g->H * g->W * g->Cin;
-        const int blocks = (int)(cdiv64(total, 256) < 4096 ? cdiv64(total, 256) : 4096);
-        hipLaunchKernelGGL(reflect_fold_scalar_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, dx, addsrc,
-                           ld_add, ldx, g->B, g->H, g->W, g->Cin, g->pad);
+        hipLaunchKernelGGL(reflect_fold_scalar_kernel, dim3(fold_blocks((int64_t)g->B * g->H * g->W * g->Cin, 4096)), dim3(256), 0, st,
+                           (const float*)workspace, dx, addsrc, ld_add, ldx, g->B, g->H, g->W, g->Cin, g->pad);
         rc = gdn_launch_status();
     } else if (fold && dx_up2x) {
         const bool w8 = (g->Cin % 8) == 0 && (ldx % 8) == 0 && (!addsrc || (ld_add % 8) == 0);
-        const int64_t nb = cdiv64((int64_t)g->B * (g->H / 2) * (g->W / 2) * (g->Cin / (w8 ? 8 : 4)), 256);
-        hipLaunchKernelGGL(w8 ? reflect_fold_up2x8_kernel : reflect_fold_up2x_kernel, dim3((unsigned)(nb < 65536 * 8 ? nb : 65536 * 8)),
-                           dim3(256), 0, st, (const void*)workspace, (void*)dx, ldx, (const void*)addsrc, ld_add, g->B, g->H, g->W,
+        hipLaunchKernelGGL(w8 ? reflect_fold_up2x8_kernel : reflect_fold_up2x_kernel,
+                           dim3(fold_blocks((int64_t)g->B * (g->H / 2) * (g->W / 2) * (g->Cin / (w8 ? 8 : 4)))), dim3(256), 0, st, (const void*)workspace, (void*)dx, ldx, (const void*)addsrc, ld_add, g->B, g->H, g->W,
                            g->Cin, g->pad, dx_up2x - 1, P.bf16);
         rc = gdn_launch_status();
     } else if (fold) {
-        const int64_t total = (int64_t)g->B * g->H * g->W * (g->Cin / 4);
-        const int blocks = (int)(cdiv64(total, 256) < 4096 ? cdiv64(total, 256) : 4096);
-        hipLaunchKernelGGL(reflect_fold_kernel, dim3(blocks), dim3(256), 0, st, (const void*)workspace, (void*)dx,
-                           (const void*)addsrc, ld_add, ldx, g->B, g->H, g->W, g->Cin, g->pad, P.bf16);
+        hipLaunchKernelGGL(reflect_fold_kernel, dim3(fold_blocks((int64_t)g->B * g->H * g->W * (g->Cin / 4), 4096)), dim3(256), 0, st,
+                           (const void*)workspace, (void*)dx, (const void*)addsrc, ld_add, ldx, g->B, g->H, g->W, g->Cin, g->pad, P.bf16);
         rc = gdn_launch_status();
     }
     return rc;

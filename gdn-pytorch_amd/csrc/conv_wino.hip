@@ -251,17 +251,23 @@ __global__ __launch_bounds__(256) void wino_weights_x3_kernel(const float* __res
         }
 }
 
-// y = A^T m A (2x2 outputs per tile) with the conv_igemm epilogue; stats slot = group of 4 tiles
+// epilogue of the two output kernels: the conv_igemm one (residual, BatchNorm partials, affine / activation) and, for a data
+// gradient, the BatchNorm-backward partials
 // bnb_y != NULL (data gradient): y is the gradient of a train-mode BatchNorm's output z = [relu](BN(bnb_y)); `stats` then
 // receives that layer's backward partials (sum dz, sum dz*xhat per slot; bnb_co = [scale, shift, mean, invstd][Nout])
 // instead of sum / sum of squares, so the stand-alone reduce pass over (dy, y) disappears.
-__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mo, float* __restrict__ y, int ldy,
-                                                          const float* __restrict__ addsrc, int ld_add,
-                                                          float* __restrict__ stats, const float* __restrict__ ep_scale,
-                                                          const float* __restrict__ ep_shift, int act, WinoGeom g, int Nout,
-                                                          int q_shift, const float* __restrict__ bnb_y, int ld_bnb,
-                                                          const float* __restrict__ bnb_co, int bnb_relu) {
-    __shared__ float red[256 * 2];
+struct WinoEp {
+    const float* addsrc; int ld_add;
+    float* stats;
+    const float* ep_scale; const float* ep_shift;
+    int act;
+    const float* bnb_y; int ld_bnb;
+    const float* bnb_co; int bnb_relu;
+};
+
+// y = A^T m A (2x2 outputs per tile) with the epilogue above; stats slot = group of 4 tiles
+__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mo, float* __restrict__ y, int ldy, WinoEp ep,
+                                                          WinoGeom g, int Nout, int q_shift) {
     int t, n;
     const bool live = wino_decode(g.M, q_shift, t, n);
     float s1 = 0.f, s2 = 0.f;
@@ -277,9 +283,9 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
         float r[2][4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) { r[0][j] = m[0][j] + m[1][j] + m[2][j]; r[1][j] = m[1][j] - m[2][j] - m[3][j]; }
-        const float es = ep_scale ? ep_scale[n] : 1.f, et = ep_shift ? ep_shift[n] : 0.f;
+        const float es = ep.ep_scale ? ep.ep_scale[n] : 1.f, et = ep.ep_shift ? ep.ep_shift[n] : 0.f;
         float bsc = 0.f, bt = 0.f, bmu = 0.f, bis = 0.f;
-        if (bnb_y) { bsc = bnb_co[n]; bt = bnb_co[Nout + n]; bmu = bnb_co[2 * Nout + n]; bis = bnb_co[3 * Nout + n]; }
+        if (ep.bnb_y) { bsc = ep.bnb_co[n]; bt = ep.bnb_co[Nout + n]; bmu = ep.bnb_co[2 * Nout + n]; bis = ep.bnb_co[3 * Nout + n]; }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const float o[2] = {r[i][0] + r[i][1] + r[i][2], r[i][1] - r[i][2] - r[i][3]};
@@ -288,35 +294,23 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
                 const int oy = 2 * a2 + i, ox = 2 * b2 + j;
                 if (oy < g.Ho && ox < g.Wo) {
                     float val = o[j];
-                    if (!bnb_y) { s1 += val; s2 += val * val; }
-                    if (ep_scale) val = val * es + et;
-                    if (act & GDN_ACT_RELU) val = fmaxf(val, 0.f);
+                    if (!ep.bnb_y) { s1 += val; s2 += val * val; }
+                    if (ep.ep_scale) val = val * es + et;
+                    if (ep.act & GDN_ACT_RELU) val = fmaxf(val, 0.f);
                     const size_t px = (size_t)(img * g.Ho + oy) * g.Wo + ox;
-                    if (addsrc) val += addsrc[px * ld_add + n];
-                    if (act & GDN_ACT_TANH) val = tanhf(val);
+                    if (ep.addsrc) val += ep.addsrc[px * ep.ld_add + n];
+                    if (ep.act & GDN_ACT_TANH) val = tanhf(val);
                     y[px * ldy + n] = val;
-                    if (bnb_y) {
-                        const float yv = bnb_y[px * ld_bnb + n];
-                        const float dz = bn_dz(val, yv, bsc, bt, bnb_relu);
+                    if (ep.bnb_y) {
+                        const float yv = ep.bnb_y[px * ep.ld_bnb + n];
+                        const float dz = bn_dz(val, yv, bsc, bt, ep.bnb_relu);
                         s1 += dz; s2 += dz * bn_xhat(yv, bmu, bis);
                     }
                 }
             }
         }
     }
-    if (stats) {
-        red[threadIdx.x * 2] = s1; red[threadIdx.x * 2 + 1] = s2;
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            float a1 = 0.f, a2s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a1 += red[(j * 64 + threadIdx.x) * 2]; a2s += red[(j * 64 + threadIdx.x) * 2 + 1]; }
-            const int slot = blockIdx.x >> q_shift;
-            const int ch = (blockIdx.x & ((1 << q_shift) - 1)) * 64 + threadIdx.x;
-            stats[((size_t)slot * 2 + 0) * Nout + ch] = a1;
-            stats[((size_t)slot * 2 + 1) * Nout + ch] = a2s;
-        }
-    }
+    if (ep.stats) wino_stats_store(s1, s2, ep.stats, q_shift, Nout);
 }
 
 // dW[tap][n][c] = (G^T P G)[ty][tx]
@@ -655,13 +649,8 @@ __global__ __launch_bounds__(256) void wino4_weights_x3_kernel(const float* __re
 // never used) and all of them are in flight together; the 16 outputs are computed, then stored under the tile's 4 + 4 row /
 // column predicates, which are scalar (WINO_UNI).
 template <bool ADD, bool BNB>
-__global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restrict__ Mo, float* __restrict__ y, int ldy,
-                                                           const float* __restrict__ addsrc, int ld_add,
-                                                           float* __restrict__ stats, const float* __restrict__ ep_scale,
-                                                           const float* __restrict__ ep_shift, int act, WinoGeom g, int Nout,
-                                                           int q_shift, const float* __restrict__ bnb_y, int ld_bnb,
-                                                           const float* __restrict__ bnb_co, int bnb_relu) {
-    __shared__ float red[256 * 2];
+__global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restrict__ Mo, float* __restrict__ y, int ldy, WinoEp ep,
+                                                           WinoGeom g, int Nout, int q_shift) {
     int tv, n;
     const bool live = wino_decode(g.M, q_shift, tv, n);
     float s1 = 0.f, s2 = 0.f;
@@ -685,15 +674,15 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const size_t px = rowpx[i] + colpx[j];
-                av[i][j] = ADD ? (addsrc + px * ld_add)[(unsigned)n] : 0.f;
-                yv[i][j] = BNB ? (bnb_y + px * ld_bnb)[(unsigned)n] : 0.f;
+                av[i][j] = ADD ? (ep.addsrc + px * ep.ld_add)[(unsigned)n] : 0.f;
+                yv[i][j] = BNB ? (ep.bnb_y + px * ep.ld_bnb)[(unsigned)n] : 0.f;
             }
         // (no branch around these two loads either -- the join would wait for everything issued above: without an affine they
         // read Mo[n], which exists, and the value is dropped)
-        const float esl = (ep_scale ? ep_scale : Mo)[(unsigned)n], etl = (ep_shift ? ep_shift : Mo)[(unsigned)n];
-        const float es = ep_scale ? esl : 1.f, et = ep_shift ? etl : 0.f;
+        const float esl = (ep.ep_scale ? ep.ep_scale : Mo)[(unsigned)n], etl = (ep.ep_shift ? ep.ep_shift : Mo)[(unsigned)n];
+        const float es = ep.ep_scale ? esl : 1.f, et = ep.ep_shift ? etl : 0.f;
         float bsc = 0.f, bt = 0.f, bmu = 0.f, bis = 0.f;
-        if (BNB) { bsc = bnb_co[n]; bt = bnb_co[Nout + n]; bmu = bnb_co[2 * Nout + n]; bis = bnb_co[3 * Nout + n]; }
+        if (BNB) { bsc = ep.bnb_co[n]; bt = ep.bnb_co[Nout + n]; bmu = ep.bnb_co[2 * Nout + n]; bis = ep.bnb_co[3 * Nout + n]; }
         float r[4][6];                       // A^T along rows, one bin column at a time
         const float* src = Mo + (size_t)t * Nout + n;
         const size_t bs = (size_t)g.M * Nout;
@@ -722,13 +711,13 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
                 const bool ok = row_ok[i] && col_ok[j];
                 float val = o[j];
                 if (!BNB) { s1 = ok ? s1 + val : s1; s2 = ok ? s2 + w4_mul_rn(val, val) : s2; }
-                if (ep_scale) val = val * es + et;
-                if (act & GDN_ACT_RELU) val = fmaxf(val, 0.f);
+                if (ep.ep_scale) val = val * es + et;
+                if (ep.act & GDN_ACT_RELU) val = fmaxf(val, 0.f);
                 if (ADD) val += av[i][j];
-                if (act & GDN_ACT_TANH) val = tanhf(val);
+                if (ep.act & GDN_ACT_TANH) val = tanhf(val);
                 out[i][j] = val;
                 if (BNB) {
-                    const float dz = bn_dz(val, yv[i][j], bsc, bt, bnb_relu);
+                    const float dz = bn_dz(val, yv[i][j], bsc, bt, ep.bnb_relu);
                     s1 = ok ? s1 + dz : s1; s2 = ok ? s2 + w4_mul_rn(dz, bn_xhat(yv[i][j], bmu, bis)) : s2;
                 }
             }
@@ -739,19 +728,7 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
             for (int j = 0; j < 4; ++j)
                 if (row_ok[i] && col_ok[j]) (y + (rowpx[i] + colpx[j]) * ldy)[(unsigned)n] = out[i][j];
     }
-    if (stats) {
-        red[threadIdx.x * 2] = s1; red[threadIdx.x * 2 + 1] = s2;
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            float a1 = 0.f, a2s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a1 += red[(j * 64 + threadIdx.x) * 2]; a2s += red[(j * 64 + threadIdx.x) * 2 + 1]; }
-            const int slot = blockIdx.x >> q_shift;
-            const int ch = (blockIdx.x & ((1 << q_shift) - 1)) * 64 + threadIdx.x;
-            stats[((size_t)slot * 2 + 0) * Nout + ch] = a1;
-            stats[((size_t)slot * 2 + 1) * Nout + ch] = a2s;
-        }
-    }
+    if (ep.stats) wino_stats_store(s1, s2, ep.stats, q_shift, Nout);
 }
 
 // dW[tap][n][c] = (A_w^T P A_w)[ty][tx], the split partial products summed in order
@@ -842,26 +819,154 @@ inline int tn_splits_max(const WinoGeom& f) {
     const int a = wino_tn_splits(f.M, f.N, f.C), b = gemm_x3_tn_ok(f.M, f.N, f.C) ? gemm_x3_tn_splits(f.bins, f.M, f.N, f.C) : 1;
     return a > b ? a : b;
 }
+inline size_t p_bytes(const WinoGeom& f) { return (size_t)tn_splits_max(f) * al256((size_t)f.bins * f.N * f.C * 4); }   // one set per split
+// The NT GEMM Cm[bin] = A[bin] * U[bin]^T of geometry f (M tiles, N outputs, K = C) runs as bf16 x 3 split products where the
+// shape allows, and its weight set is then written as panels.  True for every GEMM of an F(4x4,3x3) plan (wino_geom).  The tile
+// count does not enter, so the padded-domain data gradient of a reflection layer reads the form the forward saved.
+inline bool nt_x3(const WinoGeom& f) { return f.x3 && gemm_x3_ok(f.M, f.N, f.C); }
 
-// F(4x4,3x3) data transforms: the instantiation that holds exactly what the call uses
-inline void launch_wino4_input(const float* x, int ldx, float* V, const WinoGeom& f, const float* in_scale, const float* in_shift,
-                               int in_relu, int up2x, hipStream_t st) {
+// The data gradient of a 3x3 layer is the same kind of convolution of dy with flipped, role-swapped taps: pad 1 onto the H x W
+// input for a zero-padded layer; pad 2 onto the (H+2) x (W+2) padded domain for a reflection-padded one (always F(2x2,3x3)),
+// whose border rows / columns are then folded back onto the rows they mirror.
+inline WinoGeom dgrad_geom(const WinoGeom& f) {
+    WinoGeom fd = f;
+    fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift; fd.reflect = 0;
+    if (f.reflect) {
+        fd.Ho = f.H + 2; fd.Wo = f.W + 2; fd.pad_off = 2;
+        fd.tiles_y = cdiv(fd.Ho, f.T); fd.tiles_x = cdiv(fd.Wo, f.T); fd.M = f.B * fd.tiles_y * fd.tiles_x;
+    }
+    return fd;
+}
+
+// ---- stages: each reads the plan from the geometry and issues the launch that plan calls for ----
+
+// V = B^T d B (f: the geometry whose INPUT is x)
+void wino_input(const WinoGeom& f, const float* x, int ldx, float* V, const float* in_scale, const float* in_shift, int in_relu,
+                int up2x, hipStream_t st) {
     const dim3 grid(cdiv(f.M, 4) << f.cq_shift), blk(256);
-    if (up2x) hipLaunchKernelGGL(wino4_input_up2x_kernel, grid, blk, 0, st, x, ldx, V, f, up2x);
+    if (f.T != 4) hipLaunchKernelGGL(wino_input_kernel, grid, blk, 0, st, x, ldx, V, f, in_scale, in_shift, in_relu, up2x);
+    // F(4x4,3x3): the instantiation that holds exactly what the call uses
+    else if (up2x) hipLaunchKernelGGL(wino4_input_up2x_kernel, grid, blk, 0, st, x, ldx, V, f, up2x);
     else if (in_scale) hipLaunchKernelGGL(wino4_input_kernel<true>, grid, blk, 0, st, x, ldx, V, f, in_scale, in_shift, in_relu);
     else hipLaunchKernelGGL(wino4_input_kernel<false>, grid, blk, 0, st, x, ldx, V, f, in_scale, in_shift, in_relu);
 }
-// (f: the geometry whose tiles are the OUTPUT's; Nout / q_shift: the output's channels)
-inline void launch_wino4_output(const float* Mo, float* y, int ldy, const float* addsrc, int ld_add, float* stats,
-                                const float* ep_scale, const float* ep_shift, int act, const WinoGeom& f, int Nout, int q_shift,
-                                const float* bnb_y, int ld_bnb, const float* bnb_co, int bnb_relu, hipStream_t st) {
-    const dim3 grid(cdiv(f.M, 4) << q_shift), blk(256);
-#define W4_OUT(A, Bn) hipLaunchKernelGGL((wino4_output_kernel<A, Bn>), grid, blk, 0, st, Mo, y, ldy, addsrc, ld_add, stats, ep_scale, \
-                                         ep_shift, act, f, Nout, q_shift, bnb_y, ld_bnb, bnb_co, bnb_relu)
-    if (addsrc) { if (bnb_y) W4_OUT(true, true); else W4_OUT(true, false); }
-    else { if (bnb_y) W4_OUT(false, true); else W4_OUT(false, false); }
+
+// U = G g G^T of the forward layer f: the forward's set into Uf and / or the data gradient's (taps flipped, roles swapped) into
+// Ud, each in the form its GEMM reads (nt_x3).  Both panel sets come from one launch (grid.y = 2).  Of the fp32 sets, the
+// swapped one rides along with the forward's from the same nine reads (Uswap); asked for alone -- a backward without saved
+// state -- it is transformed from the flipped taps directly.
+void wino_weights(const WinoGeom& f, const float* w, float* Uf, float* Ud, hipStream_t st) {
+    const bool pf = Uf && nt_x3(f), pd = Ud && nt_x3(dgrad_geom(f));
+    float* const ff = pf ? nullptr : Uf;
+    float* const fs = pd ? nullptr : Ud;
+    const dim3 blk(256);
+    if (ff || fs) {
+        const dim3 grid(cdiv(f.N * f.C, 256));
+        if (Uf) hipLaunchKernelGGL(wino_weights_kernel, grid, blk, 0, st, w, ff, f.N, f.C, f.flip, fs);
+        else hipLaunchKernelGGL(wino_weights_kernel, grid, blk, 0, st, w, fs, f.N, f.C, 1 | f.flip, (float*)nullptr);
+    }
+    if (pf || pd) {
+        unsigned char* const U0 = (unsigned char*)(pf ? Uf : Ud);
+        unsigned char* const U1 = (unsigned char*)(pf && pd ? Ud : nullptr);
+        const int swap0 = pf ? f.flip : 1 | f.flip, swap1 = U1 ? 1 | f.flip : 0;
+        const dim3 grid(cdiv(f.N * f.C / 8, 256), U1 ? 2 : 1);
+        if (f.T == 4) hipLaunchKernelGGL(wino4_weights_x3_kernel, grid, blk, 0, st, w, U0, f.N, f.C, swap0, U1, swap1);
+        else hipLaunchKernelGGL(wino_weights_x3_kernel, grid, blk, 0, st, w, U0, f.N, f.C, swap0, U1, swap1);
+    }
+}
+
+// Cm[bin] = A[bin] * U[bin]^T (f: M tiles, N outputs, K = C).  nt_cfg: the bf16 x 3 kernel form (gemm_x3.h)
+void wino_gemm_nt(const WinoGeom& f, const float* A, const void* U, float* Cm, int nt_cfg, hipStream_t st) {
+    if (nt_x3(f)) launch_gemm_x3_nt_cfg(A, U, Cm, f.bins, f.M, f.N, f.C, nt_cfg, 0, st);
+    else launch_wino_gemm(A, (const float*)U, Cm, f.M, f.N, f.C, st);
+}
+
+// y = A^T m A + epilogue (f: the geometry whose OUTPUT is y)
+void wino_output(const WinoGeom& f, const float* Mo, float* y, int ldy, const WinoEp& ep, hipStream_t st) {
+    const dim3 grid(cdiv(f.M, 4) << f.nq_shift), blk(256);
+#define W4_OUT(A, Bn) hipLaunchKernelGGL((wino4_output_kernel<A, Bn>), grid, blk, 0, st, Mo, y, ldy, ep, f, f.N, f.nq_shift)
+    if (f.T != 4) hipLaunchKernelGGL(wino_output_kernel, grid, blk, 0, st, Mo, y, ldy, ep, f, f.N, f.nq_shift);
+    else if (ep.addsrc) { if (ep.bnb_y) W4_OUT(true, true); else W4_OUT(true, false); }
+    else { if (ep.bnb_y) W4_OUT(false, true); else W4_OUT(false, false); }
 #undef W4_OUT
 }
+
+// Dv = the weight gradient's transform of dy
+void wino_dy(const WinoGeom& f, const float* dy, int ldy, float* Dv, hipStream_t st) {
+    const dim3 grid(cdiv(f.M, 4) << f.nq_shift), blk(256);
+    if (f.T == 4) hipLaunchKernelGGL(wino4_dy_kernel, grid, blk, 0, st, dy, ldy, Dv, f);
+    else hipLaunchKernelGGL(wino_dy_kernel, grid, blk, 0, st, dy, ldy, Dv, f);
+}
+
+// P[split][bin] = sum over the split's tiles of Dv[bin]^T V[bin]
+void wino_gemm_tn(const WinoGeom& f, const float* Dv, const float* V, float* P, int ns, hipStream_t st) {
+    if (tn_x3(f)) launch_gemm_x3_tn(Dv, V, P, f.bins, f.M, f.N, f.C, ns, st);
+    else launch_wino_gemm_tn(Dv, V, P, f.M, f.N, f.C, ns, st);
+}
+
+// dw = the bins of P folded into the 9 taps, the ns partial sets summed in order
+void wino_tap_fold(const WinoGeom& f, const float* P, float* dw, int ns, hipStream_t st) {
+    const dim3 grid(cdiv(f.N * f.C, 256)), blk(256);
+    if (f.T == 4) hipLaunchKernelGGL(wino4_wgrad_output_kernel, grid, blk, 0, st, P, dw, f.N, f.C, ns, f.flip ? 1 : 0);
+    else hipLaunchKernelGGL(wino_wgrad_output_kernel, grid, blk, 0, st, P, dw, f.N, f.C, ns, f.flip ? 1 : 0);
+}
+
+// ---- the two chains of the backward.  Each starts with a transform of dy (wino_dy; wino_input on dgrad_geom), which the
+// two-stream form runs ahead of both; what follows touches disjoint memory when Dv / Vd and P / Eo are separate regions. ----
+
+// weight gradient, after wino_dy: Dv -> P -> dw   (V: the forward's saved input transform)
+void wgrad_chain(const WinoGeom& f, const float* Dv, const float* V, float* P, float* dw, hipStream_t st) {
+    const int ns = tn_splits(f);
+    wino_gemm_tn(f, Dv, V, P, ns, st);
+    wino_tap_fold(f, P, dw, ns, st);
+}
+
+// data gradient, after wino_input(fd, dy): Vd -> Eo -> dx (+ addsrc, BatchNorm-backward partials).  A reflection layer writes
+// the padded-domain gradient to `padded` and folds it onto dx, with the adjoint of the x2 upsampling when dx_up2x.
+void dgrad_chain(const WinoGeom& f, const WinoGeom& fd, const float* Vd, const void* Ud, float* Eo, float* padded, float* dx, int ldx,
+                 const float* addsrc, int ld_add, const float* bnb_y, int ld_bnb, const float* bnb_co, int bnb_relu,
+                 float* bnb_partial, int dx_up2x, int nt_cfg, hipStream_t st) {
+    wino_gemm_nt(fd, Vd, Ud, Eo, nt_cfg, st);
+    const WinoEp ep = {f.reflect ? nullptr : addsrc, ld_add, bnb_y ? bnb_partial : nullptr, nullptr, nullptr, 0,
+                       bnb_y, ld_bnb, bnb_co, bnb_relu};
+    wino_output(fd, Eo, f.reflect ? padded : dx, f.reflect ? f.C : ldx, ep, st);
+    if (f.reflect && dx_up2x)
+        // dx is the gradient of the LOW-resolution tensor the forward upsampled on load: fold + adjoint interpolation
+        hipLaunchKernelGGL(reflect_fold_up2x_kernel, dim3(fold_blocks((int64_t)f.B * (f.H / 2) * (f.W / 2) * (f.C / 4))), dim3(256), 0, st,
+                           (const void*)padded, (void*)dx, ldx, (const void*)addsrc, ld_add, f.B, f.H, f.W, f.C, 1, dx_up2x - 1, 0);
+    else if (f.reflect)
+        launch_wino_reflect_fold(padded, dx, ldx, addsrc, ld_add, f.B, f.H, f.W, f.C, st);
+}
+
+// ---- workspace layouts, one per entry point: byte offsets of the regions -- V (forward V / data gradient Vd), Dv, U, Mo (NT GEMM
+// output: forward Mo / data gradient Eo), P, the padded-domain gradient of a reflection layer -- and the total ----
+struct WinoWs { size_t V, Dv, U, Mo, P, padded, total; };
+inline size_t max2(size_t a, size_t b) { return a > b ? a : b; }
+inline float* ws_at(const void* base, size_t off) { return (float*)((char*)base + off); }
+
+inline WinoWs fwd_ws(const WinoGeom& f) {                  // V, U, Mo
+    WinoWs L = {};
+    L.U = v_bytes(f); L.Mo = L.U + u_bytes(f); L.total = L.Mo + m_bytes(f);
+    return L;
+}
+// single stream: Vd / Dv share, U', Eo / P share; a reflection layer's data gradient runs over the padded domain (more tiles)
+// and writes the padded gradient directly behind Eo's [bins][Md][C]
+inline WinoWs bwd_ws(const WinoGeom& f) {
+    const WinoGeom fd = dgrad_geom(f);
+    WinoWs L = {};
+    L.U = max2(v_bytes(fd), m_bytes(f)); L.Mo = L.P = L.U + u_bytes(f); L.padded = L.Mo + (size_t)f.bins * fd.M * f.C * 4;
+    L.total = L.Mo + max2(m_bytes(fd), p_bytes(f)) + (f.reflect ? al256((size_t)f.B * (f.H + 2) * (f.W + 2) * f.C * 4) : 0);
+    return L;
+}
+// two chains: Vd, Dv, P, Eo -- four SEPARATE regions, so that the weight-gradient chain (Dv -> P -> dw) and the data-gradient
+// chain (Vd -> Eo -> dx) touch disjoint memory once both transforms of dy have run
+inline WinoWs pair_ws(const WinoGeom& f) {
+    WinoWs L = {};
+    L.Dv = m_bytes(f); L.P = L.Dv + m_bytes(f); L.Mo = L.P + p_bytes(f); L.total = L.Mo + v_bytes(f);
+    return L;
+}
+// the layers the two-chain form is for: F(4x4,3x3) plans (zero padding, every GEMM bf16 x 3)
+inline bool pair_geom(const gdn_conv_geom* g, WinoGeom& f) { return wino_geom(g, f) && f.T == 4; }
 
 }  // namespace
 
@@ -871,10 +976,9 @@ extern "C" size_t gdn_winoconv_state_bytes(const gdn_conv_geom* g) {
     return wino_geom(g, f) ? v_bytes(f) + u_bytes(f) : 0;
 }
 
-// workspace: V, U, Mo
 extern "C" size_t gdn_winoconv_fwd_workspace_bytes(const gdn_conv_geom* g) {
     WinoGeom f;
-    return wino_geom(g, f) ? v_bytes(f) + u_bytes(f) + m_bytes(f) : 0;
+    return wino_geom(g, f) ? fwd_ws(f).total : 0;
 }
 
 extern "C" int64_t gdn_winoconv_stats_slots(const gdn_conv_geom* g) {
@@ -893,59 +997,25 @@ extern "C" int gdn_winoconv_fwd(const gdn_conv_geom* g, const float* x, int32_t 
     if (!wino_geom(g, f)) return GDN_ERR_UNSUPPORTED;
     if (!x || !w || !y || (!ep_scale) != (!ep_shift) || (!in_scale) != (!in_shift)) return GDN_ERR_BAD_ARG;
     if (in_up2x < 0 || in_up2x > 2 || (in_up2x && (in_scale || (g->H & 1) || (g->W & 1)))) return GDN_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < gdn_winoconv_fwd_workspace_bytes(g)) return GDN_ERR_WORKSPACE;
+    const WinoWs L = fwd_ws(f);
+    if (!workspace || workspace_bytes < L.total) return GDN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)workspace;
-    float* V = (float*)p; p += v_bytes(f);
-    float* U = (float*)p; p += u_bytes(f);
-    float* Mo = (float*)p;
-    if (state_out) V = (float*)state_out;
-    float* Usw = state_out ? (float*)((char*)state_out + v_bytes(f)) : nullptr;
-    if (f.T == 4) {
-        // F(4x4,3x3): every GEMM of the layer is a bf16 x 3 one (wino_geom); the data gradient's weight set rides along as above
-        launch_wino4_input(x, ldx, V, f, in_scale, in_shift, in_relu, in_up2x, st);
-        hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256), Usw ? 2 : 1), dim3(256), 0, st, w, (unsigned char*)U, f.N,
-                           f.C, f.flip, (unsigned char*)Usw, 1 | f.flip);
-        launch_gemm_x3_nt((const float*)V, U, Mo, f.bins, f.M, f.N, f.C, st);
-        launch_wino4_output((const float*)Mo, y, ldy, addsrc, ld_add, stats, ep_scale, ep_shift, act, f, f.N, f.nq_shift,
-                            (const float*)nullptr, 0, (const float*)nullptr, 0, st);
-        return gdn_launch_status();
-    }
-    hipLaunchKernelGGL(wino_input_kernel, dim3(cdiv(f.M, 4) << f.cq_shift), dim3(256), 0, st, x, ldx, V, f, in_scale, in_shift,
-                       in_relu, in_up2x);
-    // the per-bin GEMMs run as bf16 x 3 split products on the bf16 matrix pipe where the shape allows (gemm_x3.h); the data
-    // gradient's weight set (its GEMM has N = Cin) is written in the form ITS kernel will read
-    const bool x3f = f.x3 && gemm_x3_ok(f.M, f.N, f.C), x3d = f.x3 && gemm_x3_ok(f.M, f.C, f.N);
-    if (!x3f || (Usw && !x3d))
-        hipLaunchKernelGGL(wino_weights_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, w, x3f ? (float*)nullptr : U, f.N,
-                           f.C, f.flip, x3d ? (float*)nullptr : Usw);
-    if (x3f && Usw && x3d)
-        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256), 2), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, f.flip,
-                           (unsigned char*)Usw, 1 | f.flip);
-    else if (x3f)
-        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, f.flip,
-                           (unsigned char*)nullptr, 0);
-    else if (Usw && x3d)
-        hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)Usw, f.N, f.C, 1 | f.flip,
-                           (unsigned char*)nullptr, 0);
-    if (x3f) launch_gemm_x3_nt((const float*)V, U, Mo, WINO_BINS, f.M, f.N, f.C, st);
-    else launch_wino_gemm((const float*)V, (const float*)U, Mo, f.M, f.N, f.C, st);
-    hipLaunchKernelGGL(wino_output_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, (const float*)Mo, y, ldy, addsrc,
-                       ld_add, stats, ep_scale, ep_shift, act, f, f.N, f.nq_shift, (const float*)nullptr, 0,
-                       (const float*)nullptr, 0);
+    // a forward that will run backward writes V into the state and, behind it, the data gradient's weight set: the weights
+    // do not change between a step's forward and backward
+    float* V = state_out ? (float*)state_out : ws_at(workspace, L.V);
+    float* Usw = state_out ? ws_at(state_out, v_bytes(f)) : nullptr;
+    float* U = ws_at(workspace, L.U);
+    float* Mo = ws_at(workspace, L.Mo);
+    wino_input(f, x, ldx, V, in_scale, in_shift, in_relu, in_up2x, st);
+    wino_weights(f, w, U, Usw, st);
+    wino_gemm_nt(f, V, U, Mo, X3_NT_AUTO, st);
+    wino_output(f, Mo, y, ldy, WinoEp{addsrc, ld_add, stats, ep_scale, ep_shift, act, nullptr, 0, nullptr, 0}, st);
     return gdn_launch_status();
 }
 
-// workspace: Vd (transformed dy for the data gradient, [16][M][N]) / Dv (for the weight gradient, same size), U', Eo / P
 extern "C" size_t gdn_winoconv_bwd_workspace_bytes(const gdn_conv_geom* g) {
     WinoGeom f;
-    if (!wino_geom(g, f)) return 0;
-    // reflection layers run the data gradient over the padded domain: more tiles, plus the padded gradient itself
-    const size_t Md = f.reflect ? (size_t)f.B * cdiv(f.H + 2, 2) * cdiv(f.W + 2, 2) : (size_t)f.M;
-    const size_t vd = al256((size_t)f.bins * Md * f.N * 4), eo = al256((size_t)f.bins * Md * f.C * 4);
-    const size_t padded = f.reflect ? al256((size_t)f.B * (f.H + 2) * (f.W + 2) * f.C * 4) : 0;
-    const size_t pr = (size_t)tn_splits_max(f) * al256((size_t)f.bins * f.N * f.C * 4);   // weight-gradient products, one set per split
-    return (vd > m_bytes(f) ? vd : m_bytes(f)) + u_bytes(f) + (eo > pr ? eo : pr) + padded;
+    return wino_geom(g, f) ? bwd_ws(f).total : 0;
 }
 
 // slots of the BatchNorm-backward partials the data-gradient epilogue can emit (0: not available for this layer)
@@ -968,101 +1038,28 @@ extern "C" int gdn_winoconv_bwd(const gdn_conv_geom* g, const float* dy, int32_t
     if (dx && f.reflect && ((ldx % 4) || (addsrc && (ld_add % 4)))) return GDN_ERR_UNSUPPORTED;
     if (dx_up2x < 0 || dx_up2x > 2 || (dx_up2x && ((g->H & 1) || (g->W & 1)))) return GDN_ERR_BAD_ARG;
     if (dx && dx_up2x && !f.reflect) return GDN_ERR_UNSUPPORTED;   // (the fold pass of a reflection layer carries the adjoint)
-    if (!workspace || workspace_bytes < gdn_winoconv_bwd_workspace_bytes(g)) return GDN_ERR_WORKSPACE;
+    const WinoWs L = bwd_ws(f);
+    if (!workspace || workspace_bytes < L.total) return GDN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)workspace;
-    const size_t Md = f.reflect ? (size_t)f.B * cdiv(f.H + 2, 2) * cdiv(f.W + 2, 2) : (size_t)f.M;
-    const size_t vd = al256((size_t)f.bins * Md * f.N * 4);
-    float* Vd = (float*)p; p += (vd > m_bytes(f) ? vd : m_bytes(f));
-    float* U = (float*)p; p += u_bytes(f);
-    float* Eo = (float*)p;                       // data gradient: GEMM output [16][Md][C] (+ padded gradient); weight gradient: P
-    if (f.T == 4) {
-        if (dw) {
-            hipLaunchKernelGGL(wino4_dy_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, dy, ldy, Vd, f);
-            const int ns = tn_splits(f);
-            launch_gemm_x3_tn((const float*)Vd, (const float*)state, Eo, f.bins, f.M, f.N, f.C, ns, st);
-            hipLaunchKernelGGL(wino4_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)Eo, dw, f.N, f.C, ns, f.flip ? 1 : 0);
-        }
-        if (dx) {
-            WinoGeom fd = f;
-            fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift;
-            launch_wino4_input(dy, ldy, Vd, fd, nullptr, nullptr, 0, 0, st);
-            const float* Ud = U;
-            if (state) Ud = (const float*)((const char*)state + v_bytes(f));      // transformed by the forward's launch
-            else hipLaunchKernelGGL(wino4_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1 | f.flip,
-                                    (unsigned char*)nullptr, 0);
-            launch_gemm_x3_nt((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, st);
-            launch_wino4_output((const float*)Eo, dx, ldx, addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, nullptr, nullptr, 0,
-                                fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu, st);
-        }
-        return gdn_launch_status();
-    }
     if (dw) {
-        hipLaunchKernelGGL(wino_dy_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, dy, ldy, Vd, f);
-        const int ns = tn_splits(f);
-        if (tn_x3(f)) launch_gemm_x3_tn((const float*)Vd, (const float*)state, Eo, WINO_BINS, f.M, f.N, f.C, ns, st);
-        else launch_wino_gemm_tn((const float*)Vd, (const float*)state, Eo, f.M, f.N, f.C, ns, st);
-        hipLaunchKernelGGL(wino_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)Eo, dw, f.N, f.C, ns, f.flip ? 1 : 0);
+        wino_dy(f, dy, ldy, ws_at(workspace, L.Dv), st);
+        wgrad_chain(f, ws_at(workspace, L.Dv), (const float*)state, ws_at(workspace, L.P), dw, st);
     }
     if (dx) {
-        // the data gradient of a 3x3 layer is the same kind of convolution of dy with flipped, role-swapped taps: pad 1 onto
-        // the H x W input for a zero-padded layer; pad 2 onto the (H+2) x (W+2) padded domain for a reflection-padded one,
-        // whose border rows / columns are then folded back onto the rows they mirror
-        WinoGeom fd = f;
-        fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift; fd.reflect = 0;
-        float* out = dx;
-        int ld_out = ldx;
-        if (f.reflect) {
-            fd.Ho = f.H + 2; fd.Wo = f.W + 2; fd.pad_off = 2;
-            fd.tiles_y = cdiv(fd.Ho, 2); fd.tiles_x = cdiv(fd.Wo, 2); fd.M = f.B * fd.tiles_y * fd.tiles_x;
-            out = Eo + (size_t)WINO_BINS * fd.M * f.C;                 // padded-domain gradient, behind the GEMM output
-            ld_out = f.C;
-        }
-        hipLaunchKernelGGL(wino_input_kernel, dim3(cdiv(fd.M, 4) << fd.cq_shift), dim3(256), 0, st, dy, ldy, Vd, fd,
-                           (const float*)nullptr, (const float*)nullptr, 0, 0);
-        const float* Ud = U;
-        // (the forward decided the form of its saved set from the FORWARD tile count f.M; the padded-domain gradient of a
-        // reflection layer has more tiles but the same N and K, so eligibility is the same)
-        const bool x3d = f.x3 && gemm_x3_ok(f.M, f.C, f.N);
-        if (state) Ud = (const float*)((const char*)state + v_bytes(f));      // transformed by the forward's launch
-        else if (x3d) hipLaunchKernelGGL(wino_weights_x3_kernel, dim3(cdiv(f.N * f.C / 8, 256)), dim3(256), 0, st, w, (unsigned char*)U, f.N, f.C, 1 | f.flip,
-                                         (unsigned char*)nullptr, 0);
-        else hipLaunchKernelGGL(wino_weights_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, w, U, f.N, f.C, 1 | f.flip, (float*)nullptr);
-        if (x3d) launch_gemm_x3_nt((const float*)Vd, Ud, Eo, WINO_BINS, fd.M, f.C, f.N, st);
-        else launch_wino_gemm((const float*)Vd, Ud, Eo, fd.M, f.C, f.N, st);
-        hipLaunchKernelGGL(wino_output_kernel, dim3(cdiv(fd.M, 4) << fd.nq_shift), dim3(256), 0, st, (const float*)Eo, out, ld_out,
-                           f.reflect ? (const float*)nullptr : addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, 0, fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu);
-        if (f.reflect && dx_up2x) {
-            // dx is the gradient of the LOW-resolution tensor the forward upsampled on load: fold + adjoint interpolation
-            const int64_t nb = cdiv64((int64_t)f.B * (f.H / 2) * (f.W / 2) * (f.C / 4), 256);
-            hipLaunchKernelGGL(reflect_fold_up2x_kernel, dim3((unsigned)(nb < 65536 * 8 ? nb : 65536 * 8)), dim3(256), 0, st,
-                               (const void*)out, (void*)dx, ldx, (const void*)addsrc, ld_add, f.B, f.H, f.W, f.C, 1, dx_up2x - 1, 0);
-        } else if (f.reflect) {
-            const int64_t nb = cdiv64((int64_t)f.B * f.H * f.W * (f.C / 4), 256);
-            hipLaunchKernelGGL(wino_reflect_fold_kernel, dim3((unsigned)(nb < 65536 * 8 ? nb : 65536 * 8)), dim3(256), 0, st,
-                               (const float*)out, dx, ldx, addsrc, ld_add, f.B, f.H, f.W, f.C);
-        }
+        const WinoGeom fd = dgrad_geom(f);
+        wino_input(fd, dy, ldy, ws_at(workspace, L.V), nullptr, nullptr, 0, 0, st);
+        if (!state) wino_weights(f, w, nullptr, ws_at(workspace, L.U), st);
+        const float* Ud = state ? ws_at(state, v_bytes(f)) : ws_at(workspace, L.U);      // state: transformed by the forward's launch
+        dgrad_chain(f, fd, ws_at(workspace, L.V), Ud, ws_at(workspace, L.Mo), ws_at(workspace, L.padded), dx, ldx, addsrc, ld_add,
+                    bnb_y, ld_bnb, bnb_co, bnb_relu, bnb_partial, dx_up2x, X3_NT_AUTO, st);
     }
     return gdn_launch_status();
 }
 
 // ---- F(4x4,3x3) backward with both gradients, in phases a caller can put on two streams ----
-// workspace: Vd [36][M][N], Dv [36][M][N], P (tn_splits_max sets of [36][N][C]), Eo [36][M][C] -- four SEPARATE regions, where
-// gdn_winoconv_bwd lets Vd / Dv and P / Eo share: the weight-gradient chain (Dv -> P -> dw) and the data-gradient chain
-// (Vd -> Eo -> dx) touch disjoint memory once both transforms of dy have run.
-namespace {
-inline size_t pair_vd_bytes(const WinoGeom& f) { return al256((size_t)f.bins * f.M * f.N * 4); }
-inline size_t pair_p_bytes(const WinoGeom& f) { return (size_t)tn_splits_max(f) * al256((size_t)f.bins * f.N * f.C * 4); }
-inline size_t pair_eo_bytes(const WinoGeom& f) { return al256((size_t)f.bins * f.M * f.C * 4); }
-// the layers the two-chain form is for: F(4x4,3x3) plans (zero padding, every GEMM bf16 x 3)
-inline bool pair_geom(const gdn_conv_geom* g, WinoGeom& f) { return wino_geom(g, f) && f.T == 4; }
-}  // namespace
-
 extern "C" size_t gdn_winoconv_bwd_pair_workspace_bytes(const gdn_conv_geom* g) {
     WinoGeom f;
-    if (!pair_geom(g, f)) return 0;
-    return 2 * pair_vd_bytes(f) + pair_p_bytes(f) + pair_eo_bytes(f);
+    return pair_geom(g, f) ? pair_ws(f).total : 0;
 }
 
 extern "C" int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, int32_t ldy, const float* w, const void* state,
@@ -1079,32 +1076,20 @@ extern "C" int gdn_winoconv_bwd_pair(const gdn_conv_geom* g, const float* dy, in
     if (dx_up2x < 0 || dx_up2x > 2) return GDN_ERR_BAD_ARG;
     if (dx_up2x) return GDN_ERR_UNSUPPORTED;   // (as gdn_winoconv_bwd: only the fold pass of a reflection layer carries the adjoint)
     if (phases < 0 || phases > 7) return GDN_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < gdn_winoconv_bwd_pair_workspace_bytes(g)) return GDN_ERR_WORKSPACE;
+    const WinoWs L = pair_ws(f);
+    if (!workspace || workspace_bytes < L.total) return GDN_ERR_WORKSPACE;
     if (!phases) phases = 7;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)workspace;
-    float* Vd = (float*)p; p += pair_vd_bytes(f);
-    float* Dv = (float*)p; p += pair_vd_bytes(f);
-    float* P = (float*)p; p += pair_p_bytes(f);
-    float* Eo = (float*)p;
-    WinoGeom fd = f;
-    fd.C = f.N; fd.N = f.C; fd.cq_shift = f.nq_shift; fd.nq_shift = f.cq_shift;
+    const WinoGeom fd = dgrad_geom(f);
     if (phases & 1) {
-        launch_wino4_input(dy, ldy, Vd, fd, nullptr, nullptr, 0, 0, st);
-        hipLaunchKernelGGL(wino4_dy_kernel, dim3(cdiv(f.M, 4) << f.nq_shift), dim3(256), 0, st, dy, ldy, Dv, f);
+        wino_input(fd, dy, ldy, ws_at(workspace, L.V), nullptr, nullptr, 0, 0, st);
+        wino_dy(f, dy, ldy, ws_at(workspace, L.Dv), st);
     }
-    if (phases & 2) {
-        const int ns = tn_splits(f);
-        launch_gemm_x3_tn((const float*)Dv, (const float*)state, P, f.bins, f.M, f.N, f.C, ns, st);
-        hipLaunchKernelGGL(wino4_wgrad_output_kernel, dim3(cdiv(f.N * f.C, 256)), dim3(256), 0, st, (const float*)P, dw, f.N, f.C, ns, f.flip ? 1 : 0);
-    }
-    if (phases & 4) {
-        const float* Ud = (const float*)((const char*)state + v_bytes(f));
+    if (phases & 2) wgrad_chain(f, ws_at(workspace, L.Dv), (const float*)state, ws_at(workspace, L.P), dw, st);
+    if (phases & 4)
         // phase 4 without phase 2 is the forked form: the weight-gradient chain runs beside this GEMM on another stream
-        launch_gemm_x3_nt_cfg((const float*)Vd, Ud, Eo, f.bins, fd.M, f.C, f.N, X3_NT_AUTO | ((phases & 2) ? 0 : X3_NT_SHARED), 0, st);
-        launch_wino4_output((const float*)Eo, dx, ldx, addsrc, ld_add, bnb_y ? bnb_partial : (float*)nullptr, nullptr, nullptr, 0,
-                            fd, f.C, fd.nq_shift, bnb_y, ld_bnb, bnb_co, bnb_relu, st);
-    }
+        dgrad_chain(f, fd, ws_at(workspace, L.V), ws_at(state, v_bytes(f)), ws_at(workspace, L.Mo), nullptr, dx, ldx, addsrc, ld_add,
+                    bnb_y, ld_bnb, bnb_co, bnb_relu, bnb_partial, 0, X3_NT_AUTO | ((phases & 2) ? 0 : X3_NT_SHARED), st);
     return gdn_launch_status();
 }
 
@@ -1118,3 +1103,4 @@ extern "C" int gdn_winoconv_gemm(const gdn_conv_geom* g, const float* V, const f
     launch_wino_gemm(V, U, Mo, f.B * cdiv(f.H, 2) * cdiv(f.W, 2), f.N, f.C, (hipStream_t)stream);      // (F(2x2,3x3) tiles whatever the layer's plan)
     return gdn_launch_status();
 }
+

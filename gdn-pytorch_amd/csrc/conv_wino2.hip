@@ -157,7 +157,6 @@ struct W2Ep {
 // ---- form A output: y[3ty + i][3tx + j][n] = (A^T m A)[i][j];  stats slot = group of 4 tiles ----
 __global__ __launch_bounds__(256) void w2_output_a_kernel(const float* __restrict__ Mo, float* __restrict__ y, int ldy, W2Ep ep,
                                                           W2Geom g) {
-    __shared__ float red[256 * 2];
     int t, n;
     const bool live = wino_decode(g.Ma, g.yq, t, n);
     float s1 = 0.f, s2 = 0.f;
@@ -192,19 +191,7 @@ __global__ __launch_bounds__(256) void w2_output_a_kernel(const float* __restric
             }
         }
     }
-    if (ep.stats) {
-        red[threadIdx.x * 2] = s1; red[threadIdx.x * 2 + 1] = s2;
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a1 += red[(j * 64 + threadIdx.x) * 2]; a2 += red[(j * 64 + threadIdx.x) * 2 + 1]; }
-            const int slot = blockIdx.x >> g.yq;
-            const int ch = (blockIdx.x & ((1 << g.yq) - 1)) * 64 + threadIdx.x;
-            ep.stats[((size_t)slot * 2 + 0) * g.Cy + ch] = a1;
-            ep.stats[((size_t)slot * 2 + 1) * g.Cy + ch] = a2;
-        }
-    }
+    if (ep.stats) wino_stats_store(s1, s2, ep.stats, g.yq, g.Cy);
 }
 
 // ---- form B input: Vd[bin][t][c] = (B^T D B)[bin], D[p][q] = d[3ty - 1 + p][3tx - 1 + q] (zero outside) ----
@@ -244,7 +231,6 @@ __global__ __launch_bounds__(256) void w2_input_b_kernel(const float* __restrict
 // gradient, rows outside [0, Hout) dropped; off = 1: the (H+2) x (W+2) padded domain of a reflection layer) ----
 __global__ __launch_bounds__(256) void w2_output_b_kernel(const float* __restrict__ Eo, float* __restrict__ out, int ldo, W2Ep ep,
                                                           W2Geom g, int Hout, int Wout, int off) {
-    __shared__ float red[256 * 2];
     int t, n;
     const bool live = wino_decode(g.Mb, g.xq, t, n);
     float s1 = 0.f, s2 = 0.f;
@@ -286,19 +272,7 @@ __global__ __launch_bounds__(256) void w2_output_b_kernel(const float* __restric
                 }
             }
     }
-    if (ep.stats) {
-        red[threadIdx.x * 2] = s1; red[threadIdx.x * 2 + 1] = s2;
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a1 += red[(j * 64 + threadIdx.x) * 2]; a2 += red[(j * 64 + threadIdx.x) * 2 + 1]; }
-            const int slot = blockIdx.x >> g.xq;
-            const int ch = (blockIdx.x & ((1 << g.xq) - 1)) * 64 + threadIdx.x;
-            ep.stats[((size_t)slot * 2 + 0) * g.Cx + ch] = a1;
-            ep.stats[((size_t)slot * 2 + 1) * g.Cx + ch] = a2;
-        }
-    }
+    if (ep.stats) wino_stats_store(s1, s2, ep.stats, g.xq, g.Cx);
 }
 
 // ---- weight gradient, small-image operand: Dv[bin][t][n] = (A s A^T)[bin], s = the 3x3 tile of the small image (form A tiling) ----
@@ -560,9 +534,7 @@ extern "C" int gdn_wino2conv_bwd(const gdn_conv_geom* g, const float* dy, int32_
             // gradient over the (H+2) x (W+2) padded domain, then the border rows / columns folded onto the rows they mirror
             const W2Ep ep = {nullptr, 0, nullptr, nullptr, nullptr, 0};
             run_form_b(f, dy, ldy, w, 1, Vd, U, Eo, dxp, f.Cx, f.Hx + 2, f.Wx + 2, 1, ep, st);
-            const int64_t nb = cdiv64((int64_t)f.B * f.Hx * f.Wx * (f.Cx / 4), 256);
-            hipLaunchKernelGGL(wino_reflect_fold_kernel, dim3((unsigned)(nb < 65536 * 8 ? nb : 65536 * 8)), dim3(256), 0, st,
-                               (const float*)dxp, dx, ldx, addsrc, ld_add, f.B, f.Hx, f.Wx, f.Cx);
+            launch_wino_reflect_fold((const float*)dxp, dx, ldx, addsrc, ld_add, f.B, f.Hx, f.Wx, f.Cx, st);
         } else {
             const W2Ep ep = {addsrc, ld_add, nullptr, nullptr, nullptr, 0};
             run_form_b(f, dy, ldy, w, 1, Vd, U, Eo, dx, ldx, f.Hx, f.Wx, 0, ep, st);

@@ -10,6 +10,7 @@
 // as the path for consumers without such a loader (direct / bf16 kernels).
 #pragma once
 #include "common.h"
+#include "reflect_fold.h"
 
 namespace {
 
@@ -39,7 +40,7 @@ __device__ __forceinline__ float up2x_at(const float* __restrict__ r0, const flo
 
 // dx[b][iy][ix] (extent H/2 x W/2) = sum over the upsampled pixels (oy, ox) whose stencil touches (iy, ix) of
 // weight * F(oy, ox), F = the padded-domain gradient dxp [B][H+2p][W+2p][C] summed over the padded coordinates that reflect
-// onto (oy, ox)  (+ addsrc, low resolution).  H, W: the upsampled extent = the convolution's input extent.
+// onto (oy, ox) (reflect_sources, reflect_fold.h)  (+ addsrc, low resolution).  H, W: the upsampled extent = the convolution's input extent.
 // bf16: all three tensors hold bfloat16 (the bf16 layers' data gradient, round 5: gdn_conv_dgrad dx_up2x); sums in fp32.
 __global__ __launch_bounds__(256) void reflect_fold_up2x_kernel(const void* __restrict__ dxp, void* __restrict__ dx, int ldx,
                                                                 const void* __restrict__ addsrc, int ld_add,
@@ -59,20 +60,15 @@ __global__ __launch_bounds__(256) void reflect_fold_up2x_kernel(const void* __re
             up_src(oy, Hl, align, l, a0, a1);
             const float wy = (a0 == iy ? 1.f - l : 0.f) + (a1 == iy ? l : 0.f);
             if (wy == 0.f) continue;
-            int qy[3], ny = 0;
-            qy[ny++] = oy + p;
-            if (oy >= 1 && oy <= p) qy[ny++] = p - oy;
-            if (oy <= H - 2 && oy >= H - 1 - p) qy[ny++] = 2 * (H - 1) - oy + p;
+            int qy[3], qx[3];
+            const int ny = reflect_sources(oy, H, p, qy);
             for (int jx = 0; jx < 6; ++jx) {
                 const int ox = 2 * ix - 2 + jx;
                 if (ox < 0 || ox >= W) continue;
                 up_src(ox, Wl, align, l, a0, a1);
                 const float wx = (a0 == ix ? 1.f - l : 0.f) + (a1 == ix ? l : 0.f);
                 if (wx == 0.f) continue;
-                int qx[3], nx = 0;
-                qx[nx++] = ox + p;
-                if (ox >= 1 && ox <= p) qx[nx++] = p - ox;
-                if (ox <= W - 2 && ox >= W - 1 - p) qx[nx++] = 2 * (W - 1) - ox + p;
+                const int nx = reflect_sources(ox, W, p, qx);
                 f32x4 f4 = {0.f, 0.f, 0.f, 0.f};
                 for (int a = 0; a < ny; ++a)
                     for (int e = 0; e < nx; ++e)
@@ -112,18 +108,13 @@ __global__ __launch_bounds__(256) void reflect_fold_up2x8_kernel(const void* __r
         for (int jy = 0; jy < 6; ++jy) {
             if (wy[jy] == 0.f) continue;
             const int oy = 2 * iy - 2 + jy;
-            int qy[3], ny = 0;
-            qy[ny++] = oy + p;
-            if (oy >= 1 && oy <= p) qy[ny++] = p - oy;
-            if (oy <= H - 2 && oy >= H - 1 - p) qy[ny++] = 2 * (H - 1) - oy + p;
+            int qy[3], qx[3];
+            const int ny = reflect_sources(oy, H, p, qy);
 #pragma unroll
             for (int jx = 0; jx < 6; ++jx) {
                 if (wx[jx] == 0.f) continue;
                 const int ox = 2 * ix - 2 + jx;
-                int qx[3], nx = 0;
-                qx[nx++] = ox + p;
-                if (ox >= 1 && ox <= p) qx[nx++] = p - ox;
-                if (ox <= W - 2 && ox >= W - 1 - p) qx[nx++] = 2 * (W - 1) - ox + p;
+                const int nx = reflect_sources(ox, W, p, qx);
                 f32x4 f0 = {0.f, 0.f, 0.f, 0.f}, f1 = {0.f, 0.f, 0.f, 0.f};
                 for (int a = 0; a < ny; ++a)
                     for (int e = 0; e < nx; ++e) {

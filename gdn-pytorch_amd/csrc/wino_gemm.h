@@ -3,6 +3,7 @@
 // this header gets its own (anonymous-namespace) copy of the kernels.
 #pragma once
 #include "common.h"
+#include "reflect_fold.h"
 
 #define WINO_BINS 16
 #ifndef WINO_KC
@@ -19,6 +20,24 @@ __device__ __forceinline__ bool wino_decode(int M, int q_shift, int& t, int& c) 
     t = (blockIdx.x >> q_shift) * 4 + (threadIdx.x >> 6);
     c = (blockIdx.x & ((1 << q_shift) - 1)) * 64 + (threadIdx.x & 63);
     return t < M;
+}
+
+// Tail of the output transforms that emit per-channel partial sums (BatchNorm statistics, BatchNorm-backward sums): the block's
+// 4 tiles are summed per channel in fixed order and stored to the block's slot, stats[slot][2][Nout] (slot = group of 4 tiles).
+// Every thread of the block calls it (s1 = s2 = 0 for a dead tile).
+__device__ __forceinline__ void wino_stats_store(float s1, float s2, float* __restrict__ stats, int q_shift, int Nout) {
+    __shared__ float red[256 * 2];
+    red[threadIdx.x * 2] = s1; red[threadIdx.x * 2 + 1] = s2;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { a1 += red[(j * 64 + threadIdx.x) * 2]; a2 += red[(j * 64 + threadIdx.x) * 2 + 1]; }
+        const int slot = blockIdx.x >> q_shift;
+        const int ch = (blockIdx.x & ((1 << q_shift) - 1)) * 64 + threadIdx.x;
+        stats[((size_t)slot * 2 + 0) * Nout + ch] = a1;
+        stats[((size_t)slot * 2 + 1) * Nout + ch] = a2;
+    }
 }
 
 // Per-bin real GEMM  Cm[bin][m][n] = sum_k A[bin][m][k] * Bm[bin][n][k]  (both K-contiguous), fp32 MFMA.
@@ -198,33 +217,17 @@ void launch_wino_gemm(const float* A, const float* Bm, float* Cm, int M, int N, 
     hipLaunchKernelGGL((wino_gemm_kernel<WINO_KC, 64>), dim3(cdiv(M, 64) * (N / 64) * WINO_BINS), dim3(256), 0, st, A, Bm, Cm, M, N, K);
 }
 
-// dx[y][x] = sum of the padded-domain gradient over the padded coordinates that reflect onto (y, x)  (+ addsrc), pad 1
+// The pad-1 reflection fold of the Winograd data gradients.  p = 1 in the mirror rule (reflect_fold.h): padded row 0 mirrors
+// row 1, padded row H + 1 mirrors row H - 2.
 __global__ __launch_bounds__(256) void wino_reflect_fold_kernel(const float* __restrict__ dxp, float* __restrict__ dx, int ldx,
                                                                 const float* __restrict__ addsrc, int ld_add,
                                                                 int B, int H, int W, int C) {
-    const int Hp = H + 2, Wp = W + 2, c4n = C / 4;
-    const int64_t total = (int64_t)B * H * W * c4n;
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c4 = (int)(i % c4n);
-        int64_t t = i / c4n;
-        const int x = (int)(t % W); t /= W;
-        const int y = (int)(t % H), b = (int)(t / H);
-        int qy[3], qx[3], ny = 0, nx = 0;
-        qy[ny++] = y + 1;
-        if (y == 1) qy[ny++] = 0;                  // padded row 0 mirrors row 1
-        if (y == H - 2) qy[ny++] = H + 1;          // padded row H + 1 mirrors row H - 2
-        qx[nx++] = x + 1;
-        if (x == 1) qx[nx++] = 0;
-        if (x == W - 2) qx[nx++] = W + 1;
-        f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
-        for (int a = 0; a < ny; ++a)
-            for (int e = 0; e < nx; ++e)
-                s4 += *reinterpret_cast<const f32x4*>(dxp + ((size_t)(b * Hp + qy[a]) * Wp + qx[e]) * C + c4 * 4);
-        const size_t op = (size_t)(b * H + y) * W + x;
-        if (addsrc) s4 += *reinterpret_cast<const f32x4*>(addsrc + op * ld_add + c4 * 4);
-        *reinterpret_cast<f32x4*>(dx + op * ldx + c4 * 4) = s4;
-    }
+    reflect_fold_f32x4(dxp, dx, ldx, addsrc, ld_add, B, H, W, C, 1);
 }
-
+inline void launch_wino_reflect_fold(const float* dxp, float* dx, int ldx, const float* addsrc, int ld_add, int B, int H, int W, int C,
+                                     hipStream_t st) {
+    hipLaunchKernelGGL(wino_reflect_fold_kernel, dim3(fold_blocks((int64_t)B * H * W * (C / 4))), dim3(256), 0, st, dxp, dx, ldx,
+                       addsrc, ld_add, B, H, W, C);
+}
 
 }  // namespace

@@ -185,6 +185,19 @@ def test_dgrad_exact(gpu, case, kind):
             assert int(lib.gdn_conv_dgrad_workspace_bytes(ref, cfg)) > int(lib.gdn_conv_dgrad_workspace_bytes(ref, cfg | 0x800)) == 0
 
 
+# reflect_fold_scalar_kernel: the fold of a reflection layer whose input channels are no multiple of 4.  The network's 3- and
+# 1-channel layers need no data gradient, so nothing else runs it: 3 channels, 1 x 5 x 6 pixels, pad 1 and pad 3 -- at pad 3 rows
+# 1..3 are mirrored by BOTH borders (three sources per axis) and every branch of the mirror rule (csrc/reflect_fold.h) is taken.
+SCALAR_FOLD_CASES = [("fold_c3_k3_refl", 3, 64, 3, 1, 1, True, False, 1, 5, 6), ("fold_c3_k7_refl", 3, 64, 7, 1, 3, True, False, 1, 5, 6)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("case", SCALAR_FOLD_CASES, ids=[c[0] for c in SCALAR_FOLD_CASES])
+def test_dgrad_scalar_fold_exact(gpu, case, kind):
+    """Padded-domain gradient with pitch 3 in the fp32 workspace + the scalar fold, with and without addsrc."""
+    run_dgrad(gpu, case, kind, (0,))
+
+
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("name", ["rb_k9_64", "cb_k7s2_refl", "rb_k3_l3", "ctb_k4s2_b"])
 def test_kc64_exact(gpu, name, kind):

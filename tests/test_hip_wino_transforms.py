@@ -8,6 +8,11 @@ Two checks per case:
     arithmetic per element was not, so V, y, the BatchNorm partials, dx, dw and the BatchNorm-backward partials keep every bit;
   * against the float64 model of tests/test_winoconv_model_cpu.py at that file's bars: an output (y, dx) within 1e-4 of the
     model's rms, a weight gradient within 1e-4 of its largest entry.
+
+The generator's PLANS / UP2X_REFLECT cases run the same calls through every other plan the host side selects -- F(2x2,3x3)
+with the fp32 or bf16 x 3 GEMM per direction, the NO_X3 / NO_WINO_F4 hints, reflection padding (padded-domain data gradient and
+its fold, with and without the x2 upsampling's adjoint), flipped taps -- and get the bitwise check against the bits recorded
+before the host side was rebuilt as stage launchers and two chains.
 """
 import importlib.util
 import pathlib
@@ -37,10 +42,10 @@ def recorded():
 class Case:
     """Inputs (numpy), the library's outputs (numpy) and the float64 model's pieces (computed on first use, once)."""
 
-    def __init__(self, dev, g, up=False):
-        self.g, self.up = g, up
-        self.inp = G.inputs(g, up)
-        self.out = {k: v.detach().cpu().numpy() for k, v in (G.run_up2x if up else G.run)(dev, g, self.inp).items()}
+    def __init__(self, dev, g, up=False, plan=None):
+        self.g, self.up, self.plan = g, up, plan or {}
+        self.inp = G.inputs(g, up, up_bwd=up and plan is not None)
+        self.out = {k: v.detach().cpu().numpy() for k, v in (G.run_up2x if up else G.run)(dev, g, self.inp, plan).items()}
         B, ci, co = g[:3]
         self.x = self.inp["xw"][..., 32:32 + ci].astype(np.float64)
         self.w = self.inp["w"].astype(np.float64).reshape(3, 3, co, ci).transpose(2, 3, 0, 1)          # [N, C, 3, 3]
@@ -69,6 +74,17 @@ def case(gpu, request):
 @pytest.fixture(scope="module", params=G.UP2X, ids=[G.gid(g) for g in G.UP2X])
 def upcase(gpu, request):
     return Case(gpu, request.param, up=True)
+
+
+_PLANS = [(p, False) for p in G.PLANS] + [(p, True) for p in G.UP2X_REFLECT]
+
+
+@pytest.fixture(scope="module", params=_PLANS, ids=[p[0] for p, _ in _PLANS])
+def plancase(gpu, request):
+    (pid, g, plan), up = request.param
+    c = Case(gpu, g, up=up, plan=plan)
+    c.pid = pid
+    return c
 
 
 def assert_bits(c, recorded, prefix):
@@ -107,6 +123,29 @@ def test_bits_are_the_parents(case, recorded):
 
 def test_up2x_bits_are_the_parents(upcase, recorded):
     assert_bits(upcase, recorded, "up2x_")
+
+
+def test_plan_cases_run_the_plan_they_name(plancase):
+    """The library's own queries, under the case's switches: the two-chain backward exists for F(4x4,3x3) plans only, a
+    statistics slot is 4 tiles of the plan's tiling, and a reflection layer emits no BatchNorm-backward partials."""
+    from gdn_amd._lib import lib
+    B, ci, co, H, W = plancase.g
+    if plancase.up:
+        H, W = 2 * H, 2 * W
+    T = plancase.plan["T"]
+    with G.switches(plancase.plan):
+        op, nV = G.layer((B, ci, co, H, W), plancase.plan)
+        _, ref, _, _ = op.geom(B, H, W)
+        assert (lib.gdn_winoconv_bwd_pair_workspace_bytes(ref) > 0) == (T == 4)
+        assert lib.gdn_winoconv_stats_slots(ref) == (G.tiles(B, H, W, T) + 3) // 4
+        assert (op.wino_bnb_slots(B, H, W) == 0) == bool(plancase.plan.get("reflect"))
+    assert plancase.out["u1.V" if plancase.up else "f1.V"].size == nV
+
+
+def test_plan_bits_are_the_parents(plancase, recorded):
+    """Every output of every plan, bit for bit, as the library computed it before its host side became stage launchers."""
+    assert ("b1.part" in plancase.out) == (not plancase.up and not plancase.plan.get("reflect"))
+    assert_bits(plancase, recorded, plancase.pid + "_")
 
 
 def test_forward_plain_matches_model(case):
