@@ -12,7 +12,11 @@ takes its LOCAL_RANK GPU instead.
 The KITTI/NYU file pipeline (datasets_list.py / transform_list.py) is host I/O
 outside the hot path: pass ``--synthetic`` for KITTI-shaped random batches, or
 call ``run(args, train_loader, val_loader)`` with loaders that yield the
-reference's sample contract ``(gt[B,1,H,W], rgb[B,3,H,W], sparse[B,1,H,W])`` in [-1,1].
+reference's sample contract ``(gt[B,1,H,W], rgb[B,3,H,W], sparse[B,1,H,W])`` in [-1,1].  DATA is laid out like the
+reference's (``train.txt`` / ``val.txt`` naming scenes, per scene ``*.jpg``, ``gt/*.png`` sparse and ``color_gt2/*.png`` dense
+depth, bytes with 255 = ``--depth_scale`` metres; the three ``eigen_test_files_*.txt`` for ``--real_test``);
+``python -m gdn_amd.prepare_kitti RAW_ROOT DATA --train_list F ...`` writes that layout from a raw KITTI download, the dense
+maps filled from the LiDAR scans on the device.
 
 Evaluation (--mode DtoD_test / RtoD_test, :234-307): ``--real_test`` evaluates KITTI on the Eigen test split
 (TestFolder) instead of val.txt; ``--dataset NYU`` evaluates the NYU Depth v2 test set with compute_errors_NYU;

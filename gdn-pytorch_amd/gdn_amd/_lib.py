@@ -130,6 +130,9 @@ _SIGS = {
     "gdn_flip_w": (c_int32, [_P, _i64, _i32, _P, _P]),
     "gdn_flip_mean": (c_int32, [_P, _P, _i64, _i32, _P, _P]),
     "gdn_velo_project": (c_int32, [_P, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P]),
+    "gdn_depth_densify_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "gdn_depth_densify": (c_int32, [_P, _P, _i32, _i32, _i32, _f, _P, _P, _sz, _P]),
+    "gdn_depth_encode_u8": (c_int32, [_P, _i64, c_double, _i32, _P, _P]),
     "gdn_crop_normalize": (c_int32, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "gdn_bytescale_u8": (c_int32, [_P, _i32, _i32, _i32, _i32, _P, _P]),
     "gdn_nyu_augment_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
@@ -172,7 +175,8 @@ EXPORTS = tuple(_SIGS)
 # and gdn_bn_frozen_bwd*, the three gdn_*_seg entry points of the segmented Adam, gdn_lr_schedule, gdn_silog_masked and the
 # evaluation entry points gdn_depth_metrics_std*, gdn_flip_w and gdn_flip_mean, and the four gdn_adamw_step* entry points of
 # the decoupled weight decay, and gdn_step_record and gdn_tensor_sumsq* of the training log, and the kernel-form selector
-# gdn_gemm_x3_nt_cfg, and gdn_velo_project of the Velodyne ground truth, for the same reason.)
+# gdn_gemm_x3_nt_cfg, and gdn_velo_project of the Velodyne ground truth, and gdn_depth_densify* and gdn_depth_encode_u8 of the
+# training-set preparation, for the same reason.)
 ABI_VERSION = 223
 
 

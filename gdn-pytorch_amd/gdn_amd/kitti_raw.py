@@ -1,8 +1,9 @@
 """Raw KITTI on the host: the calibration files of a recording date and the lists that name Velodyne scans (--eval_velodyne,
 DESIGN.md 3.15).  numpy only; the projection itself runs on the device (ops.velo_project).
 
-A raw KITTI tree is ``ROOT/DATE/calib_cam_to_cam.txt``, ``ROOT/DATE/calib_velo_to_cam.txt`` and
-``ROOT/DATE/DRIVE/velodyne_points/data/%010d.bin`` (float32 x, y, z, reflectance per point)."""
+A raw KITTI tree is ``ROOT/DATE/calib_cam_to_cam.txt``, ``ROOT/DATE/calib_velo_to_cam.txt``,
+``ROOT/DATE/DRIVE/velodyne_points/data/%010d.bin`` (float32 x, y, z, reflectance per point) and, for the training-set
+preparation (gdn_amd.prepare_kitti), the colour frames ``ROOT/DATE/DRIVE/image_0C/data/%010d.png``."""
 import os
 import pathlib
 
@@ -86,6 +87,13 @@ def parse_velo_list(list_file, raw_root):
     ``DATE/DRIVE/image_0C/data/FRAME.png ...`` (camera C = 2 or 3) and ``DATE/DRIVE FRAME l|r`` (l: camera 2, r: camera 3).
     The scan is raw_root/DATE/DRIVE/velodyne_points/data/%010d.bin.  A line in neither format, a missing scan or a missing
     calibration file is a GdnError naming the file and the line."""
+    return [(f["scan"], f["date_dir"], f["cam"]) for f in parse_frame_list(list_file, raw_root, images=False)]
+
+
+def parse_frame_list(list_file, raw_root, images=True):
+    """parse_velo_list with everything a line names -> [{date, drive, frame, cam, scan, date_dir, image}, ...]: image is the
+    colour frame raw_root/DATE/DRIVE/image_0C/data/%010d.png, and with images=True a missing one is a GdnError like a missing
+    scan (gdn_amd.prepare_kitti)."""
     raw_root = pathlib.Path(raw_root)
     out = []
     with open(list_file) as f:
@@ -99,8 +107,10 @@ def parse_velo_list(list_file, raw_root):
                 raise GdnError("%s: neither DATE/DRIVE/image_0C/data/FRAME.png nor DATE/DRIVE FRAME l|r" % where)
             date, drive, frame, cam = parsed
             scan = raw_root / date / drive / "velodyne_points" / "data" / ("%010d.bin" % frame)
-            for need in (scan, *(raw_root / date / n for n in CALIB_FILES)):
+            image = raw_root / date / drive / ("image_0%d" % cam) / "data" / ("%010d.png" % frame)
+            for need in (scan, *(raw_root / date / n for n in CALIB_FILES), *((image,) if images else ())):
                 if not os.path.isfile(need):
                     raise GdnError("%s not found, named by %s" % (need, where))
-            out.append((scan, raw_root / date, cam))
+            out.append({"date": date, "drive": drive, "frame": frame, "cam": cam, "scan": scan, "date_dir": raw_root / date,
+                        "image": image})
     return out

@@ -1137,6 +1137,44 @@ def velo_project(points, offsets, proj, sizes, Hmax, Wmax, depth='camera', hits=
     return (out, count) if hits else out
 
 
+def depth_densify(pool, sizes, max_depth=100.0, out=None):
+    """gdn_depth_densify: pool float32 [B,Hmax,Wmax] metres (0 = no return; what velo_project returns) and sizes int32 [B,2]
+    = (h0, w0), dense and on the GPU -> the dense maps in a float32 pool of the same shape, the padding +0 (DESIGN.md
+    3.16).  out: a pool of that shape to write into (not the input), or None for a new one.  No sync, nothing is read on
+    the host."""
+    if not (pool.is_cuda and pool.dim() == 3 and pool.dtype == torch.float32 and pool.is_contiguous() and pool.numel() > 0):
+        raise GdnError("depth_densify: pool must be a dense [B,Hmax,Wmax] float32 tensor on the GPU")
+    B, Hmax, Wmax = (int(v) for v in pool.shape)
+    if not (sizes.is_cuda and sizes.dtype == torch.int32 and sizes.is_contiguous() and tuple(sizes.shape) == (B, 2)):
+        raise GdnError("depth_densify: sizes must be a dense int32 [B,2] tensor on the GPU for the %d images of the pool" % B)
+    max_depth = float(max_depth)
+    if not (0.2 < max_depth < float("inf")):
+        raise GdnError("depth_densify: max_depth %r is not a finite number above 0.2" % (max_depth,))
+    if out is None:
+        out = torch.empty_like(pool)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == pool.shape and
+              out.device == pool.device and out.data_ptr() != pool.data_ptr()):
+        raise GdnError("depth_densify: out must be another dense float32 tensor of the pool's shape on its device")
+    nb = int(lib.gdn_depth_densify_workspace_bytes(B, Hmax, Wmax))
+    ws = workspace(nb, pool.device, "densify")
+    lib.gdn_depth_densify(_p(pool), _p(sizes), B, Hmax, Wmax, max_depth, _p(out), _p(ws), nb, stream())
+    return out
+
+
+def depth_encode_u8(x, scale=80.0, keep_valid=False):
+    """gdn_depth_encode_u8: a dense float32 device tensor of metres -> uint8 of the same shape, rint(clamp(x, 0, scale) /
+    scale * 255) in double, half to even, NaN -> 0; keep_valid: an x > 0 that rounds to 0 becomes 1 (the sparse map, where
+    byte 0 means no LiDAR return)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0):
+        raise GdnError("depth_encode_u8: x must be a dense, non-empty float32 tensor on the GPU")
+    scale = float(scale)
+    if not (0.0 < scale < float("inf")):
+        raise GdnError("depth_encode_u8: scale %r is not a finite positive number" % (scale,))
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    lib.gdn_depth_encode_u8(_p(x), x.numel(), scale, 1 if keep_valid else 0, _p(out), stream())
+    return out
+
+
 def center_crop_offsets(in_h, in_w, out_h, out_w):
     """CenterCrop.get_params (transform_list.py:260-261): Python's round, i.e. half to even."""
     return int(round((in_h - out_h) / 2.)), int(round((in_w - out_w) / 2.))

@@ -1007,6 +1007,36 @@ int gdn_velo_project(const float* points, const int64_t* offsets, const double* 
                      int64_t max_points, int32_t Hmax, int32_t Wmax, int32_t depth_kind, float* depth, int32_t* hits,
                      void* stream);
 
+/* Sparse LiDAR depth -> dense depth, and the bytes of the training files (no reference counterpart).  All
+ * pointers are device memory.
+ *   depth    float[B][Hmax][Wmax] metres, 16-byte aligned, what gdn_velo_project leaves: 0 = no return.  Cells outside an
+ *            image's h0 x w0 are never read;
+ *   sizes    int32[B][2] = {h0, w0} of each image (held inside Hmax x Wmax); the CONTENTS are the caller's to check, as in
+ *            gdn_velo_project;
+ *   out      float[B][Hmax][Wmax], 16-byte aligned, not overlapping depth: every cell is written, the padding as +0;
+ *   workspace  gdn_depth_densify_workspace_bytes(B, Hmax, Wmax) bytes (one pool), 16-byte aligned, overlapping neither.
+ * The morphological completion of Ku, Harakeh and Waslander (2018), in float32, one IEEE operation per written operation,
+ * no contraction; empty(v) := !(v > 0.1f):
+ *   1 v = D > 0.1f ? max_depth - D : 0, then 0 where empty(v);  2 max over the 5 x 5 diamond (out-of-image 0);  3 max over
+ *   the 5 x 5 box (out-of-image 0), then min over it (out-of-image ignored);  4 where empty(v): the 7 x 7 box max;  5 rows
+ *   above a column's topmost non-empty row take its value;  6 where empty(v): the 31 x 31 box max;  7 where !empty(v): the
+ *   13th smallest of the 5 x 5 window, borders replicated;  8 where !empty(v): the [1 4 6 4 1] / 16 blur, rows then columns,
+ *   each ((((p0 + 4 p1) + 6 p2) + 4 p3) + p4) * 0.0625f, borders reflected without the edge sample (period 2 (n - 1); a
+ *   single row or column reads itself);  out = empty(v) ? +0 : max_depth - v.
+ * Four launches (steps 1-4, 5, 6, 7-8), no atomics, no allocation, no sync, no host read, capturable; two calls give the
+ * same bytes.  A NULL pointer, B outside 1 .. 65535, Hmax or Wmax < 1, Hmax * Wmax >= 2^31, a misaligned buffer, overlapping
+ * buffers, a short workspace, or a max_depth that is not finite or is <= 0.2 return GDN_ERR_BAD_ARG before any launch.
+ *
+ * gdn_depth_encode_u8: x float[n] metres (16-byte aligned) -> out uint8[n] (4-byte aligned),
+ *   q = rint(clamp(d, 0, scale) / scale * 255) in double, half to even, NaN -> 0; with keep_valid a d > 0 that rounds to 0
+ *   becomes 1 (byte 0 of a sparse map means no return).  One launch.  A NULL pointer, n < 1, a scale that is not finite or
+ *   not > 0, keep_valid outside 0 .. 1 or a misaligned buffer return GDN_ERR_BAD_ARG before the launch.
+ * Added WITHOUT a new ABI revision, like gdn_grad_accumulate and for the same reason. */
+size_t gdn_depth_densify_workspace_bytes(int32_t B, int32_t Hmax, int32_t Wmax);
+int gdn_depth_densify(const float* depth, const int32_t* sizes, int32_t B, int32_t Hmax, int32_t Wmax, float max_depth,
+                      float* out, void* workspace, size_t workspace_bytes, void* stream);
+int gdn_depth_encode_u8(const float* x, int64_t n, double scale, int32_t keep_valid, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): the shader clock the chip holds WHILE a window of launches runs, so a
  * roofline fraction can be read against the clock of the box it was measured on (bench.py `clock_ghz`, `frac_at_clock`).
